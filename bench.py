@@ -7,7 +7,12 @@ iterative PnP with the motion-model extrinsic guess.  A step = one frame of ever
 pyramid(new frame) -> LK(prev corners) -> solvePnP(guess) -> gate -> motion model, all on
 the device (agt_track_frame), frames already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|c3pairs|c4|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|c3pairs|c4|c5] [--dump-outputs DIR] [--full]
+
+    A plain run sets up, warms up (an untimed rehearsal of the timed path, Bench.settle, then W steps), times ONE block of exactly
+    K steps, writes the last step's outputs when --dump-outputs is given and prints the result line.  --full adds everything else:
+    15 timed blocks (median / p10 / p90), the roofline and per-kernel passes, the side measurements of the other configurations,
+    the CPU baselines and the checks against them.
 
     --gpus N > 1 invoked plainly: this process starts N fresh ranks (python -m torch.distributed.run, rendezvous on
     127.0.0.1) BEFORE anything touches a GPU, relays rank 0's JSON line and exits with the job's code.  Launched by
@@ -18,7 +23,7 @@ read as streams: previous pyramid cached, 1,441,008 B per stream-frame); c3pairs
 64 COLD frame pairs per step, both pyramids built, 2,650,608 B per pair = 169,638,912 B per batch (bench_pairs.py); c4 = 1 x 1920x1080 stream per GPU (configs[3]); c5 = 1280x720, 60 tags / 240 corners + dense photometric
 refinement per frame (configs[4]).
 
-Timing: W untimed warm-up steps, then R blocks (default 15) of EXACTLY K steps each, every block bracketed by barrier +
+Timing: W untimed warm-up steps, then R blocks (default 1; 15 with --full) of EXACTLY K steps each, every block bracketed by barrier +
 torch.cuda.synchronize() on both sides and including the pipeline drain and the one pose gather; the per-block time is the MAX
 over ranks.  ms_per_step / value come from the MEDIAN block; p10 / p90 are reported beside it.
 
@@ -39,6 +44,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 REDETECT = 600            # frames between detector refreshes of the corner set (drift control, see Bench.refresh)
+SETTLE_S, SETTLE_STEPS = 0.25, 2 * REDETECT     # plain runs: untimed rehearsal of the timed path before its one block (Bench.settle)
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 LEVELS, WIN = 3, 21
 
@@ -102,6 +108,20 @@ def pingpong(i, nf):
 def percentiles(samples):
     a = np.sort(np.asarray(samples, np.float64))
     return float(np.median(a)), float(np.percentile(a, 10)), float(np.percentile(a, 90))
+
+
+def block_statistic(dts):
+    return "median block, max over ranks per block" if len(dts) > 1 else "the one timed block, max over ranks"
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as DIR/<name>.npy (float32 / float64, 64 MB at most)"""
+    arrays = {n: np.ascontiguousarray(a) for n, a in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {n: a.dtype for n, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "outputs to dump exceed 64 MB"
+    os.makedirs(dirpath, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirpath, n + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -298,10 +318,29 @@ class Bench:
             self.pos += m; self.since += m; k += m
 
     # -- the measurement the contract asks for
-    def timed_blocks(self, D, R):
+    def settle(self, state_w, state):
+        """Plain runs (one timed block): the timed path -- restart, warm-up, block, with the same record buffers -- rehearsed untimed
+        until the device has run it for SETTLE_S seconds, at least once, warm-up and block cut to SETTLE_STEPS steps each: clocks up and
+        every buffer, view and launch of the block in place, as they are in the median block of a --full run.  The timed run then
+        starts again from frame 0, so its records do not depend on how often this ran."""
+        w, m = min(self.Wm, SETTLE_STEPS), min(self.K, SETTLE_STEPS)
+        out_w, out = state_w[:w], (state if m == self.K else state[:m])
+        t0 = time.perf_counter()
+        while True:
+            self.restart()
+            self.run(w, out_w)
+            self.run(m, out)
+            self.trk.join()
+            self.sync()
+            if time.perf_counter() - t0 >= SETTLE_S:
+                break
+
+    def timed_blocks(self, D, R, settle=False):
         torch, K = self.torch, self.K
         state_w = torch.zeros((max(self.Wm, 1), self.B, 16), dtype=torch.float64, device=self.dev)
         state = torch.zeros((K, self.B, 16), dtype=torch.float64, device=self.dev)
+        if settle:
+            self.settle(state_w, state)
         self.restart()
         self.run(self.Wm, state_w[:self.Wm])
         self.trk.join()
@@ -369,7 +408,8 @@ def main():
     ap.add_argument("--no-pair-build", action="store_true", help="c3pairs: two agt_pyramid_build calls per batch (the form of rounds 3-5) instead of one agt_pyramid_build_pair")
     ap.add_argument("--pair-contexts", type=int, default=4, help="c3pairs: contexts / streams the independent batches are pipelined over (1 = serial)")
     ap.add_argument("--per-step-calls", action="store_true", help="hand the frames over one agt_track_frame call at a time instead of as clips")
-    ap.add_argument("--blocks", type=int, default=15, help="timed blocks of --steps steps each (median / p10 / p90 over them)")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps each (median / p10 / p90 over them); "
+                                                             "default 1, so that --steps is the number of timed steps, 15 with --full")
     ap.add_argument("--streams", type=int, default=None, help="independent streams per GPU (default: the workload's)")
     ap.add_argument("--render-frames", type=int, default=24)
     ap.add_argument("--depth", type=int, default=0,
@@ -379,10 +419,17 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="TEST HOOK (CPU, gloo): launcher + rendezvous + block timing + gather with a stub tracker; the line it prints "
                          "is marked data = dry-run and is not a measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: 15 timed blocks, roofline / per-kernel passes, the side measurements (c2: 64 streams, "
+                         "cold pairs, c5, H2D-inclusive rate, latencies), the CPU baselines and the pose checks against them and the truth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path handed its caller in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-extras", "--no-batch-extra", dest="no_extras", action="store_true",
-                    help="skip the side measurements (64-stream HBM-bound step, H2D-inclusive rate, per-call latencies)")
+                    help="--full: skip the side measurements (64-stream HBM-bound step, H2D-inclusive rate, per-call latencies)")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 15 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                         # does not return
 
@@ -390,7 +437,7 @@ def main():
     # GPU: beside an idle parent that holds contexts and queues the same command read 2 % slower on one box (43.18 against 42.34 us per step,
     # profiles/r06_final_c2k20_bench.json / r06_final_c3pairs_bench.json) -- the process then has the device to itself, as the stand-alone workload does
     pre_pairs = None
-    if (args.workload == "c2" and not args.no_extras and not args.dry_run and args.gpus == 1
+    if (args.full and args.workload == "c2" and not args.no_extras and not args.dry_run and args.gpus == 1
             and int(os.environ.get("WORLD_SIZE", "1")) == 1):
         pre_pairs = pairs_extra(args)
 
@@ -420,43 +467,21 @@ def main():
     auto_depth = min(K, 32)           # chained launches: a short block is ONE launch deep (plus the pyramid launch ahead of it)
     depth = max(1, min(args.depth or (auto_depth if fused else min(K, 16)), 32))      # split mode (not fused): two launches per group of `depth` frames
     bench.trk.pipeline(depth)
-    dts, st_warm, st_first, st_last, gathered = bench.timed_blocks(D, max(1, args.blocks))
+    dts, st_warm, st_first, st_last, gathered = bench.timed_blocks(D, max(1, args.blocks), settle=not args.full)
     med, p10, p90 = percentiles(dts)
     fps = world * B * K / med
     accepted = float(st_last[:, :, HL.ST_OK].mean())
     iters = float(st_last[:, :, HL.ST_ITERS].mean())
 
+    if rank == 0 and args.dump_outputs:
+        # the per-stream state records (hiplib.ST_*) every rank received for the last timed step, in rank order
+        dump_outputs(args.dump_outputs, {"records": gathered[:, K - 1].cpu().numpy()})
+
     if rank == 0:
-        ab = algorithmic_bytes(bench.W, bench.H, NPTS)
-        M = max(depth, min(K, 200) // depth * depth)      # instrumented passes: whole launch groups, at least one
-        stage_us = bench.stage_spans_us(HL, M)            # separate kernels, second (instrumented) pass
-        names = ["pyramid", "lk", "pnp"]
-        if fused:
-            launch_us = bench.launch_period_us(depth, M)
-            launch_us_d1 = bench.launch_period_us(1, M) if depth != 1 else launch_us
-            achieved = depth * B * ab["frame"] / (launch_us * 1e-6) / 1e9
-            roof = {"bound": "hbm", "kernel": "step_kernel<21,4,3> (fused: LK | PnP chained to it | pyrDown of the next group, %d consecutive frames per launch)" % depth,
-                    "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                    "traffic": pmc_traffic("step_kernel<21,4,3> depth %d" % depth, launch_us) if (B == 1 and args.workload == "c2") else None,
-                    "frac_of_measured_copy_6290GBs": round(achieved / 6290.0, 6),
-                    "avg_launch_us": round(launch_us, 3), "frames_per_launch": depth, "bytes_per_launch": int(depth * B * ab["frame"]),
-                    "one_frame_per_launch": {"avg_launch_us": round(launch_us_d1, 3), "frames_per_s": round(B / (launch_us_d1 * 1e-6), 1)},
-                    "note": "latency-bound by construction: one stream is a serial chain of ~10 LK and 4 LM iterations per frame"}
-        else:
-            dom = int(np.argmax(stage_us))
-            launches = {"pyramid": LEVELS - 1, "lk": 1, "pnp": 1}[names[dom]]
-            kernel_us = float(stage_us[dom]) / launches
-            achieved = B * ab[names[dom]] / launches / (kernel_us * 1e-6) / 1e9
-            whole = B * ab["frame"] / (med / K) / 1e9
-            roof = {"bound": "hbm", "kernel": {"pyramid": "pyr_group_kernel (register-rolling pyrDown, both levels in one pass since round 5)", "lk": "lk_kernel<21,1,3>", "pnp": "pnp_kernel<float,1>"}[names[dom]],
-                    "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                    "traffic": None, "avg_launch_us": round(kernel_us, 3), "bytes_per_launch": int(B * ab[names[dom]] / launches),
-                    "whole_step": {"algorithmic_GBs": round(whole, 1), "frac_of_8TBs": round(whole / HBM_PEAK_GBS, 4),
-                                   "bytes_per_step": int(B * ab["frame"])}}
-        roof["separate_kernel_spans_us"] = {n: round(float(v), 3) for n, v in zip(names, stage_us)}
+        roof = roofline(bench, HL, args, depth, fused, med) if args.full else None
 
         extras = {}
-        if args.workload == "c2" and world == 1 and not args.no_extras:
+        if args.full and args.workload == "c2" and world == 1 and not args.no_extras:
             # (order matters: the 64-stream step runs its stages on three library streams beside the caller's; a fifth stream --
             # the copy stream of the H2D measurement -- would make two of them share a hardware queue and serialise)
             ring = bench.ring; bench.ring = None
@@ -471,7 +496,7 @@ def main():
             extras["drop_in_frame_latency_us"] = drop_in_latency(bench)
 
         cpu = pose_err = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu, pose_err = cpu_baseline(bench.seqs[0], bench.rendered[:, 0], np.concatenate([st_warm[:Wm, 0], st_first[:, 0]]), Wm, K, bench.NF)
         out = {"metric": "frames/sec (LK+PnP) on 1280x720 dodeca stream", "value": round(fps, 2), "unit": "frames/s",
                "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(med / K * 1e3, 5),
@@ -483,7 +508,7 @@ def main():
                           "launch": ("fused chained step, %d frames per launch: pyramid of the next group | LK | PnP one frame behind LK (arrival counters); "
                                      "frames handed over as clips (agt_track_frames)%s" % (depth, " -- one call per frame" if args.per_step_calls else "")) if fused else
                                     "split pipeline: pyramid launch per group (caller's stream) | per-frame LK launches, half the streams each on two library streams | PnP launch per group (library stream), %d frames per group" % depth},
-               "timing": {"blocks": len(dts), "steps_per_block": K, "statistic": "median block, max over ranks per block",
+               "timing": {"blocks": len(dts), "steps_per_block": K, "statistic": block_statistic(dts),
                           "ms_per_step_p10": round(p10 / K * 1e3, 5), "ms_per_step_p90": round(p90 / K * 1e3, 5),
                           "value_p10": round(world * B * K / p90, 2), "value_p90": round(world * B * K / p10, 2)},
                "roofline": roof, "cpu_baseline": cpu,
@@ -494,7 +519,7 @@ def main():
         # `value` is a clip rate (frames handed over in clips, `depth` per launch); the figures comparable to the
         # reference's live frame-by-frame loop sit beside it at the top level
         out["pose_latency_frames_max"] = 2 * depth if fused else 4 * depth      # pyramid launch -> chained LK | PnP launch (split: pyramid, LK, PnP a group apart + slack)
-        if fused:
+        if fused and roof:
             out["one_frame_per_launch_fps"] = roof["one_frame_per_launch"]["frames_per_s"]
         if "live_frame_latency_us" in extras:
             out["live_frame_us_median"] = extras["live_frame_latency_us"]["median"]
@@ -509,7 +534,7 @@ def main():
                                               "a reported ratio, not the target (the roofline fraction is)"}
         out["rccl_ranks"] = world
         out["dist_backend"] = D.backend_name()
-        if world > 1:
+        if args.full and world > 1:
             # block q of the gathered records carries rank q's streams (seeds 1000 q + s): poses against each stream's own trajectory
             ok_g, worst = gather_order_check(gathered.cpu().numpy(), world, B, bench.nseq, bench.NF, bench.z0, bench.block_start, bench.ring_slots, 5e-3)
             out["gather_order_ok"] = ok_g
@@ -518,6 +543,40 @@ def main():
             out["rehearsal"] = True
         print(json.dumps(out), flush=True)
     D.barrier()
+
+
+def roofline(bench, HL, args, depth, fused, med):
+    """--full: the kernel under the roofline from instrumented passes of their own (separate-kernel spans; fused: the launch period
+    at `depth` and at one frame per launch)"""
+    B, K, NPTS = bench.B, bench.K, bench.npts
+    ab = algorithmic_bytes(bench.W, bench.H, NPTS)
+    M = max(depth, min(K, 200) // depth * depth)      # instrumented passes: whole launch groups, at least one
+    stage_us = bench.stage_spans_us(HL, M)            # separate kernels, second (instrumented) pass
+    names = ["pyramid", "lk", "pnp"]
+    if fused:
+        launch_us = bench.launch_period_us(depth, M)
+        launch_us_d1 = bench.launch_period_us(1, M) if depth != 1 else launch_us
+        achieved = depth * B * ab["frame"] / (launch_us * 1e-6) / 1e9
+        roof = {"bound": "hbm", "kernel": "step_kernel<21,4,3> (fused: LK | PnP chained to it | pyrDown of the next group, %d consecutive frames per launch)" % depth,
+                "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "traffic": pmc_traffic("step_kernel<21,4,3> depth %d" % depth, launch_us) if (B == 1 and args.workload == "c2") else None,
+                "frac_of_measured_copy_6290GBs": round(achieved / 6290.0, 6),
+                "avg_launch_us": round(launch_us, 3), "frames_per_launch": depth, "bytes_per_launch": int(depth * B * ab["frame"]),
+                "one_frame_per_launch": {"avg_launch_us": round(launch_us_d1, 3), "frames_per_s": round(B / (launch_us_d1 * 1e-6), 1)},
+                "note": "latency-bound by construction: one stream is a serial chain of ~10 LK and 4 LM iterations per frame"}
+    else:
+        dom = int(np.argmax(stage_us))
+        launches = {"pyramid": LEVELS - 1, "lk": 1, "pnp": 1}[names[dom]]
+        kernel_us = float(stage_us[dom]) / launches
+        achieved = B * ab[names[dom]] / launches / (kernel_us * 1e-6) / 1e9
+        whole = B * ab["frame"] / (med / K) / 1e9
+        roof = {"bound": "hbm", "kernel": {"pyramid": "pyr_group_kernel (register-rolling pyrDown, both levels in one pass since round 5)", "lk": "lk_kernel<21,1,3>", "pnp": "pnp_kernel<float,1>"}[names[dom]],
+                "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "traffic": None, "avg_launch_us": round(kernel_us, 3), "bytes_per_launch": int(B * ab[names[dom]] / launches),
+                "whole_step": {"algorithmic_GBs": round(whole, 1), "frac_of_8TBs": round(whole / HBM_PEAK_GBS, 4),
+                               "bytes_per_step": int(B * ab["frame"])}}
+    roof["separate_kernel_spans_us"] = {n: round(float(v), 3) for n, v in zip(names, stage_us)}
+    return roof
 
 
 def dry_run(args, torch, D, rank, world):
@@ -530,6 +589,8 @@ def dry_run(args, torch, D, rank, world):
     # frame numbers of the LAST block -- the same check the real multi-rank run applies to its records
     ok, _ = gather_order_check(g, world, bench.B, bench.nseq, bench.NF, bench.z0, bench.block_start, bench.ring_slots, 1e-12)
     ok = ok and bool((np.diff(g[0, :, 0, 8]) == 1).all()) and all(np.abs(g[q, :, :, :6] - g[0, :, :, :6]).max() > 1e-4 for q in range(1, world))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"records": g[:, bench.K - 1]})
     if rank == 0:
         print(json.dumps({"metric": "frames/sec (LK+PnP) on 1280x720 dodeca stream", "value": round(world * bench.B * bench.K / med, 2),
                           "unit": "frames/s", "n_gpus": world, "steps": bench.K, "warmup": bench.Wm, "ms_per_step": round(med / bench.K * 1e3, 5),
@@ -686,7 +747,7 @@ def pairs_extra(args):
     --workload c3pairs."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "AGT_DIST_BACKEND")}
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c3pairs", "--steps", "1024", "--warmup", "32", "--blocks", "15",
-           "--render-frames", str(args.render_frames), "--no-cpu-baseline"]
+           "--render-frames", str(args.render_frames), "--full", "--no-cpu-baseline"]
     try:
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -697,16 +758,16 @@ def pairs_extra(args):
         return {"error": repr(e)}
     keep = ("metric", "value", "unit", "steps", "ms_per_step", "config", "timing", "roofline", "max_abs_pose_err_vs_truth", "tracked_frac")
     res = {k: out[k] for k in keep}
-    res["note"] = "child process of this command (python bench.py --workload c3pairs --steps 1024 --warmup 32 --blocks 15 --no-cpu-baseline)"
+    res["note"] = "child process of this command (python bench.py --workload c3pairs --steps 1024 --warmup 32 --blocks 15 --full --no-cpu-baseline)"
     return res
 
 
 def c5_extra(args):
     """BASELINE.json configs[4] on the driver-timed line (c5 was builder-run only): 1280x720, 60 tags / 240 corners,
     LK + PnP + dense photometric refinement (61,440 samples, 5 Gauss-Newton iterations) + corner re-seed per frame -- the c5 workload's
-    own default measurement (15 blocks of 400 steps), as a child process of this command (its own context and streams, like pairs64_hbm)."""
+    own --full measurement (15 blocks of 400 steps), as a child process of this command (its own context and streams, like pairs64_hbm)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "AGT_DIST_BACKEND")}
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c5", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c5", "--full", "--no-cpu-baseline"]
     try:
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -717,7 +778,7 @@ def c5_extra(args):
         return {"error": repr(e)}
     keep = ("metric", "value", "unit", "steps", "ms_per_step", "config", "timing", "roofline", "accepted_frac", "refined_frac", "tracked_corners_mean", "max_abs_pose_err_vs_truth")
     res = {k: out[k] for k in keep if k in out}
-    res["note"] = "child process of this command (python bench.py --workload c5 --no-cpu-baseline)"
+    res["note"] = "child process of this command (python bench.py --workload c5 --full --no-cpu-baseline)"
     return res
 
 

@@ -46,18 +46,23 @@ def main_c5(args, torch, D, HL, wl, rank, world, dev, rehearsal):
                 trk.step_dense(bench.ring[a], out[k] if out is not None else None, dense[d0])
             bench.pos += m; k += m
     bench.run = run                 # no detector refresh: the re-seed from the refined pose is the drift control here
-    dts, st_warm, st_first, st_last, gathered = bench.timed_blocks(D, max(1, args.blocks))
+    dts, st_warm, st_first, st_last, gathered = bench.timed_blocks(D, max(1, args.blocks), settle=not args.full)
     med, p10, p90 = B_.percentiles(dts)
     fps = world * B * K / med
     dn = dense.cpu().numpy()[:K]
     accepted = float(st_last[:, :, HL.ST_OK].mean())
-    # accuracy against the generator's truth: PnP pose vs refined pose, last block
-    err_pnp, err_ref = [], []
-    for k in range(K):
-        i = B_.pingpong(bench.pos - K + 1 + k, bench.NF)
-        tr = np.concatenate([sq.rvecs[i], sq.tvecs[i]])
-        err_pnp.append(np.abs(st_last[k, 0, :6] - tr).max()); err_ref.append(np.abs(dn[k, 0, :6] - tr).max())
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        # what the caller received for the last timed step: the state records of every rank, this rank's dense records
+        B_.dump_outputs(args.dump_outputs, {"records": gathered[:, K - 1].cpu().numpy(), "dense_records": dn[K - 1]})
+    if args.full:
+        # accuracy against the generator's truth: PnP pose vs refined pose, last block
+        err_pnp, err_ref = [], []
+        for k in range(K):
+            i = B_.pingpong(bench.pos - K + 1 + k, bench.NF)
+            tr = np.concatenate([sq.rvecs[i], sq.tvecs[i]])
+            err_pnp.append(np.abs(st_last[k, 0, :6] - tr).max()); err_ref.append(np.abs(dn[k, 0, :6] - tr).max())
+    roof = cpu = None
+    if rank == 0 and args.full:
         # per-kernel spans of an instrumented pass (HIP events on the launch stream, recorded by the library)
         Mf = min(K, 100)
         bench.restart()
@@ -80,20 +85,20 @@ def main_c5(args, torch, D, HL, wl, rank, world, dev, rehearsal):
                                    "dense_gauss_newton(x%d launches)" % ITERS: round(float(spans[3]), 2), "dense_final(update+reseed)": round(float(spans[4]), 2)},
                 "stage_spans_note": "instrumented pass: every stage a launch of its own (HIP events between them); the timed blocks run LK | PnP as one "
                                     "chained launch with the previous frame's final step as the LK prologue, so their frame is shorter than the sum of these spans"}
-        cpu = None
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_c5(sq, bench.rendered[:, 0], mx, T, bench.NF)
+    if rank == 0:
         out = {"metric": "frames/sec (LK+PnP+dense refinement) on 1280x720 60-tag stream", "value": round(fps, 2), "unit": "frames/s",
                "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(med / K * 1e3, 5),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/i64 (LK), f64 (PnP, dense GN)",
                "data": "synthetic",
                "config": {"workload": wl["label"] % B, "streams_per_gpu": B, "dense_samples": M, "gn_iterations": ITERS, "photo_weight": PHOTO_WEIGHT,
                           "corner_reseed": True, "launch": ("frames handed over as clips (agt_track_frames_dense): %d launches per frame -- one chained launch [previous frame's last Gauss-Newton update + corner re-seed as the LK workgroups' prologue | LK | four-wave PnP behind the arrival count | the next frame's pyramid pass], then the %d accumulate launches" % (1 + ITERS, ITERS)) if bench.clips else ("stage kernels in stream order, one call per frame (%d launches per frame)" % (3 + ITERS + 1))},
-               "timing": {"blocks": len(dts), "steps_per_block": K, "statistic": "median block, max over ranks per block",
+               "timing": {"blocks": len(dts), "steps_per_block": K, "statistic": B_.block_statistic(dts),
                           "ms_per_step_p10": round(p10 / K * 1e3, 5), "ms_per_step_p90": round(p90 / K * 1e3, 5)},
                "roofline": roof, "cpu_baseline": cpu, "accepted_frac": round(accepted, 4),
                "refined_frac": round(float(dn[:, :, HL.DN_REFINED].mean()), 4), "tracked_corners_mean": round(float(st_last[:, :, HL.ST_NTRACK].mean()), 1),
-               "max_abs_pose_err_vs_truth": {"pnp": float(np.max(err_pnp)), "dense_refined": float(np.max(err_ref))},
+               "max_abs_pose_err_vs_truth": {"pnp": float(np.max(err_pnp)), "dense_refined": float(np.max(err_ref))} if args.full else None,
                "render_s": round(bench.render_s, 1), "gathered_shape": list(gathered.shape), "rccl_ranks": world, "dist_backend": D.backend_name()}
         if rehearsal:
             out["rehearsal"] = True

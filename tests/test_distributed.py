@@ -109,6 +109,23 @@ def test_bench_under_torchrun_world2_gloo():
     assert j["n_gpus"] == 2 and j["gather_ok"] and j["gathered_shape"] == [2, 5, 1, 16]
 
 
+def test_bench_plain_run_times_steps_and_dumps_outputs(tmp_path):
+    """a plain run times exactly --steps steps (one block), and --dump-outputs writes the records of the last timed step -- the
+    same from run to run, since the inputs are (stub tracker on the CPU: the flow of the option, not the kernels)"""
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        j = _bench_json([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--dry-run", "--dump-outputs", str(d)], env)
+        assert j["steps"] == 5 and j["timing"] == {"blocks": 1, "steps_per_block": 5} and j["gathered_shape"] == [1, 5, 1, 16]
+        assert sorted(os.listdir(d)) == ["records.npy"]
+        got.append(np.load(d / "records.npy"))
+    assert got[0].dtype == np.float64 and got[0].shape == (1, 1, 16)
+    assert got[0][0, 0, 6] == 1.0 and got[0][0, 0, 8] == 2 + 5          # accepted, the stub's frame counter: warm-up + timed steps
+    assert np.array_equal(got[0], got[1])
+
+
 def test_bench_rejects_world_mismatch():
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -89,7 +89,7 @@ def test_two_rank_rehearsal_of_the_bench_flow_on_one_card():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("AGT_DIST_BACKEND", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4", "--steps", "8", "--blocks", "2",
-                        "--warmup", "4", "--render-frames", "6", "--no-cpu-baseline", "--no-extras"],
+                        "--warmup", "4", "--render-frames", "6", "--full", "--no-cpu-baseline", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "REHEARSAL" in r.stderr, "the parent says what it is about to do before it starts the ranks"

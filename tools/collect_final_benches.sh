@@ -2,7 +2,7 @@
 # Plain (un-profiled) bench lines of every workload, with cpu_baseline: bash tools/collect_final_benches.sh <outdir under gpurun_out>
 OUT=gpurun_out/${1:-final}
 mkdir -p "$OUT"
-run() { name=$1; shift; echo "== $name"; timeout -k 10 600 python3 bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "rc=$?"; }
+run() { name=$1; shift; echo "== $name"; timeout -k 10 600 python3 bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "rc=$?"; }
 run c2
 run c2k20 --steps 20 --warmup 5
 run c3 --workload c3 --steps 600 --warmup 16 --render-frames 8
