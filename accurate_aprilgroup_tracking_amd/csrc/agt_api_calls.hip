@@ -1,0 +1,283 @@
+// agt_api_calls.hip -- the stateless cv2-shaped calls of the C ABI: pyramids, LK, solvePnP / projectPoints (device and host-array
+// forms), dense refinement, the LK residency cap, the XCD tile order.
+#include "agt_ctx.h"
+#include <string.h>
+
+int agt_xcd_tile_order(int block, int nblocks, int xcds)
+{
+    const int xs = xcds == 8 ? 3 : xcds == 4 ? 2 : xcds == 2 ? 1 : xcds == 1 ? 0 : -1;
+    if (xs < 0 || nblocks <= 0 || (nblocks & (xcds - 1)) || block < 0 || block >= nblocks) return AGT_ERR_ARG;
+    return agt_xcd_order(block, nblocks, xs);
+}
+
+int agt_pyr_down_u8(agt_ctx* c, const uint8_t* d_src, int sw, int sh, size_t spitch, size_t sbatch,
+                    uint8_t* d_dst, size_t dpitch, size_t dbatch, int B)
+{
+    if (!c || !d_src || !d_dst || sw <= 0 || sh <= 0 || B <= 0) return AGT_ERR_ARG;
+    if ((spitch & 3) || (dpitch & 3) || ((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 3) || (sbatch & 3) || (dbatch & 3)) return AGT_ERR_ARG;
+    if (spitch < (size_t)sw || dpitch < (size_t)((sw + 1) / 2)) return AGT_ERR_ARG;
+    hipError_t e = agt_launch_pyr_down(c->stream, d_src, sw, sh, (long)spitch, (long)sbatch, d_dst, (long)dpitch, (long)dbatch, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int agt_pyramid_build(agt_ctx* c, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B)
+{
+    if (!c || slot < 0 || slot > 1) return AGT_ERR_ARG;
+    // slots 0 / 1 are ring entries of the tracker too: frames still in flight (fused pipeline groups not yet
+    // launched, stage kernels on the library's streams) are enqueued / ordered in front of this build first
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->prebuilt_t = -1;
+    return pyramid_build_on(c, c->stream, slot, d_frames, pitch, batch_stride, B);
+}
+
+// Both pyramids of a frame pair (slot 0 <- d_prev, slot 1 <- d_next) with ONE launch for levels 1 and 2 (round 6).  A batch of cold
+// pairs pays two pyramid launches per step otherwise, each a stream of its own length with a ramp and a tail and a kernel boundary
+// between them (~2 us between two streaming kernels on one stream): the two-level rolling pass of 2 B images is the same pass, once.
+// The geometry of both frames is one (pitch, batch_stride); deeper levels, other windows and small batches fall back to two builds.
+int agt_pyramid_build_pair(agt_ctx* c, const uint8_t* d_prev, const uint8_t* d_next, size_t pitch, size_t batch_stride, int B)
+{
+    if (!c || !d_prev || !d_next) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->prebuilt_t = -1;
+    const int L = c->eff_max_level;
+    bool one = L >= 2 && agt_step_supported(c->cfg.win) && B > 0 && B <= c->cfg.max_streams &&
+               !((pitch & 3) || ((uintptr_t)d_prev & 3) || ((uintptr_t)d_next & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width);
+    AgtStepParams S;
+    AgtStepTables T;
+    if (one) {
+        memset(&S, 0, sizeof(S));
+        memset(&T, 0, sizeof(T));
+        S.pnp.fault = c->fault_dev;
+        AgtPyrArgs& A = S.pyr[0];
+        A.sw = c->lw[0]; A.sh = c->lh[0]; A.dw = c->lw[1]; A.dh = c->lh[1];
+        A.spitch = (long)pitch; A.sbatch = (long)batch_stride;
+        A.dpitch = c->lpitch[1]; A.dbatch = (long)c->lh[1] * c->lpitch[1];
+        A.B = B;
+        uintptr_t src_align = 0, dst_align = 0;
+        const uint8_t* src[2] = { d_prev, d_next };
+        for (int k = 0; k < 2; k++) {
+            T.pyr_src[0][k] = src[k]; T.pyr_dst[0][k] = c->lmem[k][1]; T.pyr_dst[1][k] = c->lmem[k][2];
+            src_align |= (uintptr_t)src[k]; dst_align |= (uintptr_t)c->lmem[k][1] | (uintptr_t)c->lmem[k][2];
+        }
+        A.src = T.pyr_src[0][0]; A.dst = T.pyr_dst[0][0];
+        AgtPyrArgs A0 = A, A1 = S.pyr[1];
+        A1.sw = c->lw[1]; A1.sh = c->lh[1]; A1.dw = c->lw[2]; A1.dh = c->lh[2];
+        A1.spitch = c->lpitch[1]; A1.sbatch = (long)c->lh[1] * c->lpitch[1];
+        A1.dpitch = c->lpitch[2]; A1.dbatch = (long)c->lh[2] * c->lpitch[2];
+        A1.B = B; A1.src = nullptr; A1.dst = nullptr;
+        agt_pyr2_plan(&A0, &A1, src_align, dst_align, 2);
+        one = A0.pad != 0 || B <= AGT_PYR2_MAX_B;             // (rolling form for big batches; the tiled two-level pass for small ones)
+        if (one) {
+            S.pyr[0] = A0; S.pyr[1] = A1;
+            S.pyr_fused = 1;
+            S.pyr_nf[0] = 2;
+            S.n_pyr[0] = A0.gx * A0.gy * B * 2;
+        }
+    }
+    if (!one) {
+        rc = pyramid_build_on(c, c->stream, 0, d_prev, pitch, batch_stride, B);
+        return rc ? rc : pyramid_build_on(c, c->stream, 1, d_next, pitch, batch_stride, B);
+    }
+    hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
+    if (e != hipSuccess) return hip_fail(c, e);
+    const uint8_t* src[2] = { d_prev, d_next };
+    for (int k = 0; k < 2; k++) {
+        c->l0_ptr[k] = src[k]; c->l0_pitch[k] = (long)pitch; c->l0_bstride[k] = (long)batch_stride;
+        const uint8_t* sp_ = c->lmem[k][2]; long spitch = c->lpitch[2], sb = (long)c->lh[2] * c->lpitch[2];
+        for (int l = 3; l <= L; l++) {
+            const long db = (long)c->lh[l] * c->lpitch[l];
+            e = agt_launch_pyr_down(c->stream, sp_, c->lw[l - 1], c->lh[l - 1], spitch, sb, c->lmem[k][l], c->lpitch[l], db, B);
+            if (e != hipSuccess) return hip_fail(c, e);
+            sp_ = c->lmem[k][l]; spitch = c->lpitch[l]; sb = db;
+        }
+        c->built_B[k] = B;
+    }
+    return AGT_OK;
+}
+
+int agt_pyramid_max_level(const agt_ctx* c) { return c ? c->eff_max_level : AGT_ERR_ARG; }
+
+int agt_pyramid_level(const agt_ctx* c, int slot, int level, const uint8_t** d_ptr,
+                      int* w, int* h, size_t* pitch, size_t* batch_stride)
+{
+    if (!c || slot < 0 || slot >= c->ring || level < 0 || level > c->eff_max_level) return AGT_ERR_ARG;
+    if (c->built_B[slot] <= 0) return AGT_ERR_STATE;
+    if (d_ptr) *d_ptr = level == 0 ? c->l0_ptr[slot] : c->lmem[slot][level];
+    if (w) *w = c->lw[level];
+    if (h) *h = c->lh[level];
+    if (pitch) *pitch = (size_t)(level == 0 ? c->l0_pitch[slot] : c->lpitch[level]);
+    if (batch_stride) *batch_stride = (size_t)(level == 0 ? c->l0_bstride[slot] : (long)c->lh[level] * c->lpitch[level]);
+    return AGT_OK;
+}
+
+int agt_lk_track(agt_ctx* c, int prev_slot, int next_slot,
+                 const float* d_prev_pts, float* d_next_pts, uint8_t* d_status, float* d_err,
+                 int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                 int flags, double min_eig_threshold)
+{
+    if (!c || prev_slot < 0 || prev_slot > 1 || next_slot < 0 || next_slot > 1) return AGT_ERR_ARG;
+    return lk_track_on(c, c->stream, prev_slot, next_slot, d_prev_pts, nullptr, d_next_pts, d_status, d_err, n, B,
+                       crit_type, crit_max_count, crit_eps, flags, min_eig_threshold);
+}
+
+int agt_solve_pnp(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
+                  const uint8_t* d_mask, int n, int B,
+                  const double* K, const double* dist, int ndist,
+                  double* d_pose, int use_guess, int32_t* d_info, double* d_err)
+{
+    if (!c || !d_obj || !d_img || !d_pose || B <= 0) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (n < 3 || n > 256) return AGT_ERR_NPOINTS;
+    if (!use_guess && n < 4) return AGT_ERR_NPOINTS;
+    AgtPnpParams p;
+    memset(&p, 0, sizeof(p));
+    int rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.img = d_img; p.mask = d_mask; p.dtype = dtype;
+    p.n = n; p.use_guess = use_guess ? 1 : 0; p.pose = d_pose; p.info = d_info; p.err = d_err;
+    p.gate_px = 2.0;
+    hipError_t e = agt_launch_pnp(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int agt_project_points(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
+                       const double* d_pose, const double* K, const double* dist, int ndist,
+                       void* d_img_out, double* d_jac)
+{
+    if (!c || !d_obj || !d_pose || !d_img_out || n <= 0 || B <= 0) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    AgtProjParams p;
+    memset(&p, 0, sizeof(p));
+    int rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n; p.pose = d_pose;
+    p.img_out = d_img_out; p.jac = d_jac;
+    hipError_t e = agt_launch_project(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// ---- the reference's per-frame calls as ONE synchronous call each, host arrays in and out (detect_pose.py:509-526 solvePnP,
+// :441-465 projectPoints).  No copies are enqueued: the arguments go into a host-mapped staging area of the
+// context, the kernel reads them and writes its results there over PCIe and stores a sequence word behind them (system scope), the
+// calling thread polls the word.  Against upload + launch + download + stream wait (44 / 28 us per call): see DESIGN.md section 6.
+namespace {
+constexpr size_t HC_SEQ = 0, HC_POSE = 64, HC_INFO = 128, HC_ERR = 144, HC_OBJ = 256, HC_IMG = HC_OBJ + 256 * 3 * 8,
+                 HC_JAC = HC_IMG + 256 * 2 * 8, HC_SIZE = HC_JAC + 2 * 256 * 6 * 8;
+
+int hcall_ready(agt_ctx* c)
+{
+    if (c->hcall_host) return AGT_OK;
+    if (hipHostMalloc((void**)&c->hcall_host, HC_SIZE, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); c->hcall_host = nullptr; return AGT_ERR_ALLOC; }
+    memset(c->hcall_host, 0, HC_SIZE);
+    if (hipHostGetDevicePointer((void**)&c->hcall_dev, c->hcall_host, 0) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipHostFree(c->hcall_host); c->hcall_host = nullptr; return AGT_ERR_HIP;
+    }
+    c->hcall_n = 0;
+    return AGT_OK;
+}
+}  // namespace
+
+int agt_solve_pnp_host(agt_ctx* c, const void* h_obj, const void* h_img, int dtype, int n,
+                       const double* K, const double* dist, int ndist,
+                       double* h_pose, int use_guess, int32_t* h_info, double* h_err)
+{
+    if (!c || !h_obj || !h_img || !h_pose) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (n < 3 || n > 256) return AGT_ERR_NPOINTS;
+    if (!use_guess && n < 4) return AGT_ERR_NPOINTS;
+    int rc = hcall_ready(c);
+    if (rc) return rc;
+    AgtPnpParams p;
+    memset(&p, 0, sizeof(p));
+    rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    const size_t es = dtype == AGT_F32 ? 4 : 8;
+    memcpy(c->hcall_host + HC_OBJ, h_obj, (size_t)n * 3 * es);
+    memcpy(c->hcall_host + HC_IMG, h_img, (size_t)n * 2 * es);
+    double* pose = (double*)(c->hcall_host + HC_POSE);
+    if (use_guess) memcpy(pose, h_pose, 6 * sizeof(double)); else memset(pose, 0, 6 * sizeof(double));
+    p.obj = c->hcall_dev + HC_OBJ; p.obj_bstride = 0; p.img = c->hcall_dev + HC_IMG; p.mask = nullptr; p.dtype = dtype;
+    p.n = n; p.use_guess = use_guess ? 1 : 0; p.pose = (double*)(c->hcall_dev + HC_POSE);
+    p.info = (int32_t*)(c->hcall_dev + HC_INFO); p.err = (double*)(c->hcall_dev + HC_ERR);
+    p.gate_px = 2.0;
+    const unsigned long long want = ++c->hcall_n;
+    p.host_seq = (unsigned long long*)(c->hcall_dev + HC_SEQ); p.host_seq_base = want;
+    hipError_t e = agt_launch_pnp(c->stream, p, 1);
+    if (e != hipSuccess) return hip_fail(c, e);
+    rc = poll_seq(c, (const volatile unsigned long long*)(c->hcall_host + HC_SEQ), want);
+    if (rc) return rc;
+    memcpy(h_pose, pose, 6 * sizeof(double));
+    if (h_info) memcpy(h_info, c->hcall_host + HC_INFO, 4 * sizeof(int32_t));
+    if (h_err) *h_err = *(const double*)(c->hcall_host + HC_ERR);
+    return AGT_OK;
+}
+
+int agt_project_points_host(agt_ctx* c, const void* h_obj, int dtype, int n, const double* h_pose,
+                            const double* K, const double* dist, int ndist, void* h_img_out, double* h_jac)
+{
+    if (!c || !h_obj || !h_pose || !h_img_out) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (n <= 0 || n > 256) return AGT_ERR_NPOINTS;          // (one workgroup: the reference projects its 48 .. 240 model corners)
+    int rc = hcall_ready(c);
+    if (rc) return rc;
+    AgtProjParams p;
+    memset(&p, 0, sizeof(p));
+    rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    const size_t es = dtype == AGT_F32 ? 4 : 8;
+    memcpy(c->hcall_host + HC_OBJ, h_obj, (size_t)n * 3 * es);
+    memcpy(c->hcall_host + HC_POSE, h_pose, 6 * sizeof(double));
+    p.obj = c->hcall_dev + HC_OBJ; p.obj_bstride = 0; p.dtype = dtype; p.n = n; p.pose = (const double*)(c->hcall_dev + HC_POSE);
+    p.img_out = c->hcall_dev + HC_IMG; p.jac = h_jac ? (double*)(c->hcall_dev + HC_JAC) : nullptr;
+    const unsigned long long want = ++c->hcall_n;
+    p.host_seq = (unsigned long long*)(c->hcall_dev + HC_SEQ); p.host_seq_base = want;
+    hipError_t e = agt_launch_project(c->stream, p, 1);
+    if (e != hipSuccess) return hip_fail(c, e);
+    rc = poll_seq(c, (const volatile unsigned long long*)(c->hcall_host + HC_SEQ), want);
+    if (rc) return rc;
+    memcpy(h_img_out, c->hcall_host + HC_IMG, (size_t)n * 2 * es);
+    if (h_jac) memcpy(h_jac, c->hcall_host + HC_JAC, (size_t)n * 12 * sizeof(double));
+    return AGT_OK;
+}
+
+// residency cap of the one-wave LK launches: what it does and the library's choice at lk_lds_min (agt_api_tracker.hip)
+int agt_lk_lds_request(int workgroups_per_cu) { return lk_lds_min(workgroups_per_cu); }
+
+int agt_lk_occupancy_cu(agt_ctx* c, int workgroups_per_cu)
+{
+    if (!c || workgroups_per_cu < -1 || workgroups_per_cu > 32) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->lk_cap_cu = workgroups_per_cu;
+    return AGT_OK;
+}
+
+// the same in waves per SIMD (round 5's entry point): 4 x waves_per_simd workgroups per CU, 0 = no cap
+int agt_lk_occupancy(agt_ctx* c, int waves_per_simd)
+{
+    if (!c || waves_per_simd < 0 || waves_per_simd > 8) return AGT_ERR_ARG;
+    return agt_lk_occupancy_cu(c, 4 * waves_per_simd);
+}
+
+// dense photometric + geometric pose refinement (semantics: oracle/cv_dense.c / csrc/agt_dense.hip)
+int agt_dense_refine(agt_ctx* c, const uint8_t* d_img, size_t pitch, size_t batch_stride, int w, int h,
+                     const float* d_model_xyz, const float* d_model_t, int M,
+                     const float* d_obj, const float* d_img_pts, const uint8_t* d_mask, int N,
+                     const double* K, const double* dist, int ndist,
+                     double* d_pose, int B, int iters, double photo_weight, double* d_stats)
+{
+    if (!c || !d_img || !d_pose || !d_stats || B <= 0 || w < 4 || h < 4 || iters < 0 || iters > 1000) return AGT_ERR_ARG;
+    if (M < 0 || N < 0 || (M > 0 && (!d_model_xyz || !d_model_t)) || (N > 0 && (!d_obj || !d_img_pts))) return AGT_ERR_ARG;
+    if (M + N == 0 || pitch < (size_t)w || !(photo_weight >= 0.0)) return AGT_ERR_ARG;
+    AgtCameraHost cam;
+    int rc = camera_on(c, K, dist, ndist, &cam);
+    if (rc) return rc;
+    rc = dense_scratch(c, agt_dense_doubles(M, B), B);
+    if (rc) return rc;
+    hipError_t e = agt_launch_dense(c->stream, d_img, (long)pitch, (long)batch_stride, w, h, d_model_xyz, d_model_t, M,
+                                    d_obj, d_img_pts, d_mask, N, cam, d_pose, c->dense_partials, d_stats, c->dense_done,
+                                    B, iters, photo_weight, 1e-3, nullptr, nullptr, nullptr);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}

@@ -1,0 +1,1163 @@
+// agt_api_tracker.hip -- the tracker of the C ABI and everything a tracked frame goes through: reset / options, the fused, split and
+// serial launch forms, the dense stage, the live camera loop and its pre-processing, joins and state reads, profiling.  No host<->device
+// copies and no synchronisation on the per-frame path; everything is enqueued on the context's stream.
+#include "agt_ctx.h"
+#include <new>
+#include <string.h>
+#include <stdio.h>
+
+// scratch of the dense refinement: `need` doubles of block partials and one done word per stream; the two
+// capacities are tracked separately (a later call may bring more streams with fewer samples)
+int dense_scratch(agt_ctx* c, size_t need, int B)
+{
+    if (need <= c->dense_cap && B <= c->dense_done_B) return AGT_OK;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(c, e);
+    if (need > c->dense_cap) {
+        if (c->dense_partials) (void)hipFree(c->dense_partials);
+        c->dense_partials = nullptr; c->dense_cap = 0;
+        if (hipMalloc((void**)&c->dense_partials, need * sizeof(double)) != hipSuccess) { hip_fail(c, hipGetLastError()); return AGT_ERR_ALLOC; }
+        c->dense_cap = need;
+    }
+    if (B > c->dense_done_B) {
+        if (c->dense_done) (void)hipFree(c->dense_done);
+        c->dense_done = nullptr; c->dense_done_B = 0;
+        if (hipMalloc((void**)&c->dense_done, (size_t)B * sizeof(int) + 64) != hipSuccess) { hip_fail(c, hipGetLastError()); return AGT_ERR_ALLOC; }
+        c->dense_done_B = B;
+    }
+    return AGT_OK;
+}
+
+int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B)
+{
+    if (!c || !d_frames || slot < 0 || slot >= c->ring || B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
+    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    c->l0_ptr[slot] = d_frames; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
+    const uint8_t* src = d_frames; long sp = (long)pitch, sb = (long)batch_stride;
+    int l0 = 1;
+    bool two_level = c->eff_max_level >= 2 && B <= AGT_PYR2_MAX_B;
+    if (c->eff_max_level >= 2 && !two_level) {
+        // big batches: the two-level pass only in its register-rolling form (the tiled one loses to two single passes there)
+        AgtPyrArgs A0, A1;
+        agt_pyr2_args(src, c->lw[0], c->lh[0], sp, sb, c->lmem[slot][1], c->lpitch[1], (long)c->lh[1] * c->lpitch[1],
+                      c->lmem[slot][2], c->lpitch[2], (long)c->lh[2] * c->lpitch[2], B, &A0, &A1);
+        agt_pyr2_plan(&A0, &A1, (uintptr_t)src, (uintptr_t)c->lmem[slot][1] | (uintptr_t)c->lmem[slot][2], 1);
+        two_level = A0.pad != 0;
+    }
+    if (two_level) {
+        // levels 1 and 2 in one pass: level 0 is read once, level 1 is never re-read from HBM
+        const long db1 = (long)c->lh[1] * c->lpitch[1], db2 = (long)c->lh[2] * c->lpitch[2];
+        hipError_t e = agt_launch_pyr_down2(stream, src, c->lw[0], c->lh[0], sp, sb, c->lmem[slot][1], c->lpitch[1], db1,
+                                            c->lmem[slot][2], c->lpitch[2], db2, B);
+        if (e != hipSuccess) return hip_fail(c, e);
+        src = c->lmem[slot][2]; sp = c->lpitch[2]; sb = db2;
+        l0 = 3;
+    }
+    for (int l = l0; l <= c->eff_max_level; l++) {
+        const long db = (long)c->lh[l] * c->lpitch[l];
+        hipError_t e = agt_launch_pyr_down(stream, src, c->lw[l - 1], c->lh[l - 1], sp, sb, c->lmem[slot][l], c->lpitch[l], db, B);
+        if (e != hipSuccess) return hip_fail(c, e);
+        src = c->lmem[slot][l]; sp = c->lpitch[l]; sb = db;
+    }
+    c->built_B[slot] = B;
+    return AGT_OK;
+}
+
+static void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
+{
+    for (int l = 0; l <= c->eff_max_level; l++) {
+        L[l].w = c->lw[l]; L[l].h = c->lh[l];
+        if (l == 0) { L[l].ptr = c->l0_ptr[slot]; L[l].pitch = c->l0_pitch[slot]; L[l].bstride = c->l0_bstride[slot]; }
+        else { L[l].ptr = c->lmem[slot][l]; L[l].pitch = c->lpitch[l]; L[l].bstride = (long)c->lh[l] * c->lpitch[l]; }
+    }
+}
+
+#define AGT_SPLIT_LK_CU 10       // (see agt_lk_occupancy_cu)
+#define AGT_SPLIT_PYR_OH 6       // strip height (level-2 rows) of the split pipeline's pyramid role (agt_pyramid.hip agt_pyr2_plan) ...
+#define AGT_SPLIT_PYR_OH_B0 12   // ... for batches of 12 .. 96 streams: measured (session r6ar, us per step, strips of 6 / 16) 8 streams 20.1 / 19.8,
+#define AGT_SPLIT_PYR_OH_B1 96   // 16: 27.5 / 28.3, 32: 29.4 / 29.9, 64: 35.1-35.9 / 36.7-37.6, 128: 63.7 / 62.4
+int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
+                const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
+                int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                int flags, double min_eig_threshold, int b0, int waves, bool hybrid)
+{
+    // b0: first stream of the launch (streams b0 .. b0 + B - 1 of the slots and of the point arrays); waves: see agt_launch_lk
+    if (!c || !d_prev_pts || !d_next_pts || !d_status) return AGT_ERR_ARG;
+    if (prev_slot < 0 || prev_slot >= c->ring || next_slot < 0 || next_slot >= c->ring) return AGT_ERR_ARG;
+    if (n < 0 || B <= 0 || b0 < 0) return AGT_ERR_ARG;
+    if (n == 0) return AGT_OK;
+    if (c->built_B[prev_slot] < b0 + B || c->built_B[next_slot] < b0 + B) return AGT_ERR_STATE;
+    AgtLkParams p;
+    memset(&p, 0, sizeof(p));
+    fill_levels(c, prev_slot, p.prev);
+    fill_levels(c, next_slot, p.next);
+    p.max_level = c->eff_max_level;
+    p.n = n;
+    // SparsePyrLKOpticalFlowImpl::calc criteria normalisation
+    p.max_count = (crit_type & AGT_TERM_COUNT) ? (crit_max_count < 0 ? 0 : crit_max_count > 100 ? 100 : crit_max_count) : 30;
+    double eps = (crit_type & AGT_TERM_EPS) ? (crit_eps < 0. ? 0. : crit_eps > 10. ? 10. : crit_eps) : 0.01;
+    p.eps2 = eps * eps;
+    p.flags = flags & 0xffff;            // (the bits above are internal launch flags)
+    // (waves == 1: a half-batch launch of the split pipeline -- beside the other half's launch and the pyramid launch of the frames ahead)
+    p.lds_min = lk_lds_min(c->lk_cap_cu >= 0 ? c->lk_cap_cu : (waves == 1 ? AGT_SPLIT_LK_CU : 0));
+    if (c->lk_cap_cu > 0) p.flags |= AGT_LK_FLAG_COTENANT;        // (declared by the caller: agt_lk_occupancy_cu; see agt_lk.hip lk_kernel)
+    if (!AGT_KNOB("AGT_LK_COTENANT_PRIO", 1)) p.flags &= ~AGT_LK_FLAG_COTENANT;     // (knobs: the cap without the issue priority, A/B of the two)
+    p.min_eig_threshold = min_eig_threshold;
+    p.prev_pts = d_prev_pts; p.prev_status = d_prev_status; p.next_pts = d_next_pts; p.status = d_status; p.err = d_err;
+    if (b0) {
+        for (int l = 0; l <= c->eff_max_level; l++) { p.prev[l].ptr += (long)b0 * p.prev[l].bstride; p.next[l].ptr += (long)b0 * p.next[l].bstride; }
+        p.prev_pts += (size_t)b0 * n * 2; p.next_pts += (size_t)b0 * n * 2; p.status += (size_t)b0 * n;
+        if (p.prev_status) p.prev_status += (size_t)b0 * n;
+        if (p.err) p.err += (size_t)b0 * n;
+    }
+    // HYBRID launch, MEASURED AND NOT SHIPPED (round 5; knobs build: AGT_LK_HYBRID=<iterations>): corners that took >= that
+    // many iterations in the previous frame tracked by four waves, the rest by one, in one launch of two workgroup roles
+    // (agt_lk.hip lk_hybrid_kernel).  Bit-identical records; 64 streams: 40.2 us per step without, 49.5 with the launch form alone
+    // (threshold 200: nobody on four waves), 49.8 / 51.9 / 61.6 / 75.2 at thresholds 14 / 12 / 10 / 8 -- the chip is as much
+    // throughput- as latency-bound there, and a four-wave corner costs 3 x the wave-time of a one-wave corner (profiles/r05_experiments.md).
+    if (hybrid && c->lk_slow_thr > 0 && c->cfg.win == 21 && c->eff_max_level < 3 && !p.err && flags == 0 &&
+        (size_t)(b0 + B) * n <= (size_t)c->cfg.max_streams * c->cfg.max_points) {
+        p.iters_prev = c->lk_iters[prev_slot] + (size_t)b0 * n; p.iters_out = c->lk_iters[next_slot] + (size_t)b0 * n;
+        p.slow_thr = c->lk_slow_thr;
+        hipError_t e = agt_launch_lk_hybrid(stream, p, B);
+        return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+    }
+    hipError_t e = agt_launch_lk(stream, p, c->cfg.win, B, c->cfg.win == 21 ? waves : 0);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float* d_obj, int n, int B,
+                      const double* K, const double* dist, int ndist, int enhance_ape)
+{
+    if (!c || !d_obj || slot < 0 || slot > 1) return AGT_ERR_ARG;
+    if (n < 4 || n > c->cfg.max_points) return AGT_ERR_NPOINTS;
+    if (c->tag_gate && n % c->tag_gate) return AGT_ERR_NPOINTS;      // whole tags: corners 4t .. 4t + 3
+    if (B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
+    if (d_corners && c->built_B[slot] < B) return AGT_ERR_STATE;
+    int rc = join_pipeline(c);            // frames of an earlier run still in flight (fused pipeline or library streams)
+    if (rc) return rc;
+    if (*(volatile int*)c->fault_host) {
+        // recovery from a chained-wait give-up: everything in flight has to be over before the fault word is cleared
+        hipError_t es = hipStreamSynchronize(c->stream);
+        if (es != hipSuccess) return hip_fail(c, es);
+        *(volatile int*)c->fault_host = 0;
+    }
+    rc = camera_on(c, K, dist, ndist, &c->cam, true);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    // the tracker's frame 0 lives in ring entry 0: adopt the caller's slot as pyramid slot 0
+    if (d_corners && slot != 0) {
+        for (int l = 1; l <= c->eff_max_level; l++) { uint8_t* t = c->lmem[0][l]; c->lmem[0][l] = c->lmem[slot][l]; c->lmem[slot][l] = t; }
+        c->l0_ptr[0] = c->l0_ptr[slot]; c->l0_pitch[0] = c->l0_pitch[slot]; c->l0_bstride[0] = c->l0_bstride[slot];
+        c->built_B[0] = c->built_B[slot]; c->built_B[slot] = 0;
+    }
+    if (d_corners) e = hipMemcpyAsync(c->corners[0], d_corners, (size_t)B * n * 2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->obj, d_obj, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->tstate, 0, (size_t)B * sizeof(AgtTrackState), c->stream);
+    for (int s = 0; s < c->ring && e == hipSuccess; s++) e = hipMemsetAsync(c->status[s], 1, (size_t)B * n, c->stream);
+#ifdef AGT_DEBUG_KNOBS
+    for (int s = 0; s < c->ring && e == hipSuccess; s++) e = hipMemsetAsync(c->lk_iters[s], 0, (size_t)B * n, c->stream);
+#endif
+    // arrival counters of the chained launches: a run counts n corners per stream-frame, the next run may have other n / B
+    if (e == hipSuccess) e = hipMemsetAsync(c->lk_done, 0, (size_t)AGT_RING_MAX * c->cfg.max_streams * sizeof(unsigned), c->stream);
+    memset(c->lk_target, 0, sizeof(c->lk_target));
+    if (e != hipSuccess) return hip_fail(c, e);
+    c->prebuilt_t = -1;
+    c->hseq_off = c->hseq_last + 1;          // (sequence numbers of agt_track_host_frame stay monotonic across runs)
+    c->trk_n = n; c->trk_B = B; c->trk_frame = 0; c->n_lk = c->n_pnp = 0; c->enhance_ape = enhance_ape ? 1 : 0;
+    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = 0;
+    c->trk_ready = d_corners ? 2 : 1;
+    return AGT_OK;
+}
+
+int agt_tracker_options(agt_ctx* c, int reproject, int min_points, double gate_px)
+{
+    if (!c || min_points < 6 || min_points > 256 || !(gate_px > 0.0)) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->reproject = reproject ? 1 : 0; c->min_points = min_points; c->gate_px = gate_px;
+    return AGT_OK;
+}
+
+// Residency cap of the one-wave-per-corner LK kernel (big batches): at most `workgroups_per_cu` of its waves resident on a CU (0 = no// cap: as many as registers and LDS allow, 14-16; -1 = the library's choice, the default).  For launches that SHARE the device with
+// other kernels: a tracker wave holds 112 registers and ~7.5 KB of LDS, twelve of them on a CU leave one wave slot of registers per SIMD
+// to anybody else, and a launch lasts as long as its slowest corner -- the HBM-bound pyramid passes beside it starve.  The cap is
+// enforced with LDS: every workgroup (one wave) asks for at least LDS_per_CU / workgroups_per_cu bytes (more than its tiles need).
+// The library's choice: none for a launch of its own (agt_lk_track, the fused step); AGT_SPLIT_LK_CU for the half-batch launches of the
+// split pipeline, which run beside the pyramid launch of the frames ahead (round 6, 64 streams of 48 corners: 12 per CU -- all 3,072
+// corners resident, the LK launch alone 30.8 us -- step 39.5-40.2 us; 11: 39.1; 10: 38.4; 9: 38.7-39.5; 8: 40.1 -- with 10 the launch alone
+// takes 41 us, the step is the shortest; gpurun_out/r6s, profiles/r06_experiments.md).
+int lk_lds_min(int per_cu)
+{
+    if (per_cu <= 0) return 0;
+    // The LDS allocation granule is not documented (measured: 12,800 B -> 12 per CU, 13,824 B -> 11: consistent with 512, 1,024 and
+    // 1,280 B), so the request is the smallest multiple of 256 B above AGT_LDS_PER_CU / (per_cu + 1): per_cu + 1 workgroups do not fit WHATEVER the granule
+    // ("at most per_cu"), and per_cu do fit for granules up to 512 B (for 1,024 / 1,280 B too at the counts the library itself uses, 8 and
+    // 10; at some other counts one fewer would: tests/test_chip.py)
+    const long v = (AGT_LDS_PER_CU / (per_cu + 1) / 256 + 1) * 256;
+    return v > 64L * 1024 ? 0 : (int)v;                 // (a workgroup may ask for 64 KB in all: one per CU cannot be expressed -- no cap then)
+}
+
+int agt_tracker_tag_gate(agt_ctx* c, int corners_per_tag)
+{
+    if (!c || (corners_per_tag != 0 && corners_per_tag != 4)) return AGT_ERR_ARG;
+    if (corners_per_tag && c->trk_ready && c->trk_n % corners_per_tag) return AGT_ERR_NPOINTS;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->tag_gate = corners_per_tag;
+    return AGT_OK;
+}
+
+// move frame `f`'s ring entry when the ring size changes (only the newest frame is live after a join)
+static void ring_move(agt_ctx* c, long f, int old_ring, int new_ring)
+{
+    const int a = (int)(f % old_ring), b = (int)(f % new_ring);
+    if (a == b) return;
+    for (int l = 1; l < AGT_MAX_LEVELS; l++) { uint8_t* t = c->lmem[a][l]; c->lmem[a][l] = c->lmem[b][l]; c->lmem[b][l] = t; }
+    { float* t = c->corners[a]; c->corners[a] = c->corners[b]; c->corners[b] = t; }
+    { uint8_t* t = c->status[a]; c->status[a] = c->status[b]; c->status[b] = t; }
+    { uint8_t* t = c->lk_iters[a]; c->lk_iters[a] = c->lk_iters[b]; c->lk_iters[b] = t; }
+    c->l0_ptr[b] = c->l0_ptr[a]; c->l0_pitch[b] = c->l0_pitch[a]; c->l0_bstride[b] = c->l0_bstride[a];
+    c->built_B[b] = c->built_B[a]; c->built_B[a] = 0;
+}
+
+// depth 0: separate launches per stage, pose complete in stream order.  depth F >= 1: fused software-pipelined
+// step that advances every stage by F frames per launch (one launch every F calls of agt_track_frame).
+int agt_tracker_pipeline(agt_ctx* c, int depth)
+{
+    if (!c || depth < 0 || depth > AGT_MAX_GROUP) return AGT_ERR_ARG;
+    if (depth && !agt_step_supported(c->cfg.win)) return AGT_ERR_UNSUPPORTED;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->pipeline = depth ? 1 : 0;
+    const int group = depth ? depth : 1;
+    if (group != c->group) {
+        // every frame <= trk_frame is complete; re-seat the newest one in a ring that fits the new depth
+        const int want = (c->eff_max_level + 2) * group > AGT_SLOTS ? (c->eff_max_level + 2) * group : AGT_SLOTS;
+        const int live_ring = c->live_ring;
+        rc = ensure_ring(c, want);
+        if (rc) return rc;
+        if (c->trk_ready == 2) ring_move(c, c->trk_frame, live_ring, want);
+        c->live_ring = want;
+        c->group = group;
+    }
+    return AGT_OK;
+}
+
+static void fill_estimate(const agt_ctx* c, AgtPnpParams* p, const float* d_img, const uint8_t* d_mask,
+                          double* d_state_out, float* corners_rw, uint8_t* status_rw = nullptr)
+{
+    memset(p, 0, sizeof(*p));
+    p->obj = c->obj; p->obj_bstride = 0; p->img = d_img; p->mask = d_mask; p->dtype = AGT_F32;
+    p->n = c->trk_n; p->cam = c->cam; p->pose = c->pose;
+    p->track = c->tstate; p->state_out = d_state_out; p->corners_rw = corners_rw; p->status_rw = status_rw;
+    p->enhance_ape = c->enhance_ape; p->reproject = c->reproject; p->min_points = c->min_points; p->gate_px = c->gate_px;
+    p->tag_gate = c->tag_gate; p->fault = c->fault_dev;
+}
+
+// the solver of the launch's first frame `frame` (tracker frame index) reports to the polling host thread (agt_track_host_frame)
+static void arm_host_seq(agt_ctx* c, AgtPnpParams* p, long frame)
+{
+    if (!c->host_seq_on) return;
+    p->host_seq = c->hseq_dev;
+    p->host_seq_base = c->hseq_off + (unsigned long long)frame;
+}
+
+static int fill_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int next_slot, const float* d_prev, const uint8_t* d_prev_status, float* d_next,
+                   uint8_t* d_status, float* d_err, int n, int crit_type, int crit_max_count, double crit_eps,
+                   int flags, double min_eig_threshold)
+{
+    memset(p, 0, sizeof(*p));
+    fill_levels(c, prev_slot, p->prev);
+    fill_levels(c, next_slot, p->next);
+    p->max_level = c->eff_max_level;
+    p->n = n;
+    // SparsePyrLKOpticalFlowImpl::calc criteria normalisation
+    p->max_count = (crit_type & AGT_TERM_COUNT) ? (crit_max_count < 0 ? 0 : crit_max_count > 100 ? 100 : crit_max_count) : 30;
+    double eps = (crit_type & AGT_TERM_EPS) ? (crit_eps < 0. ? 0. : crit_eps > 10. ? 10. : crit_eps) : 0.01;
+    p->eps2 = eps * eps;
+    p->flags = flags;
+    p->min_eig_threshold = min_eig_threshold;
+    p->prev_pts = d_prev; p->prev_status = d_prev_status; p->next_pts = d_next; p->status = d_status; p->err = d_err;
+    p->lds_min = lk_lds_min(c->lk_cap_cu > 0 ? c->lk_cap_cu : 0);
+    return AGT_OK;
+}
+
+// Big batches: pyramid, LK and PnP of one frame as separate kernels on three library-owned streams.  The host runs
+// ahead, so the pyramid of frame t+1 overlaps the LK of frame t and the PnP of frame t-1; every true dependency
+// (and every buffer reuse of the rings) is an event wait, nothing is assumed about timing.
+static int ms_init(agt_ctx* c)
+{
+    if (c->ms_ready) return AGT_OK;
+    if (c->ms_pool_slot < 0) c->ms_pool_slot = ms_pool_acquire(c->cfg.device, c->ms_stream);        // (a retry after a failed event creation keeps its slot)
+    if (c->ms_pool_slot < 0) return hip_fail(c, hipGetLastError());
+    for (int k = 0; k < 5; k++)
+        for (int i = 0; i < AGT_EV_SLOTS; i++)
+            if (!c->ms_ev[k][i] && hipEventCreateWithFlags(&c->ms_ev[k][i], hipEventDisableTiming) != hipSuccess) { c->ms_ev[k][i] = nullptr; return hip_fail(c, hipGetLastError()); }
+    c->ms_ready = 1;
+    return AGT_OK;
+}
+
+// the caller's stream waits for everything in flight on the library's streams (the LK and PnP launches of split mode)
+static int ms_join(agt_ctx* c)
+{
+    if (!c->ms_active) return AGT_OK;
+    hipEvent_t ev1 = c->ms_ev[2][0], ev2 = c->ms_ev[2][1], ev0 = c->ms_ev[2][3];
+    hipError_t e = hipEventRecord(ev1, c->ms_stream[1]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev1, 0);
+    if (e == hipSuccess) e = hipEventRecord(ev0, c->ms_stream[0]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev0, 0);
+    if (e == hipSuccess) e = hipEventRecord(ev2, c->ms_stream[2]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev2, 0);
+    if (e != hipSuccess) return hip_fail(c, e);
+    c->ms_active = 0;
+    c->last_p_ev = -1; c->l_ev_hist[0] = c->l_ev_hist[1] = c->l_ev_hist[2] = -1; c->y_ev_hist[0] = c->y_ev_hist[1] = -1;     // everything issued so far is ordered before the caller's next work
+    return AGT_OK;
+}
+
+// One fused launch: every pipeline stage advances by up to `group` frames whose input is complete.
+// fmax: the most frames a stage advances by in this call (0 = c->group).  The split pipeline (big batches: three launches per group)
+// runs groups of c->group frames in the steady state but SMALLER ones while it fills and drains (round 6, tools/trace_blocks.py: of a
+// 256-frame block of 64 streams 8 % was the first pyramid launch with nothing beside it and the last pose launch with nothing beside it --
+// a stage's launch covers a whole group, and the next stage waits for all of it): split_ramp() frames at first, doubling per launch.
+static int split_ramp(const agt_ctx* c) { const int r = c->group / 4; return r < 2 ? (c->group < 2 ? c->group : 2) : r; }
+static int launch_group(agt_ctx* c, int B, int fmax = 0)
+{
+    const int L = c->eff_max_level;              // pyramid stages 0..L-1 (stage s: level s -> s+1)
+    const int F = (fmax > 0 && fmax < c->group) ? fmax : c->group, M = c->live_ring;
+    AgtStepParams S;
+    AgtStepTables T;
+    memset(&S, 0, sizeof(S));
+    memset(&T, 0, sizeof(T));
+    S.pnp.fault = c->fault_dev;                  // (also where the launch has no pose role: the LK role reports a table it cannot use through it)
+    long done_before[AGT_MAX_LEVELS + 1];        // [s] = frames available as input of stage s (s = L: input of LK)
+    done_before[0] = c->trk_frame;
+    for (int s = 0; s < L; s++) done_before[s + 1] = c->n_stage[s];
+    const long lk_before = c->n_lk;
+    long lk_f0 = 0;                              // LK role: the frame before its group
+    bool any = false;
+    // Chained launch (fused step only): the PnP role follows the LK role of the SAME launch frame by frame through arrival
+    // counters (agt_step.hip pnp_role), instead of one launch behind it.
+    bool chain = agt_step_fits(c->trk_n, B);
+    if (!AGT_KNOB("AGT_CHAIN", 1)) chain = false;          // (knobs: AGT_CHAIN=0 keeps the PnP role one launch behind the LK role)
+    // stage 0 builds levels 1 and 2 in one pass (stage 1 then only keeps the books): always while the batch is small (tiled or
+    // register-rolling two-level pass), for big batches where the rolling form applies to every frame of the launch (decided below,
+    // in the s = 0 trip) and stage 1 has no backlog from an earlier launch that ran the levels as two passes
+    bool fused = L >= 2 && B <= AGT_PYR2_MAX_B;
+    // a launch that will carry pyramid work ONLY (the first one of a run: no frame is ready for the LK role, none for the pose role)
+    // goes out as the pyramid kernel proper (below), which has the register-rolling two-level pass -- the fused step kernel has not
+    const bool pyr_only = c->n_lk >= done_before[L] && c->n_pnp >= c->n_lk;
+    for (int s = 0; s < L; s++) {
+        if (fused && s == 1) continue;
+        long cnt = done_before[s] - c->n_stage[s];
+        if (cnt <= 0) continue;
+        if (cnt > F) cnt = F;
+        AgtPyrArgs& A = S.pyr[s];
+        A.sw = c->lw[s]; A.sh = c->lh[s];
+        A.dw = c->lw[s + 1]; A.dh = c->lh[s + 1];
+        A.dpitch = c->lpitch[s + 1]; A.dbatch = (long)c->lh[s + 1] * c->lpitch[s + 1];
+        A.B = B;
+        uintptr_t src_align = 0, dst_align = 0;
+        for (long k = 0; k < cnt; k++) {
+            const int slot = (int)((c->n_stage[s] + 1 + k) % M);
+            if (s == 0) {
+                // level 0 is the caller's frame: the frames of a group must share pitch and stream stride
+                if (k == 0) { A.spitch = c->l0_pitch[slot]; A.sbatch = c->l0_bstride[slot]; }
+                else if (A.spitch != c->l0_pitch[slot] || A.sbatch != c->l0_bstride[slot]) { cnt = k; break; }
+                T.pyr_src[s][k] = c->l0_ptr[slot];
+            } else {
+                A.spitch = c->lpitch[s]; A.sbatch = (long)c->lh[s] * c->lpitch[s];
+                T.pyr_src[s][k] = c->lmem[slot][s];
+            }
+            T.pyr_dst[s][k] = c->lmem[slot][s + 1];
+            src_align |= (uintptr_t)T.pyr_src[s][k]; dst_align |= (uintptr_t)T.pyr_dst[s][k];
+        }
+        A.src = T.pyr_src[s][0]; A.dst = T.pyr_dst[s][0];
+        agt_pyr_plan(&A, src_align, dst_align, (int)cnt);          // tiled or register-rolling form (A.pad), workgroups per image in A.gx * A.gy
+        if (s == 0 && L >= 2) {
+            // the level 1 -> 2 geometry and buffers ride in stage 1's slots; the pass's grid in A: 64 x 16 tiles of level 2 (tiled
+            // form) or workgroups per image with the strip height in A.pad (register-rolling form, agt_pyramid4_body.h)
+            AgtPyrArgs A0 = A, A1 = S.pyr[1];
+            A1.sw = c->lw[1]; A1.sh = c->lh[1]; A1.dw = c->lw[2]; A1.dh = c->lh[2];
+            A1.spitch = c->lpitch[1]; A1.sbatch = (long)c->lh[1] * c->lpitch[1];
+            A1.dpitch = c->lpitch[2]; A1.dbatch = (long)c->lh[2] * c->lpitch[2];
+            A1.B = B; A1.src = nullptr; A1.dst = nullptr;
+            uintptr_t d2_align = 0;
+            for (long k = 0; k < cnt; k++) d2_align |= (uintptr_t)c->lmem[(int)((c->n_stage[0] + 1 + k) % M)][2];
+            // (fused step: agt_step_fits, <= 256 corners in flight -- its kernel carries the tiled two-level pass only: plan as ONE frame, which
+            // keeps the launch below the rolling form's 16 images.  Round 5: except the pyramid-only launch at the head of a run, which is
+            // pyr_group_kernel -- 20 frames of 1280x720, the driver's block: 15.1 us tiled, see DESIGN.md section 6 for the rolling figure)
+            agt_pyr2_plan(&A0, &A1, src_align, dst_align | d2_align, (agt_step_fits(c->trk_n, B) && !pyr_only) ? 1 : (int)cnt,
+                          (agt_step_fits(c->trk_n, B) || B < AGT_SPLIT_PYR_OH_B0 || B > AGT_SPLIT_PYR_OH_B1) ? 16 : AGT_SPLIT_PYR_OH);
+            if (!fused && A0.pad != 0 && c->n_stage[1] == c->n_stage[0]) fused = true;       // big batch, rolling form, no backlog
+            if (fused) {
+                A = A0; S.pyr[1] = A1;
+                for (long k = 0; k < cnt; k++) T.pyr_dst[1][k] = c->lmem[(int)((c->n_stage[0] + 1 + k) % M)][2];
+                c->n_stage[1] += cnt;            // (same frames: level 2 is complete when level 1 is)
+            }
+        }
+        S.pyr_nf[s] = (int)cnt;
+        S.n_pyr[s] = A.gx * A.gy * B * (int)cnt;
+        c->n_stage[s] += cnt;
+        any = true;
+    }
+    S.pyr_fused = fused ? 1 : 0;
+    if (c->n_lk < done_before[L]) {
+        long cnt = done_before[L] - c->n_lk;
+        if (cnt > F) cnt = F;
+        const long f0 = c->n_lk;                 // the frame before the group
+        lk_f0 = f0;
+        // level 0 geometry comes from the frame's own registration; a group needs it uniform
+        for (long k = 1; k <= cnt; k++) {
+            const int a = (int)(f0 % M), q = (int)((f0 + k) % M);
+            if (c->l0_pitch[q] != c->l0_pitch[a] || c->l0_bstride[q] != c->l0_bstride[a]) { cnt = k > 1 ? k - 1 : 1; break; }
+        }
+        const int pslot = (int)(f0 % M), slot = (int)((f0 + 1) % M);
+        fill_lk(c, &S.lk, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
+                AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
+        S.lk_nf = (int)cnt;
+        for (long k = 0; k <= cnt; k++) {
+            const int q = (int)((f0 + k) % M);
+            for (int l = 0; l <= L; l++) T.lk.img[k][l] = l == 0 ? c->l0_ptr[q] : c->lmem[q][l];
+            if (k) {
+                T.lk.next[k - 1] = c->corners[q]; T.lk.status[k - 1] = c->status[q];
+                (void)chain;          // (arrival counters are attached below, to the frames the PnP role of THIS launch waits for)
+            }
+        }
+        S.n_lk = 1; S.lk_B = B;
+        c->n_lk += cnt;
+        any = true;
+    }
+    // frames the PnP role may take: everything tracked before this launch; chained, also the frames tracked BY it, waiting
+    // for each one's counter -- all of them when nothing more is registered (a drain: the last frames' latency counts), all
+    // but the newest while frames keep coming (the role then never stalls: the LK role works one frame ahead of it)
+    long pnp_avail = lk_before;
+    if (chain) pnp_avail = c->n_lk - (c->n_lk < c->trk_frame && c->n_lk > lk_before ? 1 : 0);
+    if (c->n_pnp < pnp_avail) {
+        long cnt = pnp_avail - c->n_pnp;
+        if (cnt > F) cnt = F;
+        const int slot = (int)((c->n_pnp + 1) % M);
+        fill_estimate(c, &S.pnp, c->corners[slot], c->status[slot], c->so_ring[slot], nullptr);
+        arm_host_seq(c, &S.pnp, c->n_pnp + 1);
+        for (long k = 0; k < cnt; k++) {
+            const long f = c->n_pnp + 1 + k;
+            const int q = (int)(f % M);
+            T.pnp.img[k] = c->corners[q]; T.pnp.mask[k] = c->status[q]; T.pnp.so[k] = c->so_ring[q];
+            if (f > lk_before) {
+                // tracked by this launch: the LK role counts the frame's corners in (device-scope stores + acknowledgement, only
+                // for the frames somebody waits for), the PnP wave waits for the count
+                c->lk_target[q] += (unsigned)c->trk_n;
+                T.lk.done[f - lk_f0 - 1] = c->lk_done + (size_t)q * c->cfg.max_streams;
+                T.pnp.wait[k] = T.lk.done[f - lk_f0 - 1]; T.pnp.target[k] = c->lk_target[q];
+            }
+        }
+        S.pnp_nf = (int)cnt;
+        S.n_pnp = B;
+        c->n_pnp += cnt;
+        any = true;
+        // knobs: AGT_CHAIN_WITHHOLD=k makes the k-th launch with chained waits expect one arrival more than its LK role delivers for the
+        // SECOND waited frame (the first if there is only one): tests/test_gpu_tracker.py drives the give-up path with it
+        if (const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD", 0)) {
+            static long seen = 0;
+            int waited[2] = { -1, -1 }, nw = 0;
+            for (long k = 0; k < cnt && nw < 2; k++) if (T.pnp.wait[k]) waited[nw++] = (int)k;
+            if (wh > 0 && nw > 0 && ++seen == wh) T.pnp.target[waited[nw - 1]] += 1;
+        }
+    }
+    if (!any) return AGT_OK;
+    // knobs: AGT_TABLE_POISON_PNP=k / AGT_TABLE_POISON_LK=k put a word that cannot be an address (the bits of a NaN) into the second
+    // frame's entry of the k-th launch whose pose / LK role runs more than one frame -- what a stale or clobbered LDS table would hand
+    // the role.  tests/test_gpu_tracker.py: the launch must drain, flag and report, not fault.
+    {
+        const long pk = AGT_KNOB("AGT_TABLE_POISON_PNP", 0), lk = AGT_KNOB("AGT_TABLE_POISON_LK", 0);
+        static long seen_p = 0, seen_l = 0;
+        if (pk > 0 && S.pnp_nf > 1 && ++seen_p == pk) T.pnp.img[1] = (const float*)0x7ff8dead00000000ull;
+        if (lk > 0 && S.lk_nf > 1 && ++seen_l == lk) T.lk.img[2][0] = (const uint8_t*)0x7ff8dead00000000ull;
+    }
+    if (agt_step_fits(c->trk_n, B)) {
+        if (AGT_KNOB("AGT_PYR_SEPARATE", 0)) {       // (knobs: the pyramid role as its own launch, ahead of LK | PnP)
+            hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
+            if (e == hipSuccess && (S.n_lk > 0 || S.n_pnp > 0)) e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_LK | AGT_STEP_PNP);
+            return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+        }
+        // a launch with pyramid work only (the first one of a run) goes out as the pyramid kernel proper: eight workgroups per
+        // CU instead of the one the fused kernel's register budget leaves (16 frames of 720p: ~7 us instead of ~12)
+        const int roles = (S.n_lk > 0 || S.n_pnp > 0) ? AGT_STEP_ALL : AGT_STEP_PYR;
+        hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, roles);
+        return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+    }
+    // ---- split mode: the same group as three launches, one per role, each with its own LDS size and register budget:
+    // pyramid on the caller's stream (the frames come from there), LK and PnP on two library streams.  The roles of one
+    // group are independent (the pipeline skews them across frames), so the three launches overlap; ordering is by events:
+    //   LK(k)  waits for pyramid(k-1)   (its images)          and for PnP(k-2)  (ring reuse of corner / status entries)
+    //   PnP(k) waits for LK(k-1)        (its corners)
+    //   pyramid(k) waits for LK(k-3)    (ring reuse of level entries: split mode keeps AGT_SPLIT_SLACK = 2 groups of extra
+    //                                    ring entries, so the HBM-bound pyramid launches run AHEAD of the LK launches they share
+    //                                    the chip with and never sit on the critical path; the wait also keeps the caller's
+    //                                    stream behind the readers of frames handed over (L + 6) groups ago, so stream-ordered
+    //                                    allocators may recycle those)
+    // Ten HIP calls per GROUP of F frames (round 1 issued thirteen per frame).
+    int rc = ms_init(c);
+    if (rc) return rc;
+    hipStream_t sL = c->ms_stream[1], sL2 = c->ms_stream[0], sY = c->ms_stream[2];
+    hipEvent_t *evP = c->ms_ev[0], *evL = c->ms_ev[1], *evY = c->ms_ev[3], *evL2 = c->ms_ev[4];
+    // The per-frame LK launches of a group depend on each other (a corner starts where it ended), leave ~4 us between one
+    // kernel's end and the next one's start on their stream, and each lasts as long as its slowest corner.  A batch of the
+    // one-wave-per-corner kernel whose halves still hold >= 512 corners goes out as two launches per frame on two streams,
+    // streams [0, B1) and [B1, B), both with the one-wave kernel: each half's gaps and tails are filled by the other half's
+    // kernel.  Every wait on / record of the LK role below is done for both streams.  (Round 3: the halves used to be taken
+    // only from 44 streams of 48 corners on; 22 .. 43 streams gain 12-20 % -- 42 streams 43.9 -> 36.6 us per step.  Four
+    // quarters on four streams lose badly -- 64 streams 160 us, 86 with GPU_MAX_HW_QUEUES=8 against 49.7: more streams than
+    // hardware queues, and four kernels of <= 1 wave per SIMD each stretch one another.)
+    const int B1 = (!agt_lk_wide(c->trk_n, B) && (long)c->trk_n * (B / 2) >= 512) ? B / 2 : B;
+    const bool two = B1 < B;
+    // A role's n-th launch records event slot n % AGT_EV_SLOTS, so the slot a wait names (at most three launches of its role old) is not
+    // re-recorded before it.  (The slots used to follow the group count: a role that sat groups out could wait on a slot that a NEWER
+    // launch of the same role and stream had re-recorded -- later completion, so that could only over-synchronise.)
+    const int p_slot = (int)(c->split_n[0] % AGT_EV_SLOTS), l_slot = (int)(c->split_n[1] % AGT_EV_SLOTS), y_slot = (int)(c->split_n[2] % AGT_EV_SLOTS);
+    bool p_work = false;
+    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) p_work |= S.n_pyr[s] > 0;
+    const int p_before = c->last_p_ev, l_before = c->l_ev_hist[0];
+    hipError_t e = hipSuccess;
+    if (p_work) {
+        if (c->l_ev_hist[AGT_SPLIT_SLACK] >= 0) {
+            e = hipStreamWaitEvent(c->stream, evL[c->l_ev_hist[AGT_SPLIT_SLACK]], 0);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, evL2[c->l_ev_hist[AGT_SPLIT_SLACK]], 0);
+        }
+        if (e == hipSuccess) e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
+        if (e == hipSuccess) e = hipEventRecord(evP[p_slot], c->stream);
+        if (e != hipSuccess) return hip_fail(c, e);
+        c->last_p_ev = p_slot; c->split_n[0]++;
+    }
+    if (S.n_lk > 0) {
+        hipEvent_t first = nullptr;
+        if (p_before >= 0) first = evP[p_before];
+        else {
+            // no pyramid launch since the last join (single-level pyramids, or the first LK of a run): order the LK streams
+            // behind the caller's stream explicitly (reset's corner copy, earlier modes' pyramids)
+            e = hipEventRecord(c->ms_ev[2][2], c->stream);
+            first = c->ms_ev[2][2];
+        }
+        for (int h = 0; h < (two ? 2 : 1) && e == hipSuccess; h++) {
+            hipStream_t sh = h ? sL2 : sL;
+            e = hipStreamWaitEvent(sh, first, 0);
+            if (e == hipSuccess && c->y_ev_hist[1] >= 0) e = hipStreamWaitEvent(sh, evY[c->y_ev_hist[1]], 0);
+        }
+        if (e != hipSuccess) return hip_fail(c, e);
+        // Up to 1024 corners in flight (the four-waves-per-corner body): the LK role of the WHOLE group as one launch --
+        // lk_group_kernel, the frame-chained body of the fused step with its own register budget (153 VGPRs, three workgroups
+        // per CU) -- instead of one ~17 us launch + ~5 us gap per frame (round 3: 16 streams 33.9 -> see profiles/r03_stream_sweep.txt).
+        bool lk_group = agt_lk_wide(c->trk_n, B);
+        { const long on = AGT_KNOB("AGT_SPLIT_LK_GROUP", 1); if (!on) lk_group = false; if (on == 2) lk_group = true; }   // (knobs; 2: also for the one-wave kernel)
+        if (lk_group) {
+            e = agt_launch_step(sL, S, T, c->cfg.win, AGT_STEP_LK);
+            if (e != hipSuccess) return hip_fail(c, e);
+        }
+        // otherwise one stand-alone LK launch per frame of the group (and half), back to back on its stream (as a role with an in-kernel
+        // frame loop the one-wave-per-corner kernel needs 240 B of scratch per lane at its 128-register budget and runs at half speed)
+        for (int k = 1; k <= S.lk_nf && !lk_group; k++) {
+            const int ps = (int)((lk_f0 + k - 1) % M), sl = (int)((lk_f0 + k) % M);
+            // (waves = 1: a half is sized by the whole batch's kernel choice, not by its own corner count)
+            // (hybrid: only the one-wave launches of big batches -- a batch that the four-wave kernel takes whole has nothing to gain)
+            const bool hyb = !agt_lk_wide(c->trk_n, B);
+            rc = lk_track_on(c, sL, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B1,
+                             AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, 0, two ? 1 : 0, hyb);
+            if (rc == AGT_OK && two)
+                rc = lk_track_on(c, sL2, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B - B1,
+                                 AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, B1, 1, hyb);
+            if (rc) return rc;
+        }
+        e = hipEventRecord(evL[l_slot], sL);
+        // (recorded on the second stream in any case: an idle stream's event is complete at once, the waits stay uniform)
+        if (e == hipSuccess) e = hipEventRecord(evL2[l_slot], two ? sL2 : sL);
+        if (e != hipSuccess) return hip_fail(c, e);
+        c->l_ev_hist[2] = c->l_ev_hist[1]; c->l_ev_hist[1] = c->l_ev_hist[0]; c->l_ev_hist[0] = l_slot; c->split_n[1]++;
+        c->ms_active = 1;
+    }
+    if (S.n_pnp > 0) {
+        if (l_before >= 0) {
+            e = hipStreamWaitEvent(sY, evL[l_before], 0);
+            if (e == hipSuccess) e = hipStreamWaitEvent(sY, evL2[l_before], 0);
+        }
+        if (e == hipSuccess) e = agt_launch_step(sY, S, T, c->cfg.win, AGT_STEP_PNP);
+        if (e == hipSuccess) e = hipEventRecord(evY[y_slot], sY);
+        if (e != hipSuccess) return hip_fail(c, e);
+        c->y_ev_hist[1] = c->y_ev_hist[0]; c->y_ev_hist[0] = y_slot; c->split_n[2]++;
+        c->ms_active = 1;
+    }
+    return AGT_OK;
+}
+
+// The part of registering frame T+1 that comes before the registration itself: ring modulus of the mode, a free ring entry.
+static int pipelined_entry(agt_ctx* c, int B)
+{
+    c->prebuilt_t = -1;
+    // ring modulus of this mode: (L + 2) groups, plus the split mode's slack when the entries are available
+    {
+        const bool split = !agt_step_fits(c->trk_n, B);
+        int groups = c->eff_max_level + 2 + (split ? AGT_SPLIT_SLACK : 0);
+        if (groups * c->group > AGT_RING_MAX) groups = c->eff_max_level + 2;
+        const int want = groups * c->group > AGT_SLOTS ? groups * c->group : AGT_SLOTS;
+        if (want != c->live_ring) {
+            int rc = join_pipeline(c);            // only the newest frame is live afterwards
+            if (rc) return rc;
+            rc = ensure_ring(c, want);
+            if (rc) return rc;
+            ring_move(c, c->trk_frame, c->live_ring, want);
+            c->live_ring = want;
+        }
+    }
+    const long t = c->trk_frame + 1;
+    // The ring entry frame t takes must be free: its previous tenant, frame t - M, has to be past its pose solve and past the
+    // LK of the frame after it (which reads it as the previous image).  The ring size follows from every stage advancing F
+    // frames per launch; groups cut short (frames of differing pitch) let stages fall behind that rhythm.
+    {
+        const long M = c->live_ring;
+        while (c->n_pnp < t - M || c->n_lk < t - M + 1) {
+            const long before = c->n_pnp + c->n_lk + c->n_stage[0];
+            int rc = launch_group(c, B);
+            if (rc) return rc;
+            if (c->n_pnp + c->n_lk + c->n_stage[0] == before) return AGT_ERR_STATE;      // (cannot happen: work was pending)
+        }
+    }
+    return AGT_OK;
+}
+
+// Register frame T+1 of the fused pipeline; a launch goes out once `group` frames wait for their first stage.
+static int step_pipelined(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B, double* d_state_out)
+{
+    int rc = pipelined_entry(c, B);
+    if (rc) return rc;
+    const long t = c->trk_frame + 1;
+    const int slot = (int)(t % c->live_ring);
+    c->l0_ptr[slot] = d_frames; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
+    c->built_B[slot] = B;
+    c->so_ring[slot] = d_state_out;
+    c->trk_frame = t;
+    const long first_done = c->eff_max_level > 0 ? c->n_stage[0] : c->n_lk;
+    if (agt_step_fits(c->trk_n, B)) {
+        if (t - first_done < c->group) return AGT_OK;
+        return launch_group(c, B);
+    }
+    // split pipeline: groups grow from split_ramp() to c->group frames while the pipeline fills (see launch_group)
+    if (c->ramp <= 0 || c->ramp > c->group) c->ramp = split_ramp(c);
+    if (t - first_done < c->ramp) return AGT_OK;
+    rc = launch_group(c, B, c->ramp);
+    c->ramp = c->ramp * 2 > c->group ? c->group : c->ramp * 2;
+    return rc;
+}
+
+// Frame T+1 of ONE stream arrives in pinned HOST memory (h_dev: its device address): upload and pyramid in one launch -- the
+// two-level register-rolling pass reads the frame over PCIe, stores its level 0 to d_gray and levels 1 / 2 to the frame's ring
+// entry (agt_pyramid.hip agt_launch_pyr_upload2) -- and the frame is registered with its pyramid stages done; the LK | PnP launch
+// follows at the join as ever.  Returns 1 when the form does not apply (geometry, pyramid work of earlier frames still pending):
+// nothing has been enqueued for the frame then and the caller copies and calls agt_track_frame.
+static int step_pipelined_uploaded(agt_ctx* c, const uint8_t* h_dev, uint8_t* d_gray, size_t gpitch, double* d_state_out)
+{
+    if (c->eff_max_level != 2 || c->trk_B != 1) return 1;
+    int rc = pipelined_entry(c, 1);
+    if (rc) return rc;
+    const long t = c->trk_frame + 1;
+    if (c->n_stage[0] != t - 1 || c->n_stage[1] != t - 1) return 1;
+    const int slot = (int)(t % c->live_ring);
+    const int W = c->cfg.width, H = c->cfg.height;
+    hipError_t e = agt_launch_pyr_upload2(c->stream, h_dev, W, H, (long)W, d_gray, (long)gpitch, c->lmem[slot][1], c->lpitch[1], c->lmem[slot][2], c->lpitch[2]);
+    if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return 1; }
+    if (e != hipSuccess) return hip_fail(c, e);
+    c->l0_ptr[slot] = d_gray; c->l0_pitch[slot] = (long)gpitch; c->l0_bstride[slot] = (long)gpitch * H;
+    c->built_B[slot] = 1;
+    c->so_ring[slot] = d_state_out;
+    c->trk_frame = t;
+    c->n_stage[0] = c->n_stage[1] = t;
+    return AGT_OK;
+}
+
+// Drain the software pipeline: enqueue the remaining stages of every frame supplied so far.
+// (Enqueue only; the results are ordered on the context's stream like any other work.)
+int join_pipeline(agt_ctx* c)
+{
+    if (c->trk_ready != 2) return AGT_OK;
+    // (split pipeline: the drain runs in groups of split_ramp() frames -- the last pose launch then trails the last LK launch by a
+    // quarter of a group instead of a whole one; afterwards the pipeline is empty and fills again in small groups)
+    const int fmax = agt_step_fits(c->trk_n, c->trk_B) ? 0 : split_ramp(c);
+    while (c->n_pnp < c->trk_frame) {
+        int rc = launch_group(c, c->trk_B, fmax);
+        if (rc) return rc;
+    }
+    c->ramp = 0;
+    return c->ms_active ? ms_join(c) : AGT_OK;
+}
+
+int agt_tracker_join(agt_ctx* c)
+{
+    if (!c) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    // (enqueue only: a give-up of a chained wait is reported once the device has written the word -- by the next
+    // agt_synchronize at the latest; the flagged records say which frames)
+    if (rc == AGT_OK && *(volatile int*)c->fault_host) rc = AGT_ERR_CHAIN;
+    return rc;
+}
+
+int agt_estimate_pose(agt_ctx* c, const float* d_img, const uint8_t* d_mask, int B, double* d_state_out)
+{
+    if (!c || !d_img) return AGT_ERR_ARG;
+    if (!c->trk_ready) return AGT_ERR_STATE;
+    if (B <= 0 || B > c->trk_B) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);            // state updates of frames in flight come first
+    if (rc) return rc;
+    AgtPnpParams p;
+    fill_estimate(c, &p, d_img, d_mask, d_state_out, nullptr);
+    hipError_t e = agt_launch_pnp(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// Dense clips (step_serial below): which of the round-4 forms are on.
+static int dense_defer_on()
+{
+    // knobs: AGT_DENSE_DEFER=0 keeps dense_final_kernel a launch of its own in clips, 1 keeps LK and the pose solve separate launches
+    return (int)AGT_KNOB("AGT_DENSE_DEFER", 2);
+}
+
+// pyrDown.. -> LK -> PnP (+ dense stage) as launches on the context's stream: pose complete in stream order.
+// next_frame != null (clip submission with the dense stage): the caller will hand that frame in next, with the same pitch and
+// stream stride -- its two-level pyramid pass rides in one of this frame's launches (the chained LK | PnP launch, the four-wave PnP
+// launch, or the second dense launch) instead of being the first launch of its own chain, and this frame's last dense step is left
+// to that frame's LK launch (c->dense_pending).
+static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B,
+                       double* d_state_out, double* d_dense_out, hipEvent_t* pev, const uint8_t* next_frame = nullptr)
+{
+    int rc = join_pipeline(c);            // a mode switch drains the pipeline first
+    if (rc) return rc;
+    const long t = c->trk_frame + 1;
+    const int slot = (int)(t % c->live_ring), pslot = (int)((t - 1) % c->live_ring);
+    hipStream_t M = c->stream;
+    if (pev) (void)hipEventRecord(pev[0], M);
+    const bool prebuilt = c->prebuilt_t == t && c->l0_ptr[slot] == d_frames && c->l0_pitch[slot] == (long)pitch &&
+                          c->l0_bstride[slot] == (long)batch_stride && c->built_B[slot] == B;
+    c->prebuilt_t = -1;
+    rc = prebuilt ? AGT_OK : pyramid_build_on(c, M, slot, d_frames, pitch, batch_stride, B);
+    if (rc) return rc;
+    if (pev) (void)hipEventRecord(pev[1], M);
+    // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
+    // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
+    // (Measured on configs[4], us per frame: no ride 89.0; in the PnP launch 84.0-84.5; in the dense launch 84.0-85.3; in the LK
+    // launch 84.5-84.8 as tiles behind the LK role launch's own workgroups, 86.5 as the pyramid role of the fused step kernel.)
+    AgtPyrArgs npyr[2];
+    const int nslot = (int)((t + 1) % c->live_ring);
+    const bool lk_role_launch = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B) && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
+    const bool ride = next_frame && c->eff_max_level == 2 && B <= AGT_PYR2_MAX_B && nslot != slot && nslot < c->ring &&
+                      ((uintptr_t)next_frame & 3) == 0 && (agt_pnp_can_ride(c->trk_n) || (d_dense_out && c->dn_iters > 0));
+    // Dense clips with the cooperative solver (64 < n <= 256): LK and PnP of the frame in ONE launch, the solver waiting for the
+    // frame's arrival count (agt_step.hip lk_pnp_coop_kernel); the next frame's pyramid pass then rides in that launch as well
+    // (while trackers + solvers are co-resident at the one workgroup per CU the solver's registers leave: more streams keep the LK
+    // launch of its own, whose 78 registers put several workgroups on a CU)
+    // (the LK role's grid is rounded up to a multiple of 8; the device's CU count, not a literal: ADVICE r4)
+    const bool chain_pnp = lk_role_launch && d_dense_out && c->dn_iters > 0 && !pev && agt_pnp_can_ride(c->trk_n) && dense_defer_on() > 1 &&
+                           (long)agt_xcd_grid((long)c->trk_n * B, 3) + B <= c->chip.cus;
+    const bool ride_pnp = ride && agt_pnp_can_ride(c->trk_n) && !chain_pnp;
+    if (ride) {
+        // (what pyramid_build_on registers for a frame, for frame t + 1 in its ring entry)
+        c->l0_ptr[nslot] = next_frame; c->l0_pitch[nslot] = (long)pitch; c->l0_bstride[nslot] = (long)batch_stride;
+        const long db1 = (long)c->lh[1] * c->lpitch[1], db2 = (long)c->lh[2] * c->lpitch[2];
+        agt_pyr2_args(next_frame, c->lw[0], c->lh[0], (long)pitch, (long)batch_stride, c->lmem[nslot][1], c->lpitch[1], db1,
+                      c->lmem[nslot][2], c->lpitch[2], db2, B, &npyr[0], &npyr[1]);
+        c->built_B[nslot] = B;
+        c->prebuilt_t = t + 1;
+    }
+    AgtPnpParams p;
+    fill_estimate(c, &p, c->corners[slot], c->status[slot], d_state_out, c->corners[slot], c->status[slot]);
+    arm_host_seq(c, &p, t);
+    if (d_dense_out) {
+        rc = dense_scratch(c, agt_dense_doubles(c->dn_M, B), B);
+        if (rc) return rc;
+        p.dense_pose = c->pose; p.dense_done = c->dense_done; p.dense_rec = d_dense_out;
+    }
+    if (lk_role_launch) {
+        // four waves per corner: the LK role of the step as a one-frame group (the frame-chained body; see agt_step.hip lk_role)
+        AgtStepParams S; AgtStepTables T;
+        memset(&S, 0, sizeof(S)); memset(&T, 0, sizeof(T));
+        fill_lk(c, &S.lk, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
+                AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
+        S.lk_nf = 1; S.n_lk = 1; S.lk_B = B;
+        for (int k = 0; k < 2; k++) {
+            const int q = k ? slot : pslot;
+            for (int l = 0; l <= c->eff_max_level; l++) T.lk.img[k][l] = l == 0 ? c->l0_ptr[q] : c->lmem[q][l];
+        }
+        T.lk.next[0] = c->corners[slot]; T.lk.status[0] = c->status[slot];
+        hipError_t e;
+        if (chain_pnp) {
+            S.pnp = p; S.pnp_nf = 1; S.n_pnp = B;
+            // (the slot's arrival target advances only once the launch is known to be out: ADVICE r4 -- a failed launch must leave
+            // the counters' bookkeeping and the deferred dense step as they were)
+            T.lk.done[0] = c->lk_done + (size_t)slot * c->cfg.max_streams;
+            T.pnp.img[0] = c->corners[slot]; T.pnp.mask[0] = c->status[slot]; T.pnp.so[0] = d_state_out;
+            T.pnp.wait[0] = T.lk.done[0]; T.pnp.target[0] = c->lk_target[slot] + (unsigned)c->trk_n;
+            // knobs: AGT_CHAIN_WITHHOLD_DENSE=k makes the k-th chained LK | PnP launch of the dense tracker expect one arrival more than
+            // its LK role delivers (tests/test_dense.py drives the solver's give-up path with it)
+            { const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD_DENSE", 0); static long seen = 0; if (wh > 0 && ++seen == wh) T.pnp.target[0] += 1; }
+        }
+        if (c->dense_pending || chain_pnp) {
+            e = agt_launch_lk_reseed(M, S, T, c->cfg.win, c->dense_pending ? &c->dense_final : nullptr, (ride && chain_pnp) ? npyr : nullptr);
+            if (e == hipSuccess) {                  // on failure dense_pending stays set: the caller's error path flushes it (agt_launch_dense_final)
+                c->dense_pending = 0;
+                if (chain_pnp) c->lk_target[slot] += (unsigned)c->trk_n;
+            }
+        } else e = agt_launch_step(M, S, T, c->cfg.win, AGT_STEP_LK);
+        if (e != hipSuccess) return hip_fail(c, e);
+    } else {
+    if (c->dense_pending) {          // (cannot happen: the deferral is decided with this frame's launch form known)
+        c->dense_pending = 0;
+        hipError_t e = agt_launch_dense_final(M, c->dense_final, B);
+        if (e != hipSuccess) return hip_fail(c, e);
+    }
+    rc = lk_track_on(c, M, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr,
+                     c->trk_n, B, AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
+    if (rc) return rc;
+    }
+    if (pev) (void)hipEventRecord(pev[2], M);
+    hipError_t e = chain_pnp ? hipSuccess : agt_launch_pnp(M, p, B, ride_pnp ? npyr : nullptr);
+    if (e != hipSuccess) return hip_fail(c, e);
+    if (pev) { (void)hipEventRecord(pev[3], M); c->prof_n++; }
+    if (d_dense_out) {
+        // Clip submission: the stage's last step (final update + re-seed, a one-workgroup launch of 5.5 us) is left to the NEXT
+        // frame's LK launch, whose workgroups do it as their prologue (agt_step.hip lk_reseed_kernel) -- when that launch will be the
+        // four-waves-per-corner LK role launch (same geometry as this frame's) and no stage spans are being recorded
+        const bool defer = next_frame && !pev && c->dn_iters > 0 && c->cfg.win == 21 && agt_lk_wide(c->trk_n, B) && dense_defer_on();
+        // dense photometric + geometric refinement of the frame's accepted pose, then (reseed) the corner set from it
+        e = agt_launch_dense(M, d_frames, (long)pitch, (long)batch_stride, c->cfg.width, c->cfg.height, c->dn_xyz, c->dn_t, c->dn_M,
+                             c->obj, c->corners[slot], c->status[slot], c->trk_n, c->cam, c->pose, c->dense_partials, nullptr,
+                             c->dense_done, B, c->dn_iters, c->dn_weight, 1e-3, d_dense_out, c->dn_reseed ? c->corners[slot] : nullptr,
+                             c->dn_reseed ? c->status[slot] : nullptr, pev ? pev + 4 : nullptr, 2 * AGT_PROF_DENSE_MAX, (ride && !ride_pnp && !chain_pnp) ? npyr : nullptr,
+                             defer ? &c->dense_final : nullptr);
+        if (e == hipSuccess && defer) c->dense_pending = 1;
+        if (pev) c->prof_dense[c->prof_n - 1] = c->dn_iters < AGT_PROF_DENSE_MAX ? c->dn_iters : AGT_PROF_DENSE_MAX;
+        if (e != hipSuccess) return hip_fail(c, e);
+    }
+    c->trk_frame = t; c->n_lk = c->n_pnp = t;
+    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = t;
+    return AGT_OK;
+}
+
+// One frame for B streams.
+//   pipeline on  (default, needs reproject == 0): ONE fused launch; frame t's pose is produced
+//                 L+1 launches later (or by agt_tracker_join / agt_synchronize).
+//   pipeline off : pyrDown.. -> LK -> PnP as separate launches, pose complete in stream order.
+int agt_track_frame(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B,
+                    double* d_state_out)
+{
+    if (!c || !d_frames) return AGT_ERR_ARG;
+    if (c->trk_ready != 2) return AGT_ERR_STATE;
+    if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
+    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+    // the fused launch pays off while the stages are latency-bound (few streams); the biggest batches fill
+    // the chip per stage and run faster as separate launches with their own register budgets
+    if (c->pipeline && !c->reproject && (agt_step_fits(c->trk_n, B) || !pev)) {
+        // fused launch: the three spans collapse into one (span 2 = the whole step_kernel launch)
+        if (pev) { (void)hipEventRecord(pev[0], c->stream); (void)hipEventRecord(pev[1], c->stream); (void)hipEventRecord(pev[2], c->stream); }
+        int rc = step_pipelined(c, d_frames, pitch, batch_stride, B, d_state_out);
+        if (pev && rc == AGT_OK) { (void)hipEventRecord(pev[3], c->stream); c->prof_n++; }
+        return rc;
+    }
+
+    return step_serial(c, d_frames, pitch, batch_stride, B, d_state_out, nullptr, pev);
+}
+
+int agt_track_frames(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, size_t frame_stride, int B, int count,
+                     double* d_state_out)
+{
+    if (count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
+    for (int k = 0; k < count; k++) {
+        int rc = agt_track_frame(c, d_frames + (size_t)k * frame_stride, pitch, batch_stride, B,
+                                 d_state_out ? d_state_out + (size_t)k * B * AGT_STATE_STRIDE : nullptr);
+        if (rc) return rc;
+    }
+    return AGT_OK;
+}
+
+// A frame whose corners come from the detector (detect_pose.py:389-437 found >= 2 tags, so the reference does not track):
+// the frame joins the stream as frame t (its pyramid is built: the next agt_track_frame tracks FROM it), the supplied table
+// becomes the frame's corner set and LK status, and _estimate_pose runs on it -- pyramid pass + one PnP launch, in stream order.
+int agt_track_frame_detected(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B,
+                             const float* d_corners, const uint8_t* d_mask, double* d_state_out)
+{
+    if (!c || !d_frames || !d_corners) return AGT_ERR_ARG;
+    if (!c->trk_ready) return AGT_ERR_STATE;
+    if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
+    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->prebuilt_t = -1;
+    const long t = c->trk_frame + 1;
+    const int slot = (int)(t % c->live_ring);
+    rc = pyramid_build_on(c, c->stream, slot, d_frames, pitch, batch_stride, B);
+    if (rc) return rc;
+    AgtPnpParams p;
+    fill_estimate(c, &p, d_corners, d_mask, d_state_out, c->corners[slot], c->status[slot]);
+    p.seed_pts = c->corners[slot]; p.seed_status = c->status[slot];
+    hipError_t e = agt_launch_pnp(c->stream, p, B);
+    if (e != hipSuccess) return hip_fail(c, e);
+    c->trk_frame = t; c->n_lk = c->n_pnp = t;
+    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = t;
+    c->trk_ready = 2;
+    return AGT_OK;
+}
+
+// undistort (optional) + BGR2GRAY + ROI crop in one pass: BGR (src_w x src_h) -> gray (roi_w x roi_h)
+int agt_preprocess_bgr(agt_ctx* c, const uint8_t* d_bgr, size_t spitch, size_t sbatch, int src_w, int src_h, int B,
+                       int undistort, int roi_x, int roi_y, int roi_w, int roi_h,
+                       uint8_t* d_gray, size_t gpitch, size_t gbatch)
+{
+    if (!c || !d_bgr || !d_gray || B <= 0 || src_w <= 0 || src_h <= 0) return AGT_ERR_ARG;
+    if (roi_x < 0 || roi_y < 0 || roi_w <= 0 || roi_h <= 0 || roi_x + roi_w > src_w || roi_y + roi_h > src_h) return AGT_ERR_ARG;
+    if (spitch < (size_t)src_w * 3 || gpitch < (size_t)roi_w) return AGT_ERR_ARG;
+    if (undistort && (!c->map1 || c->map_w != src_w || c->map_h != src_h)) return AGT_ERR_STATE;
+    hipError_t e = agt_launch_preprocess(c->stream, d_bgr, (long)spitch, (long)sbatch, src_w, src_h, c->map1, c->map2, src_w,
+                                         roi_x, roi_y, roi_w, roi_h, d_gray, (long)gpitch, (long)gbatch, undistort ? 1 : 0, 1, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// The live camera loop in ONE call (detect_pose.py:669-681, LK path): host frame -> HBM -> [undistort / gray / crop] -> agt_track_frame
+// -> join -> record back -> wait.  Everything a Python caller would otherwise issue as five separate foreign calls.
+int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int src_w, int src_h, uint8_t* d_staging,
+                         int undistort, int roi_x, int roi_y, uint8_t* d_gray, size_t gpitch, double* d_state, double* h_state)
+{
+    if (!c || !h_frame || !d_gray || !h_state || (channels != 1 && channels != 3)) return AGT_ERR_ARG;
+    if (c->trk_ready != 2 || c->trk_B != 1) return AGT_ERR_STATE;
+    const int W = c->cfg.width, H = c->cfg.height;
+    hipError_t e;
+#ifdef AGT_DEBUG_KNOBS      // diagnostic library only: AGT_HOST_FRAME_TIMES=1 prints where the host time of this call goes (us, mean) at exit
+    struct Acc { double t[6]; long n; ~Acc() { if (n) fprintf(stderr, "agt_track_host_frame host us: upload-call %.2f track-call %.2f join %.2f d2h-call %.2f sync %.2f total %.2f (n=%ld)\n",
+                                                              t[0] / n, t[1] / n, t[2] / n, t[3] / n, t[4] / n, t[5] / n, n); } };
+    static Acc acc = {};
+    const long timing = AGT_KNOB("AGT_HOST_FRAME_TIMES", 0);
+    auto now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
+    double tq[6] = { 0, 0, 0, 0, 0, 0 };
+    if (timing) tq[0] = now();
+#define AGT_TQ(i) do { if (timing) tq[i] = now(); } while (0)
+#else
+#define AGT_TQ(i)
+#endif
+    // Polled record: the frame's record goes straight to host-mapped memory of the context and the solver stores a sequence word behind
+    // it (system scope); this thread polls the word -- no 128-byte copy (a blit KERNEL of ~4.5 us behind the step's launch,
+    // rocprofv3), no completion signal, no stream wait.  (With profiling spans armed the call waits for the stream as before.)
+    bool polled = !(c->prof_ev && c->prof_n < c->prof_cap);
+    if (!AGT_KNOB("AGT_HOST_POLL", 1)) polled = false;       // (knobs: AGT_HOST_POLL=0 takes the waited form)
+    double* const d_rec = (polled || !d_state) ? c->hrec_dev : d_state;       // where the pose solver writes the frame's record
+    bool registered = false;
+    // (the device address of the caller's buffer when it is pinned host memory, asked for on EVERY call: a cached answer would outlive the buffer)
+    const uint8_t* h_dev = nullptr;
+    {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, h_frame) == hipSuccess && at.type == hipMemoryTypeHost) h_dev = (const uint8_t*)at.devicePointer;
+        else (void)hipGetLastError();
+    }
+    if (channels == 1) {
+        if (src_w != W || src_h != H || roi_x || roi_y || undistort) return AGT_ERR_ARG;
+        // Round 4: a gray frame in PINNED host memory is not copied first: the two-level pyramid pass reads it over PCIe and writes its
+        // level 0 to d_gray on the way (step_pipelined_uploaded) -- one launch instead of a copy-engine transfer (19 us + ~8 us of
+        // submission and hand-over) and a pyramid launch (6 us).  Pageable memory, frame sizes the rolling pass does not take, the
+        // stage-by-stage mode and pending pyramid work of earlier frames keep the copy.
+        if (c->pipeline && !c->reproject && agt_step_fits(c->trk_n, 1) && !(c->prof_ev && c->prof_n < c->prof_cap)) {
+            if (h_dev) {
+                int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
+                if (rcu < 0) return rcu;
+                registered = rcu == AGT_OK;
+            }
+        }
+        if (!registered) {
+            if (gpitch == (size_t)W) e = hipMemcpyAsync(d_gray, h_frame, (size_t)W * H, hipMemcpyHostToDevice, c->stream);
+            else e = hipMemcpy2DAsync(d_gray, gpitch, h_frame, (size_t)W, (size_t)W, (size_t)H, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e);
+        }
+    } else {
+        // BGR: without undistortion the gray conversion streams through the frame once -- from pinned host memory it reads the frame
+        // over PCIe itself (no 2.8 MB copy first); the undistortion's gather keeps the frame in HBM (d_staging)
+        const uint8_t* src = d_staging;
+        if (h_dev && !undistort) src = h_dev;
+        else {
+            if (!d_staging) return AGT_ERR_ARG;
+            e = hipMemcpyAsync(d_staging, h_frame, (size_t)src_w * src_h * 3, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e);
+        }
+        int rc = agt_preprocess_bgr(c, src, (size_t)src_w * 3, (size_t)src_w * src_h * 3, src_w, src_h, 1, undistort, roi_x, roi_y, W, H,
+                                    d_gray, gpitch, gpitch * (size_t)H);
+        if (rc) return rc;
+    }
+    AGT_TQ(1);
+    int rc = AGT_OK;
+    unsigned long long want = 0;
+    if (polled) c->host_seq_on = 1;            // (every pose launch issued from here on reports the frames it solves)
+    if (!registered) rc = agt_track_frame(c, d_gray, gpitch, gpitch * (size_t)H, 1, d_rec);
+    if (polled && rc == AGT_OK) { want = c->hseq_off + (unsigned long long)c->trk_frame; c->hseq_last = want; }
+    if (rc == AGT_OK) { AGT_TQ(2); rc = join_pipeline(c); }
+    c->host_seq_on = 0;
+    if (rc) return rc;
+    AGT_TQ(3);
+    if (polled) {
+        if (d_state) {          // the device copy of the record, for callers that keep one (stream-ordered; nobody waits for it here)
+            e = hipMemcpyAsync(d_state, c->hrec_dev, AGT_STATE_STRIDE * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e);
+        }
+        AGT_TQ(4);
+        rc = poll_seq(c, c->hseq_host, want);
+        if (rc) return rc;
+        memcpy(h_state, c->hrec_host, AGT_STATE_STRIDE * sizeof(double));
+#ifdef AGT_DEBUG_KNOBS
+        if (timing) { const double t5 = now(); for (int i = 0; i < 4; i++) acc.t[i] += tq[i + 1] - tq[i]; acc.t[4] += t5 - tq[4]; acc.t[5] += t5 - tq[0]; acc.n++; }
+#endif
+        return *(volatile int*)c->fault_host ? AGT_ERR_CHAIN : AGT_OK;
+    }
+    // (the waited form: profiling spans armed, or the knobs build's AGT_HOST_POLL=0.  HSA_ENABLE_SDMA=0 -- blit-kernel copies -- made
+    // the copy-first form of round 3 slower still: 107 us.)
+    if (d_state) {
+        e = hipMemcpyAsync(h_state, d_state, AGT_STATE_STRIDE * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        AGT_TQ(4);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return hip_fail(c, e);
+    } else {                                   // (no device record asked for: the record is in the context's host-mapped memory once the stream is done)
+        AGT_TQ(4);
+        e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return hip_fail(c, e);
+        memcpy(h_state, c->hrec_host, AGT_STATE_STRIDE * sizeof(double));
+    }
+#ifdef AGT_DEBUG_KNOBS
+    if (timing) { const double t5 = now(); for (int i = 0; i < 4; i++) acc.t[i] += tq[i + 1] - tq[i]; acc.t[4] += t5 - tq[4]; acc.t[5] += t5 - tq[0]; acc.n++; }
+#endif
+    return *(volatile int*)c->fault_host ? AGT_ERR_CHAIN : AGT_OK;
+}
+
+// detect_pose.py:570-574 / the mirror's `if ids:`: a frame in which LK lost EVERY tag does not become the "previous" frame --
+// the next frame is tracked from the frame before it, with that frame's corner set and status.  The host sees the record
+// (AGT_ST_NTRACK == 0) and takes the frame back: its ring entry is re-used by the next frame, entry t - 1 (never written since)
+// is the LK source again.  The pose state machine keeps what the lost frame did to it (guess cleared), as in the reference.
+int agt_tracker_rewind(agt_ctx* c)
+{
+    if (!c) return AGT_ERR_ARG;
+    if (c->trk_ready != 2 || c->trk_frame < 1) return AGT_ERR_STATE;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->prebuilt_t = -1;
+    c->trk_frame -= 1;
+    c->hseq_off += 1;                         // (the next frame re-uses the frame index: its sequence number must not)
+    c->n_lk = c->n_pnp = c->trk_frame;
+    for (int s = 0; s < AGT_MAX_LEVELS; s++)
+        if (c->n_stage[s] > c->trk_frame) c->n_stage[s] = c->trk_frame;
+    return AGT_OK;
+}
+
+int agt_tracker_state_size(void) { return (int)sizeof(AgtTrackState); }
+
+int agt_tracker_state_read(agt_ctx* c, void* host_dst, int B)
+{
+    if (!c || !host_dst || !c->trk_ready || B <= 0 || B > c->trk_B) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(host_dst, c->tstate, (size_t)B * sizeof(AgtTrackState), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// valid after agt_tracker_join: the newest frame's corner set and LK status
+int agt_tracker_buffers(const agt_ctx* c, const float** d_corners, const uint8_t** d_status)
+{
+    if (!c || !c->trk_ready) return AGT_ERR_STATE;
+    if (d_corners) *d_corners = c->corners[c->trk_frame % c->live_ring];
+    if (d_status) *d_status = c->status[c->trk_frame % c->live_ring];
+    return AGT_OK;
+}
+
+// dense stage of the per-frame step (BASELINE configs[4]); semantics in include/agt_hip.h
+int agt_tracker_dense(agt_ctx* c, const float* d_model_xyz, const float* d_model_t, int M, int iters, double photo_weight, int reseed)
+{
+    if (!c || M < 0 || iters < 0 || iters > 1000 || !(photo_weight >= 0.0)) return AGT_ERR_ARG;
+    if (M > 0 && (!d_model_xyz || !d_model_t || iters == 0)) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->dn_xyz = M ? d_model_xyz : nullptr; c->dn_t = M ? d_model_t : nullptr; c->dn_M = M;
+    c->dn_iters = iters; c->dn_weight = photo_weight; c->dn_reseed = reseed ? 1 : 0;
+    return AGT_OK;
+}
+
+int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B,
+                          double* d_state_out, double* d_dense_out)
+{
+    if (!c || !d_frames || !d_dense_out) return AGT_ERR_ARG;
+    if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
+    if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
+    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+    return step_serial(c, d_frames, pitch, batch_stride, B, d_state_out, d_dense_out, pev);
+}
+
+// `count` consecutive frames of the stream(s), frame k at d_frames + k * frame_stride: agt_track_frame_dense for each, in order.
+// Knowing the next frame, the library lets its pyramid pass ride in the current frame's four-wave PnP launch or second dense launch (step_serial) --
+// same records, one launch less in every frame's serial chain.
+int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, size_t frame_stride, int B, int count,
+                           double* d_state_out, double* d_dense_out)
+{
+    if (!c || !d_frames || !d_dense_out || count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
+    if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
+    if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
+    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    for (int k = 0; k < count; k++) {
+        hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+        int rc = step_serial(c, d_frames + (size_t)k * frame_stride, pitch, batch_stride, B,
+                             d_state_out ? d_state_out + (size_t)k * B * AGT_STATE_STRIDE : nullptr,
+                             d_dense_out + (size_t)k * B * AGT_DENSE_STRIDE, pev, k + 1 < count ? d_frames + (size_t)(k + 1) * frame_stride : nullptr);
+        if (rc) {
+            if (c->dense_pending) { c->dense_pending = 0; (void)agt_launch_dense_final(c->stream, c->dense_final, B); }     // (a frame failed before its LK launch)
+            return rc;
+        }
+    }
+    return AGT_OK;
+}
+
+int agt_profile_begin(agt_ctx* c, int max_frames)
+{
+    if (!c || max_frames <= 0 || max_frames > (1 << 20) || c->prof_ev) return AGT_ERR_ARG;
+    const size_t n = (size_t)max_frames * AGT_PROF_EVENTS;
+    c->prof_ev = new (std::nothrow) hipEvent_t[n];
+    if (!c->prof_ev) return AGT_ERR_ALLOC;
+    for (size_t i = 0; i < n; i++) {
+        hipError_t e = hipEventCreate(&c->prof_ev[i]);
+        if (e != hipSuccess) {
+            for (size_t j = 0; j < i; j++) (void)hipEventDestroy(c->prof_ev[j]);
+            delete[] c->prof_ev; c->prof_ev = nullptr;
+            return hip_fail(c, e);
+        }
+    }
+    c->prof_dense = new (std::nothrow) int[max_frames];
+    if (!c->prof_dense) { for (size_t j = 0; j < n; j++) (void)hipEventDestroy(c->prof_ev[j]); delete[] c->prof_ev; c->prof_ev = nullptr; return AGT_ERR_ALLOC; }
+    for (int i = 0; i < max_frames; i++) c->prof_dense[i] = 0;
+    c->prof_cap = max_frames; c->prof_n = 0;
+    return AGT_OK;
+}
+
+int agt_profile_end(agt_ctx* c, float* ms_out, int* n_frames)
+{
+    if (!c || !c->prof_ev) return AGT_ERR_ARG;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    int rc = e == hipSuccess ? AGT_OK : hip_fail(c, e);
+    if (rc == AGT_OK && ms_out)
+        for (int f = 0; f < c->prof_n && rc == AGT_OK; f++) {
+            hipEvent_t* ev = c->prof_ev + (size_t)f * AGT_PROF_EVENTS;
+            for (int k = 0; k < 3; k++) {
+                e = hipEventElapsedTime(&ms_out[f * AGT_PROF_SPANS + k], ev[k], ev[k + 1]);
+                if (e != hipSuccess) { rc = hip_fail(c, e); break; }
+            }
+            // dense stage: ev[3] = its start, ev[4] after the last Gauss-Newton launch, ev[5] after the final launch
+            float acc = 0.f, upd = 0.f;
+            if (c->prof_dense[f] > 0 && rc == AGT_OK) {
+                e = hipEventElapsedTime(&acc, ev[3], ev[4]);
+                if (e == hipSuccess) e = hipEventElapsedTime(&upd, ev[4], ev[5]);
+                if (e != hipSuccess) { rc = hip_fail(c, e); break; }
+            }
+            ms_out[f * AGT_PROF_SPANS + 3] = acc; ms_out[f * AGT_PROF_SPANS + 4] = upd;
+        }
+    if (n_frames) *n_frames = c->prof_n;
+    for (size_t i = 0; i < (size_t)c->prof_cap * AGT_PROF_EVENTS; i++) (void)hipEventDestroy(c->prof_ev[i]);
+    delete[] c->prof_ev; c->prof_ev = nullptr; c->prof_cap = c->prof_n = 0;
+    delete[] c->prof_dense; c->prof_dense = nullptr;
+    return rc;
+}

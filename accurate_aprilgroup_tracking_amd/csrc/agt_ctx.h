@@ -1,0 +1,137 @@
+// agt_ctx.h -- the context of the C ABI and the host internals its sources share (agt_api.hip: context lifecycle and the device
+// table; agt_api_calls.hip: the stateless calls; agt_api_tracker.hip: the tracker; agt_api_undistort.hip: undistortion).
+// The entry points take their C linkage from include/agt_hip.h; nothing declared here leaves the library (agt_hip.map).
+#pragma once
+#include "agt_kernels.h"
+#include "agt_knobs.h"
+#include <time.h>
+
+#define AGT_SLOTS 4              // ring entries every context owns (slots 0 / 1 are also the public pyramid slots)
+#define AGT_RING_MAX 224         // (levels + 1) * AGT_MAX_GROUP frames in flight at the deepest pipeline
+#define AGT_EV_SLOTS 8           // events of the split pipeline, per kind: a launch waits for events at most three launches of their role old (l_ev_hist), slots are re-recorded modulo 8
+// The two-level pyramid pass saves a launch / pipeline stage and 16 % of the pyramid's HBM bytes, but its 41 KB workgroups
+// (3 per CU, eight barriers per tile) stream at 2.5 TB/s against 3.9 + 3.4 TB/s for two single-level passes (8 per CU): it is
+// used where the stage count matters (few streams), the two passes where throughput does (measured at 64 x 720p: 30.5 vs 25 us).
+#define AGT_PYR2_MAX_B 8
+#define AGT_TILT_SLOTS 8          // device table of tilted-sensor matrices: slot 0 the tracker's camera, 1.. the stateless calls'
+#define AGT_SPLIT_SLACK 2        // split mode: groups of extra ring entries (pyramid launches run that far ahead of LK)
+
+struct agt_ctx {
+    agt_config cfg;
+    AgtChip chip;                            // the device the context was created on (CU / XCD counts: launch rules and block orders)
+    int lk_cap_cu;                           // agt_lk_occupancy_cu: resident one-wave LK workgroups per CU (0 = no cap, -1 = the library's choice)
+    hipStream_t stream;
+    int last_hip;
+    int eff_max_level;                       // after OpenCV's early stop
+    int lw[AGT_MAX_LEVELS], lh[AGT_MAX_LEVELS];
+    long lpitch[AGT_MAX_LEVELS];             // levels >= 1 (context-owned)
+    char* hcall_host; char* hcall_dev; unsigned long long hcall_n;      // host-mapped staging of the synchronous host-array calls (agt_solve_pnp_host)
+    double* d_tilt; double tilt_host[AGT_TILT_SLOTS][18]; int tilt_valid[AGT_TILT_SLOTS]; int tilt_next;   // tilted-sensor matrices (camera_on)
+    uint8_t* lmem[AGT_RING_MAX][AGT_MAX_LEVELS];
+    const uint8_t* l0_ptr[AGT_RING_MAX];
+    long l0_pitch[AGT_RING_MAX], l0_bstride[AGT_RING_MAX];
+    int built_B[AGT_RING_MAX];
+    // tracker: rings (frame t lives in entry t % ring) so that one fused launch can work on pyramid
+    // stage s of frames t-sF.., LK of frames t-LF.. and PnP of frames t-(L+1)F.. at once (F = group)
+    int ring;                                // allocated ring entries: >= (L + 2) * group
+    float* corners[AGT_RING_MAX];            // [B][n][2]
+    uint8_t* status[AGT_RING_MAX];           // [B][n]
+    uint8_t* lk_iters[AGT_RING_MAX];         // [B][n] iterations every corner took in the frame of the ring entry (hybrid LK launch: a hint, never a result)
+    int lk_slow_thr;                         // agt_lk_hybrid: corners at or above it in the previous frame are tracked by four waves (0 = off)
+    double* so_ring[AGT_RING_MAX];           // caller's state_out of the frames in flight
+    int pipeline;                            // 1 = software-pipelined fused step (agt_step.hip)
+    int group;                               // frames per fused launch (1..AGT_MAX_GROUP)
+    int ramp;                                // split pipeline: frames per group while the pipeline fills (launch_group: split_ramp)
+    int live_ring;                           // ring modulus in use (<= ring): (L + 2) * group, at least AGT_SLOTS
+    // big batches: the three stages of a step run on three library-owned streams (stage kernels of different frames
+    // overlap: 57 us against 93 us back to back at 64 streams); events carry the exact dependencies
+    hipStream_t ms_stream[3];                // pyramid, LK, PnP
+    hipEvent_t ms_ev[5][AGT_EV_SLOTS];       // per launch of the role (split_n modulo AGT_EV_SLOTS): pyramid done, LK done, [2]: join / hand-over events, PnP done, LK done (second half of the streams)
+    int ms_pool_slot;                        // which set of the process's library streams the context holds (-1: none)
+    int ms_ready, ms_active;                 // streams / events exist; frames are in flight on them
+    // split mode (more corners in flight than the fused launch takes): the pipeline's groups go out as three launches,
+    // pyramid on the caller's stream, LK and PnP on library streams (ms_stream[1], [2])
+    long split_n[3];                         // launches issued in split mode per role: pyramid, LK, PnP
+    int last_p_ev;                           // event slot of the most recent pyramid launch (-1 = none)
+    int l_ev_hist[3];                        // event slots of the three most recent LK launches (-1 = none)
+    int y_ev_hist[2];                        // event slots of the two most recent PnP launches (-1 = none)
+    long trk_frame;                          // frames supplied since reset (0 = only the reset frame)
+    long prebuilt_t = -1;                    // serial step, clip submission: frame whose pyramid the previous frame's dense launch built (-1 = none)
+    // clip submission of the dense stage: the previous frame's last step (final update + re-seed) waits for this frame's LK launch
+    // (agt_step.hip lk_reseed_kernel); only ever set between two frames of one agt_track_frames_dense call
+    int dense_pending = 0;
+    AgtDenseFinal dense_final;
+    long n_stage[AGT_MAX_LEVELS];            // frames whose pyramid stage s (level s -> s+1) is done
+    long n_lk, n_pnp;                        // frames whose LK / PnP is done (enqueued)
+    // chained launches (fused step): per ring entry, [max_streams] arrival counters the LK role counts corners into and
+    // the PnP role of the same launch waits on; lk_target = the value the entry's counters reach once every corner
+    // of its current frame is written (counters only ever grow: no reset, no reuse hazard)
+    unsigned* lk_done;
+    unsigned lk_target[AGT_RING_MAX];
+    float* lkerr;                            // [B][n]
+    float* obj;                              // [n][3]
+    double* pose;                            // [B][6]
+    AgtTrackState* tstate;                   // [B]
+    AgtCameraHost cam;
+    int trk_n, trk_B, enhance_ape, trk_ready;
+    int reproject, min_points, tag_gate;
+    double gate_px;
+    int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
+    // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
+    // record, +192 the word); seq(frame t) = hseq_off + t, monotonic across resets and rewinds
+    double* hrec_host; double* hrec_dev; unsigned long long* hseq_host; unsigned long long* hseq_dev;
+    unsigned long long hseq_off, hseq_last; int host_seq_on;
+    // LK parameters of the fused step (COUNT+EPS (30, 0.01), minEig 1e-4, flags 0)
+    int lk_max_count; double lk_eps; double lk_min_eig;
+    // undistortion maps of the pre-processing stage (built once per camera)
+    short2* map1; unsigned short* map2; int map_w, map_h;
+    // scratch of the dense refinement: per-block partial sums and the per-stream done words
+    double* dense_partials; int* dense_done; size_t dense_cap; int dense_done_B;   // capacities: doubles / streams
+    // dense stage of the tracker (agt_tracker_dense): model retained by pointer
+    const float* dn_xyz; const float* dn_t; int dn_M, dn_iters, dn_reseed; double dn_weight;
+    // optional per-kernel timing (agt_profile_begin/end)
+    hipEvent_t* prof_ev;
+    int prof_cap, prof_n;
+    int* prof_dense;                         // per recorded frame: dense iterations whose launches carry events
+};
+
+// agt_api.hip
+int hip_fail(agt_ctx* c, hipError_t e);
+int fill_camera(const double* K, const double* dist, int ndist, AgtCameraHost* cam, AgtTiltHost* tilt = nullptr);
+int camera_on(agt_ctx* c, const double* K, const double* dist, int ndist, AgtCameraHost* cam, bool tracker = false);
+int ensure_ring(agt_ctx* c, int want);
+int ms_pool_acquire(int device, hipStream_t out[3]);
+
+// agt_api_tracker.hip
+int dense_scratch(agt_ctx* c, size_t need, int B);
+int join_pipeline(agt_ctx* c);
+int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B);
+int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
+                const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
+                int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                int flags, double min_eig_threshold, int b0 = 0, int waves = 0, bool hybrid = false);
+int lk_lds_min(int per_cu);
+
+// Wait for a sequence word in host-mapped memory that a kernel stores behind its results (system scope) to reach `want`; after 2 s
+// without it the stream is asked what happened (a launch failed, the device is gone).  Inline: the per-frame caller keeps it in its unit.
+inline int poll_seq(agt_ctx* c, const volatile unsigned long long* seq, unsigned long long want)
+{
+    timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (unsigned long spins = 1; *seq < want; spins++) {
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#else
+        __asm__ __volatile__("" ::: "memory");       // (other hosts: a compiler barrier; the volatile load above is the poll)
+#endif
+        if ((spins & 0xffff) == 0) {
+            timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+            if ((t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9 > 2.0) {
+                hipError_t e = hipStreamSynchronize(c->stream);
+                if (e != hipSuccess) return hip_fail(c, e);
+                if (*seq < want) return AGT_ERR_STATE;
+            }
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return AGT_OK;
+}

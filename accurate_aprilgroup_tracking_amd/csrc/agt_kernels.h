@@ -23,6 +23,8 @@ struct AgtChip {
     int xshift;               // log2(xcds)
     char arch[32];            // gcnArchName up to the first ':'
 };
+// gfx950: 160 KB of LDS per CU (MI355X_MICROARCH.md; hipDeviceProp_t reports the 64 KB a workgroup may ask for, not this)
+constexpr long AGT_LDS_PER_CU = 160L * 1024;
 __host__ __device__ inline int agt_xcd_order(int b, int nblk, int xshift)
 {
     return (b & ((1 << xshift) - 1)) * (nblk >> xshift) + (b >> xshift);

@@ -1,5 +1,5 @@
 // agt_lk.hip -- stand-alone cv::calcOpticalFlowPyrLK launch (body and design notes: agt_lk_body.h).
-#include <cstdlib>
+#include "agt_knobs.h"
 #include "agt_lk_rs_body.h"
 #include "agt_lk_any_body.h"
 
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
     if (NW == 1) asm volatile("" ::: "v" AGT_STR(AGT_LK_TOUCH_VGPR));
 #endif
     // issue priority 1 for every tracker wave of a context that has DECLARED co-tenancy (agt_lk_occupancy_cu with a count: its launches share
-    // the device with other contexts' pyramid passes, agt_api.hip lk_track_on sets the internal flag): cold pairs 44.4-44.6 -> 43.3-43.4 us per
+    // the device with other contexts' pyramid passes, agt_api_tracker.hip lk_track_on sets the internal flag): cold pairs 44.4-44.6 -> 43.3-43.4 us per
     // step (priority 2: the same).  Not for the split pipeline's own launches: c3 37.3-37.6 -> 37.8-38.1 (profiles/r06_experiments.md 17)
     const bool cotenant = NW == 1 && (P.flags & AGT_LK_FLAG_COTENANT) != 0;
     if (cotenant) __builtin_amdgcn_s_setprio(1);
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
     agt_lk::lk_body<WIN, NW, NLEV>(&P, bX, bY, lds, io, ox, oy, ost);
 }
 
-#ifdef AGT_DEBUG_KNOBS      // measured and not shipped: agt_api.hip lk_track_on
+#ifdef AGT_DEBUG_KNOBS      // measured and not shipped: agt_api_tracker.hip lk_track_on
 // HYBRID launch (round 5, win 21, big batches): 256-thread workgroups in two roles.  Workgroups [0, n4) are the FOUR-WAVE role, one
 // per corner (XCD-aware order): the corner is tracked here if it took >= slow_thr iterations in the previous frame, else the
 // workgroup exits at once.  Workgroups [n4, n4 + nquad) are the ONE-WAVE role: wave w tracks corner 4 q + w (q in XCD-aware order:
@@ -132,9 +132,8 @@ hipError_t launch_lk_t(hipStream_t stream, const AgtLkParams& p_in, int B)
     p.xshift = agt_chip_current().xshift;
     size_t lds = agt_lk::lk_lds_bytes<WIN, NW>(p.max_level + 1);
     if (NW == 1 && (size_t)p.lds_min > lds) lds = (size_t)p.lds_min;          // agt_lk_occupancy_cu: fewer resident LK waves per CU
-#ifdef AGT_DEBUG_KNOBS      // AGT_LK_LDS_PAD=bytes: extra LDS per workgroup = fewer LK waves per CU (room for other kernels' waves beside them)
-    { static const long pad = [] { const char* e = getenv("AGT_LK_LDS_PAD"); return e ? atol(e) : 0L; }(); if (pad > 0 && NW == 1) lds += (size_t)pad; }
-#endif
+    // knobs: AGT_LK_LDS_PAD=bytes: extra LDS per workgroup = fewer LK waves per CU (room for other kernels' waves beside them)
+    { const long pad = AGT_KNOB("AGT_LK_LDS_PAD", 0); if (pad > 0 && NW == 1) lds += (size_t)pad; }
     const long total = (long)p.n * B;
     if (total <= 0 || total > (1L << 30)) return hipErrorInvalidValue;
     const dim3 grid(agt_xcd_grid(total, p.xshift)), block(AGT_WAVE * NW);
@@ -185,12 +184,7 @@ bool agt_lk_window_supported(int win)
 // matters), 1 for large batches (throughput matters)
 bool agt_lk_wide(int n, int B)
 {
-#ifdef AGT_DEBUG_KNOBS
-    static const long cap = [] { const char* e = getenv("AGT_LK_WIDE_MAX"); return e ? atol(e) : 1024L; }();
-#else
-    const long cap = 1024;
-#endif
-    return (long)n * B <= cap;
+    return (long)n * B <= AGT_KNOB("AGT_LK_WIDE_MAX", 1024);
 }
 
 #ifdef AGT_DEBUG_KNOBS
@@ -215,9 +209,7 @@ hipError_t agt_launch_lk_hybrid(hipStream_t, const AgtLkParams&, int) { return h
 hipError_t agt_launch_lk(hipStream_t stream, const AgtLkParams& p_in, int win, int B, int waves)
 {
     AgtLkParams p = p_in;
-#ifdef AGT_DEBUG_KNOBS      // diagnostic library only: AGT_LK_RS=0 keeps every corner on the general body (flag bit 16, internal)
-    { static const int rs = [] { const char* e = getenv("AGT_LK_RS"); return e ? atoi(e) : 1; }(); if (!rs) p.flags |= 0x10000; }
-#endif
+    if (!AGT_KNOB("AGT_LK_RS", 1)) p.flags |= 0x10000;     // (knobs: AGT_LK_RS=0 keeps every corner on the general body; flag bit 16, internal)
     switch (win) {
     // (2 and 8 waves per corner were measured too: 2 loses to 1 on big batches -- 60 vs 42 us at 64 streams --, 8 loses
     // to 4 on small ones -- 19.5 vs 17.8 us)

@@ -1,7 +1,7 @@
 // agt_pyramid.hip -- stand-alone cv::pyrDown launch (body: agt_pyramid_body.h).
 // Replaces the pyramid build inside cv.calcOpticalFlowPyrLK (north-star step).
 // Algorithmic bytes per launch: sw*sh read + dw*dh written (per image).
-#include <cstdlib>
+#include "agt_knobs.h"
 #include "agt_pyramid2_body.h"
 #include "agt_pyramid3_body.h"
 #include "agt_pyramid4_body.h"
@@ -115,10 +115,9 @@ void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintpt
     // tiled, 5.9-8.5 rolling).
     const long images = (long)A0.B * (frames > 0 ? frames : 1);
     int want = images >= 16 ? 1 : 0;
-#ifdef AGT_DEBUG_KNOBS      // AGT_PYR4=0 / 1 forces the choice, AGT_PYR4_OH=n the strip height, AGT_PYR4_REV=0 top-down strips only
-    { static const int on = [] { const char* e = getenv("AGT_PYR4"); return e ? atoi(e) : -1; }(); if (on >= 0) want = on; }
-    { static const int rv = [] { const char* e = getenv("AGT_PYR4_REV"); return e ? atoi(e) : 1; }(); A0.rsv_ = A1.rsv_ = rv ? 0 : 1; }
-#endif
+    // knobs: AGT_PYR4=0 / 1 forces the choice, AGT_PYR4_OH=n the strip height, AGT_PYR4_REV=0 top-down strips only
+    { const long on = AGT_KNOB("AGT_PYR4", -1); if (on >= 0) want = (int)on; }
+    A0.rsv_ = A1.rsv_ = AGT_KNOB("AGT_PYR4_REV", 1) ? 0 : 1;
     if (!ok || !want) return;
     // strip height (level-2 rows, even): ~2 waves on each SIMD where the launch has that many units (the pass shares the chip with
     // the LK kernels of other batches; measured on 64 x 720p inside the pipelined step: oh2 = 4: 53.5 us, 6: 50.3, 8: 48.8-49.1,
@@ -131,15 +130,13 @@ void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintpt
     constexpr int Q = agt_pyr4::L2_PER_TRIP;
     int oh = (int)((A1.dh + strips - 1) / strips + Q - 1) / Q * Q;
     // oh_cap (round 6): 16 for a launch of its own (agt_pyramid_build, agt_pyramid_build_pair: the pass IS the step's long pole there and
-    // every strip pays 9 halo rows of loads and arithmetic); AGT_SPLIT_PYR_OH = 6 (agt_api.hip) for the pyramid role of the split pipeline,
+    // every strip pays 9 halo rows of loads and arithmetic); AGT_SPLIT_PYR_OH = 6 (agt_api_tracker.hip) for the pyramid role of the split pipeline,
     // whose launch of up to 1,024 images runs for hundreds of microseconds BESIDE the per-frame LK launches: 64 streams x 16 frames, us per
     // step over four boxes 16: 36.7-37.6, 10: 36.0-36.2, 8: 35.7-36.3, 6: 35.1-35.9, 4: 35.4-36.3, 2: 40.6 (profiles/r06_experiments.md 17)
     // -- short-lived pyramid waves give their slots back sooner
     if (oh_cap < Q) oh_cap = Q;
     oh = oh < Q ? Q : (oh > oh_cap ? oh_cap : oh);
-#ifdef AGT_DEBUG_KNOBS
-    { static const int f = [] { const char* e = getenv("AGT_PYR4_OH"); return e ? atoi(e) : 0; }(); if (f > 0) oh = (f + Q - 1) / Q * Q; }
-#endif
+    { const long f = AGT_KNOB("AGT_PYR4_OH", 0); if (f > 0) oh = (int)(f + Q - 1) / Q * Q; }
     A0.pad = A1.pad = oh;
     A0.gx = A1.gx = agt_pyr4::roll2_blocks(A0.sw, A1.dh, oh);
     A0.gy = A1.gy = 1;
@@ -197,9 +194,7 @@ void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int 
     const bool ok = ((src_align | (uintptr_t)A.spitch | (uintptr_t)A.sbatch | (uintptr_t)A.sw) & 15) == 0 &&
                     ((dst_align | (uintptr_t)A.dpitch | (uintptr_t)A.dbatch) & 7) == 0 &&
                     A.sw >= 32 && A.sh >= 8 && (long)A.sh * A.spitch < (1L << 31) && (long)A.dh * A.dpitch < (1L << 31);
-#ifdef AGT_DEBUG_KNOBS      // diagnostic library only: AGT_PYR3=0 keeps the tiled kernel, AGT_PYR3_OH=n forces the strip height
-    { static const int on = [] { const char* e = getenv("AGT_PYR3"); return e ? atoi(e) : 1; }(); if (!on) return; }
-#endif
+    if (!AGT_KNOB("AGT_PYR3", 1)) return;       // (knobs: AGT_PYR3=0 keeps the tiled kernel, AGT_PYR3_OH=n forces the strip height)
     if (!ok) return;
     // strip height: enough units (four per wave) to put ~3 waves on each of the chip's SIMDs (1024 on MI355X: 12,288 units) -- a wave keeps 8 KB of reads in
     // flight --, strips no longer than 16 output rows (measured on 64 x 720p, L0 -> L1: 8 rows 17.8 us, 16: 17.0, 24: 21.2,
@@ -212,9 +207,7 @@ void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int 
     if (strips < 1) strips = 1;
     int oh = (int)(A.dh / strips) & ~3;
     oh = oh < 4 ? 4 : (oh > 16 ? 16 : oh);
-#ifdef AGT_DEBUG_KNOBS
-    { static const int f = [] { const char* e = getenv("AGT_PYR3_OH"); return e ? atoi(e) : 0; }(); if (f > 0) oh = f & ~3; }
-#endif
+    { const long f = AGT_KNOB("AGT_PYR3_OH", 0); if (f > 0) oh = (int)f & ~3; }
     A.pad = oh;
     A.gx = agt_pyr3::roll_blocks(A.sw, A.dh, oh);
     A.gy = 1;

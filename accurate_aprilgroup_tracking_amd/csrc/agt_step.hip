@@ -19,6 +19,7 @@
 #endif
 #undef AGT_PNP_STAMPS
 #include "agt_step_args.h"
+#include "agt_knobs.h"
 
 // Role timeline of the fused step (diagnostic build only, -DAGT_STEP_STAMPS; tools/stepstamps.py): s_memtime at entry and
 // exit of the PnP block, of the first LK block and the latest exit of any LK / pyramid block.
@@ -215,7 +216,7 @@ __device__ __forceinline__ void lk_role(const AgtStepParams& S, const AgtStepTab
 // workgroup (decides which XCD a workgroup sits on).  Everything is read from the kernel-argument segment (scalar loads):
 // a reference to the by-value argument would make the compiler copy the whole structure to scratch.
 // ROLL2: the register-rolling two-level pass may be planned (split pipeline: pyr_group_kernel); the fused step kernel is planned with
-// the tiled two-level pass only (agt_api.hip launch_group) and does not carry the rolling body -- it sits on the edge of its registers
+// the tiled two-level pass only (agt_api_tracker.hip launch_group) and does not carry the rolling body -- it sits on the edge of its registers
 template <bool ROLL2>
 __device__ __forceinline__ void pyr_role(KParams KS, KTables KT, int blk, int base, uint8_t* lds)
 {
@@ -545,11 +546,7 @@ hipError_t launch_step_t(hipStream_t stream, const AgtStepParams& S, const AgtSt
         // per frame; profiles/r05_experiments.md).  Zero scratch needs the guess-less initialisation (DLT / homography, one-wave code
         // with four points per lane) in cooperative form, so that no PPL = 4 body sits beside the cooperative one: open.
         // The knobs build can take the per-frame path (AGT_PNP_COOP_GROUP=0).
-        bool group = true;
-#ifdef AGT_DEBUG_KNOBS
-        { static const int f = [] { const char* e = getenv("AGT_PNP_COOP_GROUP"); return e ? atoi(e) : 1; }(); group = f != 0; }
-#endif
-        if (group) return agt_launch_pnp_group_coop(stream, P, T);
+        if (AGT_KNOB("AGT_PNP_COOP_GROUP", 1)) return agt_launch_pnp_group_coop(stream, P, T);
         for (int k = 0; k < P.pnp_nf; k++) {
             if (T.pnp.wait[k]) return hipErrorInvalidValue;          // (split launches are ordered by events: no in-kernel wait to honour)
             AgtPnpParams q = P.pnp;
@@ -564,13 +561,11 @@ hipError_t launch_step_t(hipStream_t stream, const AgtStepParams& S, const AgtSt
     if (!(roles & AGT_STEP_PNP)) { P.n_pnp = 0; P.pnp_nf = 0; }
     if (!(roles & AGT_STEP_LK)) { P.n_lk = 0; P.lk_nf = 0; }
     if (!(roles & AGT_STEP_PYR)) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) { P.n_pyr[s] = 0; P.pyr_nf[s] = 0; } }
-#ifdef AGT_DEBUG_KNOBS      // diagnostic library only: AGT_LK_RS=0 keeps every corner on the general LK body
-    { static const int rs = [] { const char* e = getenv("AGT_LK_RS"); return e ? atoi(e) : 1; }(); if (!rs) P.lk.flags |= 0x10000; }
-#endif
-#ifdef AGT_DEBUG_KNOBS      // diagnostic library only (make dbg): drop roles from the launch to time the others
-    { static const int skip = [] { const char* e = getenv("AGT_STEP_SKIP"); return e ? atoi(e) : 0; }();
-      if (skip & 1) P.n_pnp = 0; if (skip & 2) P.n_lk = 0; if (skip & 4) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.n_pyr[s] = 0; } }
-#endif
+    if (!AGT_KNOB("AGT_LK_RS", 1)) P.lk.flags |= 0x10000;        // (knobs: AGT_LK_RS=0 keeps every corner on the general LK body)
+    {   // knobs: AGT_STEP_SKIP drops roles from the launch to time the others
+        const long skip = AGT_KNOB("AGT_STEP_SKIP", 0);
+        if (skip & 1) P.n_pnp = 0; if (skip & 2) P.n_lk = 0; if (skip & 4) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.n_pyr[s] = 0; }
+    }
     size_t lds = 0;
     int blocks = 0;
     // (the register-rolling forms of the pyramid passes, pyr[s].pad != 0, use no LDS: a launch of them alone must not be held to
@@ -675,9 +670,7 @@ bool agt_step_fits(int n, int B)
     // one LK workgroup per CU, all co-resident (the PnP role's registers leave room for one workgroup per CU): the chip's CU count,
     // 256 on a whole MI355X
     long cap = agt_chip_current().cus;
-#ifdef AGT_DEBUG_KNOBS
-    { static const long f = [] { const char* e = getenv("AGT_STEP_MAX_CORNERS"); return e ? atol(e) : 0L; }(); if (f > 0) cap = f; }
-#endif
+    { const long f = AGT_KNOB("AGT_STEP_MAX_CORNERS", 0); if (f > 0) cap = f; }
     return n <= AGT_WAVE && (long)n * B <= cap;
 }
 

@@ -1,9 +1,10 @@
-"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol that
-include/agt_hip.h declares (no compute calls without a GPU); the product refuses to run
-without its HIP extension."""
+"""CPU: the C-ABI library builds for gfx950, loads, and exports exactly the symbols that
+include/agt_hip.h declares (no compute calls without a GPU) and reads no environment; the
+product refuses to run without its HIP extension."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -34,6 +35,28 @@ def test_build_and_exports():
     # argument errors are reported without touching a device
     assert lib.agt_create(None, None, None) == -1
     assert lib.agt_destroy(None) == 0
+
+
+def dynamic_symbols(name, *flags):
+    # (nm comes with binutils, which the oracle's gcc build needs anyway)
+    lib = os.path.join(ROOT, "accurate_aprilgroup_tracking_amd", name)
+    out = subprocess.check_output(["nm", "-D", *flags, lib], text=True)
+    return {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+
+
+def test_product_exports_exactly_the_abi():
+    # agt_hip.map: the product's dynamic symbol table is the header's function list -- no internal launcher, pool, helper or
+    # __hip_cuid_* leaks into a caller's namespace
+    assert dynamic_symbols("libagt_hip.so", "--defined-only") == set(declared_symbols())
+
+
+def test_product_reads_no_environment():
+    # the debug knobs (agt_knobs.h) exist only in the diagnostic builds; the dbg library proves that the check can fail
+    assert "getenv" not in dynamic_symbols("libagt_hip.so", "--undefined-only")
+    assert "getenv" in dynamic_symbols("libagt_hip_dbg.so", "--undefined-only")
+    dbg = dynamic_symbols("libagt_hip_dbg.so", "--defined-only")
+    assert set(declared_symbols()) <= dbg
+    assert {"agt_debug_lk_stamps", "agt_debug_pnp_stamps", "agt_debug_step_stamps", "agt_debug_dense_stamps"} <= dbg
 
 
 def test_gfx950_code_object_present():

@@ -4,7 +4,7 @@ timeline of corner 0's last frame, slowest corner per frame index and the mean c
 library libagt_hip_exp.so:
     cd accurate_aprilgroup_tracking_amd/csrc && make knobs && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
         -DAGT_DEBUG_KNOBS -DAGT_STEP_LK_STAMPS -c agt_step.hip -o /tmp/step_st.o && hipcc --offload-arch=gfx950 -shared -fPIC -o ../libagt_hip_exp.so \
-        agt_api.knobs.o agt_pyramid.knobs.o agt_lk.knobs.o agt_pnp.knobs.o /tmp/step_st.o agt_preproc.knobs.o agt_dense.knobs.o
+        agt_api*.knobs.o agt_pyramid.knobs.o agt_lk.knobs.o agt_pnp.knobs.o /tmp/step_st.o agt_preproc.knobs.o agt_dense.knobs.o
     AGT_SPLIT_LK_GROUP=2 LKB=64 python tools/lkgroupstamps.py
 Round 4: mean corner-frame 22.2 us at 24 streams, 52 us at 64 streams (a corner alone: 14.3 us with 8 iterations) -- the chip, not the launch
 structure, bounds the 64-stream step."""
