@@ -113,10 +113,6 @@ int ensure_ring(agt_ctx* c, int want)
         ok = ok && hipMalloc((void**)&c->corners[s], B * N * 2 * sizeof(float)) == hipSuccess;
         ok = ok && hipMalloc((void**)&c->status[s], B * N) == hipSuccess;
         ok = ok && hipMemsetAsync(c->status[s], 1, B * N, c->stream) == hipSuccess;
-#ifdef AGT_DEBUG_KNOBS      // (the hybrid LK launch that reads / writes it exists only in the knobs build: ADVICE r5)
-        ok = ok && hipMalloc((void**)&c->lk_iters[s], B * N) == hipSuccess;
-        ok = ok && hipMemsetAsync(c->lk_iters[s], 0, B * N, c->stream) == hipSuccess;
-#endif
         if (!ok) { hip_fail(c, hipGetLastError()); return AGT_ERR_ALLOC; }      // partial entry is freed by agt_destroy
         c->ring = s + 1;
     }
@@ -211,9 +207,7 @@ int ms_pool_acquire(int device, hipStream_t out[3])
     if (hipGetDevice(&cur) != hipSuccess) return -1;
     if (cur != device && hipSetDevice(device) != hipSuccess) return -1;
     int pr_lo = 0, pr_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-    // knobs: AGT_MS_PRIO=low|mid: the library's streams at the lowest / the default priority instead of the highest (A/B)
-    { const char* prio = AGT_KNOB_S("AGT_MS_PRIO"); if (prio[0] == 'l') pr_hi = pr_lo; else if (prio[0] == 'm') pr_hi = 0; }
+    (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);      // (the default or the lowest priority measured the same: profiles/r06_experiments.md)
     bool ok = true;
     for (int k = 0; k < 3 && ok; k++) {
         if (hipStreamCreateWithPriority(&e.s[k], hipStreamNonBlocking, pr_hi) != hipSuccess) {
@@ -319,8 +313,7 @@ int agt_create(const agt_config* cfg, void* hip_stream, agt_ctx** out)
     c->reproject = 0; c->min_points = 8; c->gate_px = 2.0;
     // knobs: fixed iteration counts (AGT_LK_MAX_COUNT=n AGT_LK_EPS=0) separate the per-iteration cost of the LK role from its per-frame cost
     c->lk_max_count = AGT_KNOB("AGT_LK_MAX_COUNT", 30); c->lk_eps = AGT_KNOB_F("AGT_LK_EPS", 0.01); c->lk_min_eig = 1e-4;
-    c->lk_cap_cu = AGT_KNOB("AGT_LK_SPLIT_CU", -1);     // (-1: the library's choice, agt_lk_occupancy_cu; the knob caps every one-wave LK launch)
-    c->lk_slow_thr = AGT_KNOB("AGT_LK_HYBRID", 0);
+    c->lk_cap_cu = -1;                               // (the library's choice: agt_lk_occupancy_cu)
     *out = c;
     return AGT_OK;
 }
@@ -333,7 +326,6 @@ int agt_destroy(agt_ctx* c)
         for (int l = 1; l < AGT_MAX_LEVELS; l++) if (c->lmem[s][l]) (void)hipFree(c->lmem[s][l]);
         if (c->corners[s]) (void)hipFree(c->corners[s]);
         if (c->status[s]) (void)hipFree(c->status[s]);
-        if (c->lk_iters[s]) (void)hipFree(c->lk_iters[s]);
     }
     if (c->ms_pool_slot >= 0) {                      // (also after an ms_init that stopped half-way: the slot and the events it did create)
         for (int i = 0; i < 3; i++) (void)hipStreamSynchronize(c->ms_stream[i]);

@@ -72,6 +72,26 @@ static void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
     }
 }
 
+static int fill_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int next_slot, const float* d_prev, const uint8_t* d_prev_status, float* d_next,
+                   uint8_t* d_status, float* d_err, int n, int crit_type, int crit_max_count, double crit_eps,
+                   int flags, double min_eig_threshold)
+{
+    memset(p, 0, sizeof(*p));
+    fill_levels(c, prev_slot, p->prev);
+    fill_levels(c, next_slot, p->next);
+    p->max_level = c->eff_max_level;
+    p->n = n;
+    // SparsePyrLKOpticalFlowImpl::calc criteria normalisation
+    p->max_count = (crit_type & AGT_TERM_COUNT) ? (crit_max_count < 0 ? 0 : crit_max_count > 100 ? 100 : crit_max_count) : 30;
+    double eps = (crit_type & AGT_TERM_EPS) ? (crit_eps < 0. ? 0. : crit_eps > 10. ? 10. : crit_eps) : 0.01;
+    p->eps2 = eps * eps;
+    p->flags = flags;
+    p->min_eig_threshold = min_eig_threshold;
+    p->prev_pts = d_prev; p->prev_status = d_prev_status; p->next_pts = d_next; p->status = d_status; p->err = d_err;
+    p->lds_min = lk_lds_min(c->lk_cap_cu > 0 ? c->lk_cap_cu : 0);
+    return AGT_OK;
+}
+
 #define AGT_SPLIT_LK_CU 10       // (see agt_lk_occupancy_cu)
 #define AGT_SPLIT_PYR_OH 6       // strip height (level-2 rows) of the split pipeline's pyramid role (agt_pyramid.hip agt_pyr2_plan) ...
 #define AGT_SPLIT_PYR_OH_B0 12   // ... for batches of 12 .. 96 streams: measured (session r6ar, us per step, strips of 6 / 16) 8 streams 20.1 / 19.8,
@@ -79,7 +99,7 @@ static void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
 int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                 const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
                 int n, int B, int crit_type, int crit_max_count, double crit_eps,
-                int flags, double min_eig_threshold, int b0, int waves, bool hybrid)
+                int flags, double min_eig_threshold, int b0, int waves)
 {
     // b0: first stream of the launch (streams b0 .. b0 + B - 1 of the slots and of the point arrays); waves: see agt_launch_lk
     if (!c || !d_prev_pts || !d_next_pts || !d_status) return AGT_ERR_ARG;
@@ -88,39 +108,16 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
     if (n == 0) return AGT_OK;
     if (c->built_B[prev_slot] < b0 + B || c->built_B[next_slot] < b0 + B) return AGT_ERR_STATE;
     AgtLkParams p;
-    memset(&p, 0, sizeof(p));
-    fill_levels(c, prev_slot, p.prev);
-    fill_levels(c, next_slot, p.next);
-    p.max_level = c->eff_max_level;
-    p.n = n;
-    // SparsePyrLKOpticalFlowImpl::calc criteria normalisation
-    p.max_count = (crit_type & AGT_TERM_COUNT) ? (crit_max_count < 0 ? 0 : crit_max_count > 100 ? 100 : crit_max_count) : 30;
-    double eps = (crit_type & AGT_TERM_EPS) ? (crit_eps < 0. ? 0. : crit_eps > 10. ? 10. : crit_eps) : 0.01;
-    p.eps2 = eps * eps;
-    p.flags = flags & 0xffff;            // (the bits above are internal launch flags)
+    fill_lk(c, &p, prev_slot, next_slot, d_prev_pts, d_prev_status, d_next_pts, d_status, d_err, n, crit_type, crit_max_count, crit_eps,
+            flags & 0xffff, min_eig_threshold);          // (the bits above 0xffff are internal launch flags)
     // (waves == 1: a half-batch launch of the split pipeline -- beside the other half's launch and the pyramid launch of the frames ahead)
     p.lds_min = lk_lds_min(c->lk_cap_cu >= 0 ? c->lk_cap_cu : (waves == 1 ? AGT_SPLIT_LK_CU : 0));
     if (c->lk_cap_cu > 0) p.flags |= AGT_LK_FLAG_COTENANT;        // (declared by the caller: agt_lk_occupancy_cu; see agt_lk.hip lk_kernel)
-    if (!AGT_KNOB("AGT_LK_COTENANT_PRIO", 1)) p.flags &= ~AGT_LK_FLAG_COTENANT;     // (knobs: the cap without the issue priority, A/B of the two)
-    p.min_eig_threshold = min_eig_threshold;
-    p.prev_pts = d_prev_pts; p.prev_status = d_prev_status; p.next_pts = d_next_pts; p.status = d_status; p.err = d_err;
     if (b0) {
         for (int l = 0; l <= c->eff_max_level; l++) { p.prev[l].ptr += (long)b0 * p.prev[l].bstride; p.next[l].ptr += (long)b0 * p.next[l].bstride; }
         p.prev_pts += (size_t)b0 * n * 2; p.next_pts += (size_t)b0 * n * 2; p.status += (size_t)b0 * n;
         if (p.prev_status) p.prev_status += (size_t)b0 * n;
         if (p.err) p.err += (size_t)b0 * n;
-    }
-    // HYBRID launch, MEASURED AND NOT SHIPPED (round 5; knobs build: AGT_LK_HYBRID=<iterations>): corners that took >= that
-    // many iterations in the previous frame tracked by four waves, the rest by one, in one launch of two workgroup roles
-    // (agt_lk.hip lk_hybrid_kernel).  Bit-identical records; 64 streams: 40.2 us per step without, 49.5 with the launch form alone
-    // (threshold 200: nobody on four waves), 49.8 / 51.9 / 61.6 / 75.2 at thresholds 14 / 12 / 10 / 8 -- the chip is as much
-    // throughput- as latency-bound there, and a four-wave corner costs 3 x the wave-time of a one-wave corner (profiles/r05_experiments.md).
-    if (hybrid && c->lk_slow_thr > 0 && c->cfg.win == 21 && c->eff_max_level < 3 && !p.err && flags == 0 &&
-        (size_t)(b0 + B) * n <= (size_t)c->cfg.max_streams * c->cfg.max_points) {
-        p.iters_prev = c->lk_iters[prev_slot] + (size_t)b0 * n; p.iters_out = c->lk_iters[next_slot] + (size_t)b0 * n;
-        p.slow_thr = c->lk_slow_thr;
-        hipError_t e = agt_launch_lk_hybrid(stream, p, B);
-        return e == hipSuccess ? AGT_OK : hip_fail(c, e);
     }
     hipError_t e = agt_launch_lk(stream, p, c->cfg.win, B, c->cfg.win == 21 ? waves : 0);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
@@ -155,9 +152,6 @@ int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float*
     if (e == hipSuccess) e = hipMemcpyAsync(c->obj, d_obj, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->tstate, 0, (size_t)B * sizeof(AgtTrackState), c->stream);
     for (int s = 0; s < c->ring && e == hipSuccess; s++) e = hipMemsetAsync(c->status[s], 1, (size_t)B * n, c->stream);
-#ifdef AGT_DEBUG_KNOBS
-    for (int s = 0; s < c->ring && e == hipSuccess; s++) e = hipMemsetAsync(c->lk_iters[s], 0, (size_t)B * n, c->stream);
-#endif
     // arrival counters of the chained launches: a run counts n corners per stream-frame, the next run may have other n / B
     if (e == hipSuccess) e = hipMemsetAsync(c->lk_done, 0, (size_t)AGT_RING_MAX * c->cfg.max_streams * sizeof(unsigned), c->stream);
     memset(c->lk_target, 0, sizeof(c->lk_target));
@@ -216,7 +210,6 @@ static void ring_move(agt_ctx* c, long f, int old_ring, int new_ring)
     for (int l = 1; l < AGT_MAX_LEVELS; l++) { uint8_t* t = c->lmem[a][l]; c->lmem[a][l] = c->lmem[b][l]; c->lmem[b][l] = t; }
     { float* t = c->corners[a]; c->corners[a] = c->corners[b]; c->corners[b] = t; }
     { uint8_t* t = c->status[a]; c->status[a] = c->status[b]; c->status[b] = t; }
-    { uint8_t* t = c->lk_iters[a]; c->lk_iters[a] = c->lk_iters[b]; c->lk_iters[b] = t; }
     c->l0_ptr[b] = c->l0_ptr[a]; c->l0_pitch[b] = c->l0_pitch[a]; c->l0_bstride[b] = c->l0_bstride[a];
     c->built_B[b] = c->built_B[a]; c->built_B[a] = 0;
 }
@@ -261,26 +254,6 @@ static void arm_host_seq(agt_ctx* c, AgtPnpParams* p, long frame)
     if (!c->host_seq_on) return;
     p->host_seq = c->hseq_dev;
     p->host_seq_base = c->hseq_off + (unsigned long long)frame;
-}
-
-static int fill_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int next_slot, const float* d_prev, const uint8_t* d_prev_status, float* d_next,
-                   uint8_t* d_status, float* d_err, int n, int crit_type, int crit_max_count, double crit_eps,
-                   int flags, double min_eig_threshold)
-{
-    memset(p, 0, sizeof(*p));
-    fill_levels(c, prev_slot, p->prev);
-    fill_levels(c, next_slot, p->next);
-    p->max_level = c->eff_max_level;
-    p->n = n;
-    // SparsePyrLKOpticalFlowImpl::calc criteria normalisation
-    p->max_count = (crit_type & AGT_TERM_COUNT) ? (crit_max_count < 0 ? 0 : crit_max_count > 100 ? 100 : crit_max_count) : 30;
-    double eps = (crit_type & AGT_TERM_EPS) ? (crit_eps < 0. ? 0. : crit_eps > 10. ? 10. : crit_eps) : 0.01;
-    p->eps2 = eps * eps;
-    p->flags = flags;
-    p->min_eig_threshold = min_eig_threshold;
-    p->prev_pts = d_prev; p->prev_status = d_prev_status; p->next_pts = d_next; p->status = d_status; p->err = d_err;
-    p->lds_min = lk_lds_min(c->lk_cap_cu > 0 ? c->lk_cap_cu : 0);
-    return AGT_OK;
 }
 
 // Big batches: pyramid, LK and PnP of one frame as separate kernels on three library-owned streams.  The host runs
@@ -338,8 +311,7 @@ static int launch_group(agt_ctx* c, int B, int fmax = 0)
     bool any = false;
     // Chained launch (fused step only): the PnP role follows the LK role of the SAME launch frame by frame through arrival
     // counters (agt_step.hip pnp_role), instead of one launch behind it.
-    bool chain = agt_step_fits(c->trk_n, B);
-    if (!AGT_KNOB("AGT_CHAIN", 1)) chain = false;          // (knobs: AGT_CHAIN=0 keeps the PnP role one launch behind the LK role)
+    const bool chain = agt_step_fits(c->trk_n, B);
     // stage 0 builds levels 1 and 2 in one pass (stage 1 then only keeps the books): always while the batch is small (tiled or
     // register-rolling two-level pass), for big batches where the rolling form applies to every frame of the launch (decided below,
     // in the s = 0 trip) and stage 1 has no backlog from an earlier launch that ran the levels as two passes
@@ -419,10 +391,7 @@ static int launch_group(agt_ctx* c, int B, int fmax = 0)
         for (long k = 0; k <= cnt; k++) {
             const int q = (int)((f0 + k) % M);
             for (int l = 0; l <= L; l++) T.lk.img[k][l] = l == 0 ? c->l0_ptr[q] : c->lmem[q][l];
-            if (k) {
-                T.lk.next[k - 1] = c->corners[q]; T.lk.status[k - 1] = c->status[q];
-                (void)chain;          // (arrival counters are attached below, to the frames the PnP role of THIS launch waits for)
-            }
+            if (k) { T.lk.next[k - 1] = c->corners[q]; T.lk.status[k - 1] = c->status[q]; }     // (arrival counters: attached below)
         }
         S.n_lk = 1; S.lk_B = B;
         c->n_lk += cnt;
@@ -475,11 +444,6 @@ static int launch_group(agt_ctx* c, int B, int fmax = 0)
         if (lk > 0 && S.lk_nf > 1 && ++seen_l == lk) T.lk.img[2][0] = (const uint8_t*)0x7ff8dead00000000ull;
     }
     if (agt_step_fits(c->trk_n, B)) {
-        if (AGT_KNOB("AGT_PYR_SEPARATE", 0)) {       // (knobs: the pyramid role as its own launch, ahead of LK | PnP)
-            hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
-            if (e == hipSuccess && (S.n_lk > 0 || S.n_pnp > 0)) e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_LK | AGT_STEP_PNP);
-            return e == hipSuccess ? AGT_OK : hip_fail(c, e);
-        }
         // a launch with pyramid work only (the first one of a run) goes out as the pyramid kernel proper: eight workgroups per
         // CU instead of the one the fused kernel's register budget leaves (16 frames of 720p: ~7 us instead of ~12)
         const int roles = (S.n_lk > 0 || S.n_pnp > 0) ? AGT_STEP_ALL : AGT_STEP_PYR;
@@ -547,8 +511,7 @@ static int launch_group(agt_ctx* c, int B, int fmax = 0)
         // Up to 1024 corners in flight (the four-waves-per-corner body): the LK role of the WHOLE group as one launch --
         // lk_group_kernel, the frame-chained body of the fused step with its own register budget (153 VGPRs, three workgroups
         // per CU) -- instead of one ~17 us launch + ~5 us gap per frame (round 3: 16 streams 33.9 -> see profiles/r03_stream_sweep.txt).
-        bool lk_group = agt_lk_wide(c->trk_n, B);
-        { const long on = AGT_KNOB("AGT_SPLIT_LK_GROUP", 1); if (!on) lk_group = false; if (on == 2) lk_group = true; }   // (knobs; 2: also for the one-wave kernel)
+        const bool lk_group = agt_lk_wide(c->trk_n, B);
         if (lk_group) {
             e = agt_launch_step(sL, S, T, c->cfg.win, AGT_STEP_LK);
             if (e != hipSuccess) return hip_fail(c, e);
@@ -558,13 +521,11 @@ static int launch_group(agt_ctx* c, int B, int fmax = 0)
         for (int k = 1; k <= S.lk_nf && !lk_group; k++) {
             const int ps = (int)((lk_f0 + k - 1) % M), sl = (int)((lk_f0 + k) % M);
             // (waves = 1: a half is sized by the whole batch's kernel choice, not by its own corner count)
-            // (hybrid: only the one-wave launches of big batches -- a batch that the four-wave kernel takes whole has nothing to gain)
-            const bool hyb = !agt_lk_wide(c->trk_n, B);
             rc = lk_track_on(c, sL, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B1,
-                             AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, 0, two ? 1 : 0, hyb);
+                             AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, 0, two ? 1 : 0);
             if (rc == AGT_OK && two)
                 rc = lk_track_on(c, sL2, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B - B1,
-                                 AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, B1, 1, hyb);
+                                 AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, B1, 1);
             if (rc) return rc;
         }
         e = hipEventRecord(evL[l_slot], sL);
@@ -711,13 +672,6 @@ int agt_estimate_pose(agt_ctx* c, const float* d_img, const uint8_t* d_mask, int
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
-// Dense clips (step_serial below): which of the round-4 forms are on.
-static int dense_defer_on()
-{
-    // knobs: AGT_DENSE_DEFER=0 keeps dense_final_kernel a launch of its own in clips, 1 keeps LK and the pose solve separate launches
-    return (int)AGT_KNOB("AGT_DENSE_DEFER", 2);
-}
-
 // pyrDown.. -> LK -> PnP (+ dense stage) as launches on the context's stream: pose complete in stream order.
 // next_frame != null (clip submission with the dense stage): the caller will hand that frame in next, with the same pitch and
 // stream stride -- its two-level pyramid pass rides in one of this frame's launches (the chained LK | PnP launch, the four-wave PnP
@@ -752,7 +706,7 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
     // (while trackers + solvers are co-resident at the one workgroup per CU the solver's registers leave: more streams keep the LK
     // launch of its own, whose 78 registers put several workgroups on a CU)
     // (the LK role's grid is rounded up to a multiple of 8; the device's CU count, not a literal: ADVICE r4)
-    const bool chain_pnp = lk_role_launch && d_dense_out && c->dn_iters > 0 && !pev && agt_pnp_can_ride(c->trk_n) && dense_defer_on() > 1 &&
+    const bool chain_pnp = lk_role_launch && d_dense_out && c->dn_iters > 0 && !pev && agt_pnp_can_ride(c->trk_n) &&
                            (long)agt_xcd_grid((long)c->trk_n * B, 3) + B <= c->chip.cus;
     const bool ride_pnp = ride && agt_pnp_can_ride(c->trk_n) && !chain_pnp;
     if (ride) {
@@ -822,7 +776,7 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
         // Clip submission: the stage's last step (final update + re-seed, a one-workgroup launch of 5.5 us) is left to the NEXT
         // frame's LK launch, whose workgroups do it as their prologue (agt_step.hip lk_reseed_kernel) -- when that launch will be the
         // four-waves-per-corner LK role launch (same geometry as this frame's) and no stage spans are being recorded
-        const bool defer = next_frame && !pev && c->dn_iters > 0 && c->cfg.win == 21 && agt_lk_wide(c->trk_n, B) && dense_defer_on();
+        const bool defer = next_frame && !pev && c->dn_iters > 0 && c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
         // dense photometric + geometric refinement of the frame's accepted pose, then (reseed) the corner set from it
         e = agt_launch_dense(M, d_frames, (long)pitch, (long)batch_stride, c->cfg.width, c->cfg.height, c->dn_xyz, c->dn_t, c->dn_M,
                              c->obj, c->corners[slot], c->status[slot], c->trk_n, c->cam, c->pose, c->dense_partials, nullptr,
@@ -941,8 +895,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
     // Polled record: the frame's record goes straight to host-mapped memory of the context and the solver stores a sequence word behind
     // it (system scope); this thread polls the word -- no 128-byte copy (a blit KERNEL of ~4.5 us behind the step's launch,
     // rocprofv3), no completion signal, no stream wait.  (With profiling spans armed the call waits for the stream as before.)
-    bool polled = !(c->prof_ev && c->prof_n < c->prof_cap);
-    if (!AGT_KNOB("AGT_HOST_POLL", 1)) polled = false;       // (knobs: AGT_HOST_POLL=0 takes the waited form)
+    const bool polled = !(c->prof_ev && c->prof_n < c->prof_cap);
     double* const d_rec = (polled || !d_state) ? c->hrec_dev : d_state;       // where the pose solver writes the frame's record
     bool registered = false;
     // (the device address of the caller's buffer when it is pinned host memory, asked for on EVERY call: a cached answer would outlive the buffer)
@@ -1008,7 +961,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
 #endif
         return *(volatile int*)c->fault_host ? AGT_ERR_CHAIN : AGT_OK;
     }
-    // (the waited form: profiling spans armed, or the knobs build's AGT_HOST_POLL=0.  HSA_ENABLE_SDMA=0 -- blit-kernel copies -- made
+    // (the waited form: profiling spans armed.  HSA_ENABLE_SDMA=0 -- blit-kernel copies -- made
     // the copy-first form of round 3 slower still: 107 us.)
     if (d_state) {
         e = hipMemcpyAsync(h_state, d_state, AGT_STATE_STRIDE * sizeof(double), hipMemcpyDeviceToHost, c->stream);

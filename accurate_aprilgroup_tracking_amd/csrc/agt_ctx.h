@@ -36,8 +36,6 @@ struct agt_ctx {
     int ring;                                // allocated ring entries: >= (L + 2) * group
     float* corners[AGT_RING_MAX];            // [B][n][2]
     uint8_t* status[AGT_RING_MAX];           // [B][n]
-    uint8_t* lk_iters[AGT_RING_MAX];         // [B][n] iterations every corner took in the frame of the ring entry (hybrid LK launch: a hint, never a result)
-    int lk_slow_thr;                         // agt_lk_hybrid: corners at or above it in the previous frame are tracked by four waves (0 = off)
     double* so_ring[AGT_RING_MAX];           // caller's state_out of the frames in flight
     int pipeline;                            // 1 = software-pipelined fused step (agt_step.hip)
     int group;                               // frames per fused launch (1..AGT_MAX_GROUP)
@@ -109,7 +107,7 @@ int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_
 int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                 const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
                 int n, int B, int crit_type, int crit_max_count, double crit_eps,
-                int flags, double min_eig_threshold, int b0 = 0, int waves = 0, bool hybrid = false);
+                int flags, double min_eig_threshold, int b0 = 0, int waves = 0);
 int lk_lds_min(int per_cu);
 
 // Wait for a sequence word in host-mapped memory that a kernel stores behind its results (system scope) to reach `want`; after 2 s

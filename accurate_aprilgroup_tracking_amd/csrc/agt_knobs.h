@@ -5,9 +5,7 @@
 #include <stdlib.h>
 #define AGT_KNOB(name, def) ([] { static const long v_ = [] { const char* e_ = getenv(name); return e_ ? atol(e_) : (long)(def); }(); return v_; }())
 #define AGT_KNOB_F(name, def) ([] { static const double v_ = [] { const char* e_ = getenv(name); return e_ ? atof(e_) : (double)(def); }(); return v_; }())
-#define AGT_KNOB_S(name) ([] { static const char* const v_ = [] { const char* e_ = getenv(name); return e_ ? e_ : ""; }(); return v_; }())
 #else
 #define AGT_KNOB(name, def) ((long)(def))
 #define AGT_KNOB_F(name, def) ((double)(def))
-#define AGT_KNOB_S(name) ("")
 #endif

@@ -12,20 +12,9 @@ namespace {
 // a tag's four corners (and of neighbouring tags) overlap, and with consecutive corners on eight different XCDs each of those
 // L2s fetched the shared lines from HBM for itself (FETCH_SIZE 2.9x the algorithmic bytes at 64 streams).
 template <int WIN, int NW, int NLEV, int OCC>
-#ifdef AGT_LK_NUM_VGPR       // experiment builds (tools/build_variant.sh): a register ceiling below the occupancy attribute's 128
-#define AGT_LK_VGPR_ATTR __attribute__((amdgpu_num_vgpr(AGT_LK_NUM_VGPR)))
-#else
-#define AGT_LK_VGPR_ATTR
-#endif
-__global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(OCC))) AGT_LK_VGPR_ATTR void lk_kernel(const AgtLkParams P, const int total)
+__global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(OCC))) void lk_kernel(const AgtLkParams P, const int total)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-#ifdef AGT_LK_TOUCH_VGPR     // experiment builds: a clobber of one high register raises the kernel's allocation (e.g. v135: 136 registers = at most
-                             // three of its waves on a SIMD, whatever the CU's LDS would allow)
-#define AGT_STR2(x) #x
-#define AGT_STR(x) AGT_STR2(x)
-    if (NW == 1) asm volatile("" ::: "v" AGT_STR(AGT_LK_TOUCH_VGPR));
-#endif
     // issue priority 1 for every tracker wave of a context that has DECLARED co-tenancy (agt_lk_occupancy_cu with a count: its launches share
     // the device with other contexts' pyramid passes, agt_api_tracker.hip lk_track_on sets the internal flag): cold pairs 44.4-44.6 -> 43.3-43.4 us per
     // step (priority 2: the same).  Not for the split pipeline's own launches: c3 37.3-37.6 -> 37.8-38.1 (profiles/r06_experiments.md 17)
@@ -79,52 +68,6 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
     agt_lk::lk_body<WIN, NW, NLEV>(&P, bX, bY, lds, io, ox, oy, ost);
 }
 
-#ifdef AGT_DEBUG_KNOBS      // measured and not shipped: agt_api_tracker.hip lk_track_on
-// HYBRID launch (round 5, win 21, big batches): 256-thread workgroups in two roles.  Workgroups [0, n4) are the FOUR-WAVE role, one
-// per corner (XCD-aware order): the corner is tracked here if it took >= slow_thr iterations in the previous frame, else the
-// workgroup exits at once.  Workgroups [n4, n4 + nquad) are the ONE-WAVE role: wave w tracks corner 4 q + w (q in XCD-aware order:
-// the four corners of a tag share a workgroup, their overlapping tiles one CU's L1) unless the four-wave role has it.  The slow
-// corners are dispatched first -- they are the launch's critical path.  Register budget of four waves per SIMD (the one-wave
-// body's 128; the four-wave bodies need 67).
-template <int NLEV>
-__global__ __launch_bounds__(AGT_WAVE * 4) __attribute__((amdgpu_waves_per_eu(4))) void lk_hybrid_kernel(const AgtLkParams P, const int total, const int n4,
-                                                                                                           const int nquad, const int per_wave_lds)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int bid = (int)blockIdx.x;
-    const bool four = bid < n4;
-    int cidx;
-    uint8_t* my = lds;
-    if (four) cidx = agt_xcd_order(bid, n4, P.xshift);
-    else {
-        const int wave = agt_uniform((int)threadIdx.x >> 6);          // (scalar: the wave's LDS base stays out of the vector registers)
-        cidx = agt_xcd_order(bid - n4, nquad, P.xshift) * 4 + wave;
-        my = lds + wave * per_wave_lds;
-    }
-    if (cidx >= total) return;
-    const float ppx = P.prev_pts[(long)cidx * 2], ppy = P.prev_pts[(long)cidx * 2 + 1];
-    const int pst = P.prev_status ? P.prev_status[cidx] : 1;
-    const bool rs = agt_uniform((int)(pst != 0 && !(P.flags & 0x10000) && agt_lk::rs_interior(ppx, ppy, P.max_level, P.prev[0].w, P.prev[0].h))) != 0;
-    // four waves only for corners whose windows stay inside the image (the row-segment body); a slow corner at the image border keeps
-    // its one wave and the general body -- three tracker bodies in this kernel instead of four (with four, 14 VGPRs spilled)
-    const bool slow = rs && agt_uniform((int)(P.iters_prev[cidx] >= P.slow_thr)) != 0;
-    if (slow != four) return;
-    const int bY = cidx / P.n, bX = cidx - bY * P.n;          // stream, corner
-    agt_lk::LkFrameIo<NLEV> io;
-    io.grouped = false; io.prev_pts = P.prev_pts; io.next_pts = P.next_pts; io.status = P.status; io.err = P.err;
-    io.have_pos = false; io.px = io.py = 0.f; io.pst = 1;
-    io.iters_out = P.iters_out;
-    float ox, oy; int ost;
-    if (four) {
-        agt_lk::lk_body_rs<4, NLEV>(&P, bX, bY, my, io, ppx, ppy, ox, oy, ost);
-    } else {
-        if (rs) agt_lk::lk_body_rs<1, NLEV>(&P, bX, bY, my, io, ppx, ppy, ox, oy, ost);
-        else agt_lk::lk_body<21, 1, NLEV>(&P, bX, bY, my, io, ox, oy, ost);
-    }
-}
-
-#endif
-
 template <int WIN, int NW>
 hipError_t launch_lk_t(hipStream_t stream, const AgtLkParams& p_in, int B)
 {
@@ -132,8 +75,6 @@ hipError_t launch_lk_t(hipStream_t stream, const AgtLkParams& p_in, int B)
     p.xshift = agt_chip_current().xshift;
     size_t lds = agt_lk::lk_lds_bytes<WIN, NW>(p.max_level + 1);
     if (NW == 1 && (size_t)p.lds_min > lds) lds = (size_t)p.lds_min;          // agt_lk_occupancy_cu: fewer resident LK waves per CU
-    // knobs: AGT_LK_LDS_PAD=bytes: extra LDS per workgroup = fewer LK waves per CU (room for other kernels' waves beside them)
-    { const long pad = AGT_KNOB("AGT_LK_LDS_PAD", 0); if (pad > 0 && NW == 1) lds += (size_t)pad; }
     const long total = (long)p.n * B;
     if (total <= 0 || total > (1L << 30)) return hipErrorInvalidValue;
     const dim3 grid(agt_xcd_grid(total, p.xshift)), block(AGT_WAVE * NW);
@@ -181,30 +122,12 @@ bool agt_lk_window_supported(int win)
 }
 
 // waves per corner: 4 while the launch cannot fill the chip with single-wave corners (latency
-// matters), 1 for large batches (throughput matters)
+// matters), 1 for large batches (throughput matters).  (A hybrid launch -- four waves for the corners that iterated long in the
+// previous frame, one for the rest -- lost: 64 streams 40.2 us per step without, 49.5-75.2 with; round 5, profiles/r05_experiments.md)
 bool agt_lk_wide(int n, int B)
 {
-    return (long)n * B <= AGT_KNOB("AGT_LK_WIDE_MAX", 1024);
+    return (long)n * B <= 1024;
 }
-
-#ifdef AGT_DEBUG_KNOBS
-hipError_t agt_launch_lk_hybrid(hipStream_t stream, const AgtLkParams& p_in, int B)
-{
-    AgtLkParams p = p_in;
-    if (!p.iters_prev || p.slow_thr <= 0 || p.max_level >= 3 || p.err) return hipErrorInvalidValue;
-    p.xshift = agt_chip_current().xshift;
-    const long total = (long)p.n * B;
-    if (total <= 0 || total > (1L << 28)) return hipErrorInvalidValue;
-    const size_t lds1 = agt_lk::lk_lds_bytes<21, 1>(p.max_level + 1), lds4 = agt_lk::lk_lds_bytes<21, 4>(p.max_level + 1);
-    const size_t per = (lds1 + 15) & ~(size_t)15;
-    size_t lds = 4 * per > lds4 ? 4 * per : lds4;
-    const unsigned n4 = agt_xcd_grid(total, p.xshift), nquad = agt_xcd_grid((total + 3) / 4, p.xshift);
-    hipLaunchKernelGGL((lk_hybrid_kernel<3>), dim3(n4 + nquad), dim3(AGT_WAVE * 4), lds, stream, p, (int)total, (int)n4, (int)nquad, (int)per);
-    return hipGetLastError();
-}
-#else
-hipError_t agt_launch_lk_hybrid(hipStream_t, const AgtLkParams&, int) { return hipErrorInvalidValue; }
-#endif
 
 hipError_t agt_launch_lk(hipStream_t stream, const AgtLkParams& p_in, int win, int B, int waves)
 {

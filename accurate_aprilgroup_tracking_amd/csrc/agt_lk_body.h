@@ -293,7 +293,7 @@ struct LkFrameIo {
     bool have_pos; float px, py; int pst;       // pst: the corner's status after the previous frame (with have_pos)
     unsigned* done = nullptr;                   // chained launch (agt_step.hip): arrival counters of this frame, [B]; see lk_publish
     bool bad = false;                           // frame group: the frame's table entries cannot be addresses (agt_step.hip lk_role) -- nothing of the frame is touched
-    uint8_t* iters_out = nullptr;               // stand-alone launches of big batches: iterations the corner took, [B][n] (AgtLkParams::iters_out)
+    uint8_t* rsv_ = nullptr;                    // unused: without it lk_any_kernel is register-allocated differently (kept, as AgtLkParams::rsv_)
 };
 
 // The frame's result for one corner (called by one lane).  In a chained launch the PnP role of the SAME launch picks the
@@ -369,7 +369,7 @@ __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const
     if (NW == 4 && tid < 24) reinterpret_cast<int*>(slots)[tid] = 0;       // block_sum_exact's accumulators (a barrier precedes the first sum)
     const int lane = tid & (AGT_WAVE - 1), wave = tid / AGT_WAVE;
     const long pidx = (long)b * P->n + pt;
-    int nit = 0;                    // iterations over all levels (only kept where io.iters_out is set)
+    [[maybe_unused]] int nit = 0;   // iterations over all levels: read by nothing, but without the count the LK roles of agt_step.hip are register-allocated differently
 
     // window pixels of this thread, as byte / element offsets into the three LDS tiles (computed once;
     // threads without a k-th pixel point at offset 0 and are masked arithmetically, not by branches)
@@ -648,7 +648,6 @@ __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const
     STAMP(3);
     if (level_stop > 0) { ox = outx; oy = outy; ost = st; return; }       // (the finer levels and the result are the caller's)
     if (tid == 0) lk_publish(io, pidx, b, outx, outy, st, errv);
-    if (tid == 0 && io.iters_out) io.iters_out[pidx] = (uint8_t)(nit > 255 ? 255 : nit);
     ox = outx; oy = outy; ost = st;
 }
 

@@ -239,7 +239,7 @@ __device__ __forceinline__ void lk_body_rs(PP P, int pt, int b, uint8_t* lds, co
     long long* slots = reinterpret_cast<long long*>(lds + (P->max_level + 1) * C::LEVEL_LDS + ((C::DW * C::DW + 3) & ~3) * sizeof(int));
     if (NW == 4 && tid < 24) reinterpret_cast<int*>(slots)[tid] = 0;       // block_sum_exact's accumulators (a barrier precedes the first sum)
     int phase = 0;
-    int nit = 0;                    // iterations over all levels (only kept where io.iters_out is set)
+    [[maybe_unused]] int nit = 0;   // iterations over all levels (the AGT_LK_STAMPS corner log reads it)
 
     float outx = cx, outy = cy;
     if (!cont && (P->flags & AGT_LK_USE_INITIAL_FLOW)) {
@@ -642,7 +642,6 @@ __device__ __forceinline__ void lk_body_rs(PP P, int pt, int b, uint8_t* lds, co
 
     STAMP(3);
     if (tid == 0) lk_publish(io, pidx, b, outx, outy, st, errv);
-    if (tid == 0 && io.iters_out) io.iters_out[pidx] = (uint8_t)(nit > 255 ? 255 : nit);
 #ifdef AGT_LK_STAMPS
     if (tid == 0 && !io.grouped && pidx < AGT_LK_CORNER_LOG) agt_lk_corner_log[pidx][2] = (unsigned long long)nit;
 #endif

@@ -24,10 +24,7 @@ __global__ __launch_bounds__(agt_pyr::NT) void pyr_down_kernel(const AgtPyrArgs 
 }
 
 // register-rolling form (agt_pyramid3_body.h): A.gx = workgroups per image, A.pad = output rows per strip; same XCD-aware order
-#ifndef AGT_PYR3_ATTR
-#define AGT_PYR3_ATTR
-#endif
-__global__ __launch_bounds__(agt_pyr::NT) AGT_PYR3_ATTR void pyr_roll_kernel(const AgtPyrArgs A)
+__global__ __launch_bounds__(agt_pyr::NT) void pyr_roll_kernel(const AgtPyrArgs A)
 {
     const int t = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, A.xshift);
     if (t >= A.gx * A.B) return;
@@ -61,9 +58,6 @@ __global__ __launch_bounds__(agt_pyr::NT) void pyr_upload2_kernel(const AgtPyrAr
 // A0.pad = level-2 rows per strip
 __global__ __launch_bounds__(agt_pyr::NT) void pyr_roll2_kernel(const AgtPyrArgs A0, const AgtPyrArgs A1)
 {
-#ifdef AGT_PYR_PRIO         // experiment builds: issue priority of the HBM-bound pass beside the LK kernels' waves
-    __builtin_amdgcn_s_setprio(AGT_PYR_PRIO);
-#endif
     const int t = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, A0.xshift);
     if (t >= A0.gx * A0.B) return;
     const int bz = t / A0.gx;

@@ -10,13 +10,7 @@
 // buffers the serial order would give it (rings of 4 in the context).
 //
 // Bodies: agt_pyramid_body.h, agt_lk_body.h, agt_pnp_body.h (shared with the stand-alone kernels).
-#ifdef AGT_STEP_LK_STAMPS       // experiment builds only: the LK role's in-kernel stamps under their own symbol (tools/_exp)
-#define AGT_LK_STAMPS
-#define agt_lk_stamps agt_lk_stamps_step
-#define agt_debug_lk_stamps agt_debug_lk_stamps_step
-#else
 #undef AGT_LK_STAMPS
-#endif
 #undef AGT_PNP_STAMPS
 #include "agt_step_args.h"
 #include "agt_knobs.h"
@@ -90,32 +84,27 @@ __device__ __forceinline__ bool lk_table_bad(const agt_lk::LkFrameIo<NLEV>& io, 
     return agt_uniform((int)(null_img || !agt_ptr_plausible(acc))) != 0;
 }
 
-#ifndef AGT_LKG_OCC
-#define AGT_LKG_OCC 4            // waves per SIMD the one-wave-per-corner LK group kernel is register-allocated for (4: 128 VGPRs)
-#endif
-
 // (defined in the translation unit compiled without MachineLICM: see pnp_group_coop_kernel below)
 hipError_t agt_launch_pnp_group_coop(hipStream_t stream, const AgtStepParams& P, const AgtStepTables& T);
-hipError_t agt_launch_step_deep(hipStream_t stream, const AgtStepParams& P, const AgtStepTables& T, int nw, int blocks, size_t lds);
+hipError_t agt_launch_step_deep(hipStream_t stream, const AgtStepParams& P, const AgtStepTables& T, int blocks, size_t lds);
 
 namespace {
 
-// ---- LK role: workgroup `blk` of the role, THREADS threads.  NW = 4: the workgroup is one corner; NW = 1: each wave is
-// its own corner.  Consecutive frames of a corner are tracked in-kernel (position carried in registers).
+// ---- LK role: workgroup `blk` of the role is one corner, tracked by its NW = 4 waves (the one-wave-per-corner role lost as a group
+// launch: see agt_launch_step).  Consecutive frames of a corner are tracked in-kernel (position carried in registers).
 // XCD_MAP (the role as its own launch, grid rounded up to a multiple of 8): workgroup g takes block (g mod 8) * (grid / 8) + g / 8 of
 // the role -- every XCD walks a contiguous run of corners, so the overlapping tiles of a tag's corners meet in one L2 (see agt_lk.hip).
-template <int WIN, int NW, int NLEV, int THREADS, bool XCD_MAP = false>
+template <int WIN, int NW, int NLEV, bool XCD_MAP = false>
 __device__ __forceinline__ void lk_role(const AgtStepParams& S, const AgtStepTables& T, KParams KS, KTables KT, int blk, uint8_t* lds)
 {
-    constexpr int CPB = THREADS / (AGT_WAVE * NW);
+    static_assert(NW == 4, "one corner per workgroup of four waves");
     if constexpr (XCD_MAP) blk = agt_xcd_order(blk, (int)gridDim.x, KS->xshift);
-    const int wave = threadIdx.x / AGT_WAVE;
-    const long corner = (long)blk * CPB + (NW == 1 ? wave : 0);
+    const long corner = blk;
     if (corner >= (long)S.lk.n * S.lk_B) return;
     const int b = (int)(corner / S.lk.n), pt = (int)(corner - (long)b * S.lk.n);
     constexpr size_t LKB = sizeof(AgtLkTables);
     const size_t per = lk_role_lds<WIN, NW, NLEV>(S.lk.max_level + 1);
-    uint8_t* my = lds + (NW == 1 ? (size_t)wave * per : 0);
+    uint8_t* my = lds;
     // Frames 2.. of the group take their image / output pointers from a copy of the tables in LDS: a dependent
     // scalar load from the kernel-argument segment in the middle of the chain costs a memory round trip (device
     // memory with this runtime's defaults, host memory across PCIe under HIP_FORCE_DEV_KERNARG=0: profiles/
@@ -124,7 +113,7 @@ __device__ __forceinline__ void lk_role(const AgtStepParams& S, const AgtStepTab
     AgtLkTables* tab = reinterpret_cast<AgtLkTables*>(my + per - LKB);
     {
         static_assert(sizeof(AgtLkTables) % 8 == 0, "table copy: 8-byte words");
-        const int tid = NW == 1 ? (int)(threadIdx.x & (AGT_WAVE - 1)) : (int)threadIdx.x;
+        const int tid = (int)threadIdx.x;
         // (vector loads through a generic view of the kernel-argument segment: one word per lane, all in flight at once; a character
         // copy -- see agt_copy_words_to_lds -- so the typed reads of tab->... below depend on it for every alias analysis)
         if (S.lk_nf > 1) agt_copy_words_to_lds(tab, (const void*)(const __attribute__((address_space(4))) void*)&KT->lk, (int)(LKB / 8), tid, AGT_WAVE * NW);
@@ -173,42 +162,12 @@ __device__ __forceinline__ void lk_role(const AgtStepParams& S, const AgtStepTab
         }
         return io;
     };
-    int k = 0;
-    if constexpr (WIN == 21 && NW == 1) {
-        // one wave per corner: the row-segment body while the window stays inside the image and the corner is alive (with four
-        // waves per corner the general body is kept: inside this kernel the row-segment form measured 16.7 us per frame against
-        // 15.9, although it wins by 2.5 us as the stand-alone lk_kernel).  Two loops in sequence, NOT one loop with both bodies:
-        // side by side in one loop body the two trackers are register-allocated as one (29 VGPR spills at a 168-register budget,
-        // 79 at 128; each alone fits 137).  A corner that needs the general body once (window at the image border, status lost)
-        // finishes the group's remaining frames in the second loop -- the general body tracks every case, only slower.
-        const long pidx = (long)b * S.lk.n + pt;
-        for (; k < S.lk_nf; k++) {
-            const float ppx = k ? px : S.lk.prev_pts[pidx * 2], ppy = k ? py : S.lk.prev_pts[pidx * 2 + 1];
-            const int alive = k ? pst : (S.lk.prev_status ? S.lk.prev_status[pidx] : 1);
-            if (!agt_uniform((int)(alive != 0 && !(S.lk.flags & 0x10000) && agt_lk::rs_interior(ppx, ppy, S.lk.max_level, S.lk.prev[0].w, S.lk.prev[0].h))))
-                break;
-#ifdef AGT_STEP_LK_STAMPS
-            const unsigned long long tq0 = __builtin_amdgcn_s_memtime();
-#endif
-            const agt_lk::LkFrameIo<NLEV> io = frame_io(k);
-            if (io.bad) return;
-            agt_lk::lk_body_rs<NW, NLEV>(&KS->lk, pt, b, my, io, ppx, ppy, px, py, pst);
-#ifdef AGT_STEP_LK_STAMPS
-            if ((threadIdx.x & 63) == 0) {       // experiment: slowest / summed per-frame time over all corners, frames in the row-segment loop
-                const unsigned long long dt = __builtin_amdgcn_s_memtime() - tq0;
-                atomicMax(&agt_lk_stamps[40 + (k < 15 ? k : 15)], dt);
-                atomicAdd(&agt_lk_stamps[56], dt); atomicAdd(&agt_lk_stamps[57], 1ull);
-            }
-#endif
-        }
-    }
-    for (; k < S.lk_nf; k++) {
+    // (with four waves per corner the general body, not the row-segment one, tracks what the frame-chained body does not take: inside
+    // this kernel the row-segment form measured 16.7 us per frame against 15.9, although it wins by 2.5 us as the stand-alone lk_kernel)
+    for (int k = 0; k < S.lk_nf; k++) {
         const agt_lk::LkFrameIo<NLEV> io = frame_io(k);
         if (io.bad) return;
         agt_lk::lk_body<WIN, NW, NLEV>(&KS->lk, pt, b, my, io, px, py, pst);
-#ifdef AGT_STEP_LK_STAMPS
-        if ((threadIdx.x & 63) == 0) atomicAdd(&agt_lk_stamps[58], 1ull);
-#endif
     }
 }
 
@@ -451,7 +410,7 @@ __global__ __launch_bounds__(STEP_THREADS) __attribute__((amdgpu_waves_per_eu(OC
     SSTAMP_MIN(6);                                   // earliest entry of any block
     if (blk < S.n_lk) {
         if (blk == 0) SSTAMP_SET(2);
-        lk_role<WIN, NW, NLEV, STEP_THREADS>(S, T, KS, KT, blk, lds);
+        lk_role<WIN, NW, NLEV>(S, T, KS, KT, blk, lds);
         if (blk == 0) SSTAMP_SET(3);
         SSTAMP_MAX(4);
         return;
@@ -486,16 +445,11 @@ template <int WIN, int NW, int NLEV, int OCC>
 __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(OCC))) void lk_group_kernel(const AgtStepParams S, const AgtStepTables T)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    lk_role<WIN, NW, NLEV, AGT_WAVE * NW, true>(S, T, kernarg_params(), kernarg_tables(), blockIdx.x, lds);
+    lk_role<WIN, NW, NLEV, true>(S, T, kernarg_params(), kernarg_tables(), blockIdx.x, lds);
 }
 
 #ifndef AGT_STEP_NOLICM_TU
-#ifdef AGT_PYRG_NUM_VGPR     // experiment builds: register ceiling of the split pipeline's pyramid launch
-#define AGT_PYRG_VGPR_ATTR __attribute__((amdgpu_num_vgpr(AGT_PYRG_NUM_VGPR)))
-#else
-#define AGT_PYRG_VGPR_ATTR
-#endif
-__global__ __launch_bounds__(agt_pyr::NT) AGT_PYRG_VGPR_ATTR void pyr_group_kernel(const AgtStepParams S, const AgtStepTables T)
+__global__ __launch_bounds__(agt_pyr::NT) void pyr_group_kernel(const AgtStepParams S, const AgtStepTables T)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     pyr_role<true>(kernarg_params(), kernarg_tables(), blockIdx.x, 0, lds);
@@ -524,120 +478,6 @@ __global__ __launch_bounds__(AGT_WAVE * PNP_COOP) void pnp_group_coop_kernel(con
 }
 #endif
 
-#ifndef AGT_STEP_NOLICM_TU
-// roles: AGT_STEP_ALL = one fused launch; AGT_STEP_PYR / AGT_STEP_LK = that role alone, from the kernel compiled without
-// the FP64 PnP role (the one-wave-per-corner LK keeps its four waves per SIMD; each launch sizes its own LDS);
-// AGT_STEP_PNP = the PnP role alone
-template <int WIN, int NW>
-hipError_t launch_step_t(hipStream_t stream, const AgtStepParams& S, const AgtStepTables& T, int roles)
-{
-    constexpr int CPB = STEP_THREADS / (AGT_WAVE * NW);
-    AgtStepParams P = S;
-    P.xshift = agt_chip_current().xshift; P.rsv_ = 0; P.lk.xshift = P.xshift;
-    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.pyr[s].xshift = P.xshift;
-    if (roles == AGT_STEP_PNP) {
-        if (P.n_pnp <= 0) return hipSuccess;
-        if (P.pnp.n <= AGT_WAVE) { hipLaunchKernelGGL((pnp_group_kernel<1>), dim3(P.n_pnp), dim3(AGT_WAVE), 0, stream, P, T); return hipGetLastError(); }
-        // 64 < n <= 256 (the four-wave solver): the group's frames inside ONE launch (pnp_group_coop_kernel).  With the frame loop around
-        // both solver bodies the function needs more than its 512 registers: 154 VGPR spills / 1,600 B of scratch with the LDS-resident
-        // state of rounds 3-4, 129 / 376 B with the state in global memory (round 5, shipped).  The spill-free alternative -- the
-        // stand-alone pnp_coop_kernel once per frame (419 registers, no scratch) -- was measured and loses: 240 corners, 16 frames per
-        // group, us per step group / per frame: 2 streams 28.5 / 36.9, 4: 37.6 / 44.4, 8: 45.4 / 52.5 (the host enqueues one more launch
-        // per frame; profiles/r05_experiments.md).  Zero scratch needs the guess-less initialisation (DLT / homography, one-wave code
-        // with four points per lane) in cooperative form, so that no PPL = 4 body sits beside the cooperative one: open.
-        // The knobs build can take the per-frame path (AGT_PNP_COOP_GROUP=0).
-        if (AGT_KNOB("AGT_PNP_COOP_GROUP", 1)) return agt_launch_pnp_group_coop(stream, P, T);
-        for (int k = 0; k < P.pnp_nf; k++) {
-            if (T.pnp.wait[k]) return hipErrorInvalidValue;          // (split launches are ordered by events: no in-kernel wait to honour)
-            AgtPnpParams q = P.pnp;
-            q.img = T.pnp.img[k]; q.mask = T.pnp.mask[k]; q.state_out = T.pnp.so[k];
-            q.host_seq = (k == P.pnp_nf - 1) ? P.pnp.host_seq : nullptr;
-            q.host_seq_base = P.pnp.host_seq_base + (unsigned long long)k;
-            const hipError_t e = agt_launch_pnp(stream, q, P.n_pnp);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    if (!(roles & AGT_STEP_PNP)) { P.n_pnp = 0; P.pnp_nf = 0; }
-    if (!(roles & AGT_STEP_LK)) { P.n_lk = 0; P.lk_nf = 0; }
-    if (!(roles & AGT_STEP_PYR)) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) { P.n_pyr[s] = 0; P.pyr_nf[s] = 0; } }
-    if (!AGT_KNOB("AGT_LK_RS", 1)) P.lk.flags |= 0x10000;        // (knobs: AGT_LK_RS=0 keeps every corner on the general LK body)
-    {   // knobs: AGT_STEP_SKIP drops roles from the launch to time the others
-        const long skip = AGT_KNOB("AGT_STEP_SKIP", 0);
-        if (skip & 1) P.n_pnp = 0; if (skip & 2) P.n_lk = 0; if (skip & 4) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.n_pyr[s] = 0; }
-    }
-    size_t lds = 0;
-    int blocks = 0;
-    // (the register-rolling forms of the pyramid passes, pyr[s].pad != 0, use no LDS: a launch of them alone must not be held to
-    // the tiled kernels' occupancy)
-    size_t pyr_lds = 0;
-    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++)
-        if (P.n_pyr[s] > 0) {
-            blocks += P.n_pyr[s];
-            const size_t need = P.pyr[s].pad ? 0 : ((P.pyr_fused && s == 0) ? (size_t)agt_pyr2::PYR2_LDS_BYTES : (size_t)agt_pyr::PYR_LDS_BYTES);
-            pyr_lds = pyr_lds > need ? pyr_lds : need;
-        }
-    lds = pyr_lds;
-    if (P.n_lk > 0) {
-        const long corners = (long)P.lk.n * P.lk_B;
-        P.n_lk = (int)((corners + CPB - 1) / CPB);
-        blocks += P.n_lk;
-        const size_t per = P.lk.max_level < 3 ? lk_role_lds<WIN, NW, 3>(P.lk.max_level + 1) : lk_role_lds<WIN, NW, AGT_MAX_LEVELS>(P.lk.max_level + 1);
-        const size_t need = per * (NW == 1 ? CPB : 1);
-        lds = lds > need ? lds : need;
-    }
-    if (P.n_pnp > 0) { blocks += P.n_pnp; lds = lds > sizeof(agt_pnp::PnpShared) ? lds : sizeof(agt_pnp::PnpShared); }
-    if (blocks == 0) return hipSuccess;
-    const bool small = P.lk.max_level < 3;
-    if (roles == AGT_STEP_PYR) {
-        hipLaunchKernelGGL(pyr_group_kernel, dim3(blocks), dim3(agt_pyr::NT), pyr_lds, stream, P, T);
-        return hipGetLastError();
-    }
-    if (roles == AGT_STEP_LK) {
-#ifndef AGT_DEBUG_KNOBS
-        // The one-wave-per-corner LK role as a group launch (in-kernel frame loop) is a measured dead end -- round 4, spill-free at
-        // last (two frame loops in sequence instead of one with both tracker bodies): 64 streams 54.2 us per step against 42.1 with
-        // per-frame launches in two half-batch chains, 24 streams 36.9 against 30.6; the corners that need 30 iterations need them
-        // in EVERY frame, so a corner's own chain over the group is as long as the chain of per-frame maxima.  Sub-groups of 2 / 4 / 8
-        // frames per launch (to save the ~4 us launch boundary and ~2 us kernel start per frame) lose as well: 64 streams 55.3 / 52.4 /
-        // 51.5 us, 24 streams 39.9 / 37.5 / 35.9 against 30.7 -- inside the frame loop a frame costs the one-wave kernel ~10 us more
-        // than as a launch of its own.  Only the knobs build (AGT_SPLIT_LK_GROUP=2) still carries the instantiation.
-        if constexpr (NW == 1) return hipErrorInvalidValue;
-        else {
-#endif
-        constexpr int OCCL = (WIN == 21 && NW == 1) ? AGT_LKG_OCC : 1;
-        const long corners = (long)P.lk.n * P.lk_B;
-        size_t per = small ? lk_role_lds<WIN, NW, 3>(P.lk.max_level + 1) : lk_role_lds<WIN, NW, AGT_MAX_LEVELS>(P.lk.max_level + 1);
-        if (NW == 1 && (size_t)P.lk.lds_min > per) per = (size_t)P.lk.lds_min;      // agt_lk_occupancy_cu also caps the one-wave group launch (knobs build only: ADVICE r5)
-        const unsigned grid8 = agt_xcd_grid(corners, P.xshift);           // (XCD-aware corner order: lk_role; blocks past the last corner exit)
-        if (small) hipLaunchKernelGGL((lk_group_kernel<WIN, NW, 3, OCCL>), dim3(grid8), dim3(AGT_WAVE * NW), per, stream, P, T);
-        else hipLaunchKernelGGL((lk_group_kernel<WIN, NW, AGT_MAX_LEVELS, OCCL>), dim3(grid8), dim3(AGT_WAVE * NW), per, stream, P, T);
-        return hipGetLastError();
-#ifndef AGT_DEBUG_KNOBS
-        }
-#endif
-    }
-    if (!(roles & (AGT_STEP_LK | AGT_STEP_PNP))) return hipErrorInvalidValue;       // (LK | PnP without the pyramid role: diagnostics)
-    // The FP64 PnP role gets the whole register file (256 VGPR + AGPR spill space): one workgroup per CU, which is why the fused
-    // launch is only used while <= 256 corners are in flight (agt_step_fits).  Round 2 also shipped an OCC = 2 build for 257-2048
-    // corners (registers capped at 256: ~500 VGPR spills, 1 KB of scratch in the PnP role); round 3's split mode with the LK role
-    // as one group launch beats it at every stream count (profiles/r03_stream_sweep.txt), so it is gone.
-#ifndef AGT_DEBUG_KNOBS
-    // (the fused launch needs <= 256 corners in flight -- agt_step_fits -- and <= 1024 corners are always tracked by four waves each
-    // -- agt_lk_wide --, so step_kernel<21, 1, *> was unreachable object code: 476 VGPRs, scratch.  Only the knobs build, whose
-    // AGT_LK_WIDE_MAX can force the one-wave body on small batches, still instantiates it: VERDICT r4 #4)
-    if constexpr (NW == 1) return hipErrorInvalidValue;
-    else {
-#endif
-    if (small) hipLaunchKernelGGL((step_kernel<WIN, NW, 3, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T);
-    else return agt_launch_step_deep(stream, P, T, NW, blocks, lds);
-    return hipGetLastError();
-#ifndef AGT_DEBUG_KNOBS
-    }
-#endif
-}
-#endif      // !AGT_STEP_NOLICM_TU
-
 }  // namespace
 
 #ifdef AGT_STEP_NOLICM_TU
@@ -648,12 +488,8 @@ hipError_t agt_launch_pnp_group_coop(hipStream_t stream, const AgtStepParams& P,
 }
 
 // the fused step of pyramids with more than three levels (cv2's default maxLevel = 3 is four)
-hipError_t agt_launch_step_deep(hipStream_t stream, const AgtStepParams& P, const AgtStepTables& T, int nw, int blocks, size_t lds)
+hipError_t agt_launch_step_deep(hipStream_t stream, const AgtStepParams& P, const AgtStepTables& T, int blocks, size_t lds)
 {
-#ifdef AGT_DEBUG_KNOBS      // (the one-wave-per-corner fused kernel: knobs build only, see launch_step_t)
-    if (nw == 1) { hipLaunchKernelGGL((step_kernel<21, 1, AGT_MAX_LEVELS, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T); return hipGetLastError(); }
-#endif
-    if (nw != 4) return hipErrorInvalidValue;
     hipLaunchKernelGGL((step_kernel<21, 4, AGT_MAX_LEVELS, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T);
     return hipGetLastError();
 }
@@ -669,15 +505,76 @@ bool agt_step_fits(int n, int B)
 {
     // one LK workgroup per CU, all co-resident (the PnP role's registers leave room for one workgroup per CU): the chip's CU count,
     // 256 on a whole MI355X
-    long cap = agt_chip_current().cus;
-    { const long f = AGT_KNOB("AGT_STEP_MAX_CORNERS", 0); if (f > 0) cap = f; }
-    return n <= AGT_WAVE && (long)n * B <= cap;
+    return n <= AGT_WAVE && (long)n * B <= agt_chip_current().cus;
 }
 
+// roles: AGT_STEP_ALL = one fused launch; AGT_STEP_PYR / AGT_STEP_LK = that role alone, from the kernel compiled without
+// the FP64 PnP role (each launch sizes its own LDS); AGT_STEP_PNP = the PnP role alone.
+// The LK role tracks every corner with four waves.  Its one-wave forms lost: as a group launch of the split pipeline 54.2 against
+// 42.1 us per step at 64 streams (per-frame launches instead, agt_api_tracker.hip launch_group; round 4, profiles/r04_experiments.md),
+// and the fused launch never holds more than the 1024 corners up to which agt_lk_wide picks four waves.
 hipError_t agt_launch_step(hipStream_t stream, const AgtStepParams& S, const AgtStepTables& T, int win, int roles)
 {
     if (win != 21) return hipErrorInvalidValue;
-    const bool wide = S.n_lk > 0 ? agt_lk_wide(S.lk.n, S.lk_B) : true;
-    return wide ? launch_step_t<21, 4>(stream, S, T, roles) : launch_step_t<21, 1>(stream, S, T, roles);
+    AgtStepParams P = S;
+    P.xshift = agt_chip_current().xshift; P.rsv_ = 0; P.lk.xshift = P.xshift;
+    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.pyr[s].xshift = P.xshift;
+    if (roles == AGT_STEP_PNP) {
+        if (P.n_pnp <= 0) return hipSuccess;
+        if (P.pnp.n <= AGT_WAVE) { hipLaunchKernelGGL((pnp_group_kernel<1>), dim3(P.n_pnp), dim3(AGT_WAVE), 0, stream, P, T); return hipGetLastError(); }
+        // 64 < n <= 256 (the four-wave solver): the group's frames inside ONE launch (pnp_group_coop_kernel), although the frame loop
+        // around both solver bodies spills (129 VGPRs / 376 B of scratch): the stand-alone pnp_coop_kernel once per frame (no scratch)
+        // lost, 240 corners, us per step group: 2 streams 28.5 against 36.9, 8: 45.4 against 52.5 (round 5, profiles/r05_experiments.md).
+        // Zero scratch needs the guess-less initialisation in cooperative form: open.
+        return agt_launch_pnp_group_coop(stream, P, T);
+    }
+    if (!(roles & AGT_STEP_PNP)) { P.n_pnp = 0; P.pnp_nf = 0; }
+    if (!(roles & AGT_STEP_LK)) { P.n_lk = 0; P.lk_nf = 0; }
+    if (!(roles & AGT_STEP_PYR)) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) { P.n_pyr[s] = 0; P.pyr_nf[s] = 0; } }
+    if (!AGT_KNOB("AGT_LK_RS", 1)) P.lk.flags |= 0x10000;        // (knobs: AGT_LK_RS=0 keeps every corner on the general LK body)
+    {   // knobs: AGT_STEP_SKIP drops roles from the launch to time the others
+        const long skip = AGT_KNOB("AGT_STEP_SKIP", 0);
+        if (skip & 1) P.n_pnp = 0; if (skip & 2) P.n_lk = 0; if (skip & 4) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.n_pyr[s] = 0; }
+    }
+    const bool small = P.lk.max_level < 3;
+    size_t lds = 0;
+    int blocks = 0;
+    // (the register-rolling forms of the pyramid passes, pyr[s].pad != 0, use no LDS: a launch of them alone must not be held to
+    // the tiled kernels' occupancy)
+    size_t pyr_lds = 0;
+    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++)
+        if (P.n_pyr[s] > 0) {
+            blocks += P.n_pyr[s];
+            const size_t need = P.pyr[s].pad ? 0 : ((P.pyr_fused && s == 0) ? (size_t)agt_pyr2::PYR2_LDS_BYTES : (size_t)agt_pyr::PYR_LDS_BYTES);
+            pyr_lds = pyr_lds > need ? pyr_lds : need;
+        }
+    lds = pyr_lds;
+    // the LK role: one workgroup per corner
+    const size_t lk_lds = small ? lk_role_lds<21, 4, 3>(P.lk.max_level + 1) : lk_role_lds<21, 4, AGT_MAX_LEVELS>(P.lk.max_level + 1);
+    if (P.n_lk > 0) {
+        P.n_lk = (int)((long)P.lk.n * P.lk_B);
+        blocks += P.n_lk;
+        lds = lds > lk_lds ? lds : lk_lds;
+    }
+    if (P.n_pnp > 0) { blocks += P.n_pnp; lds = lds > sizeof(agt_pnp::PnpShared) ? lds : sizeof(agt_pnp::PnpShared); }
+    if (blocks == 0) return hipSuccess;
+    if (roles == AGT_STEP_PYR) {
+        hipLaunchKernelGGL(pyr_group_kernel, dim3(blocks), dim3(agt_pyr::NT), pyr_lds, stream, P, T);
+        return hipGetLastError();
+    }
+    if (roles == AGT_STEP_LK) {
+        const unsigned grid8 = agt_xcd_grid(P.n_lk, P.xshift);          // (XCD-aware corner order: lk_role; blocks past the last corner exit)
+        if (small) hipLaunchKernelGGL((lk_group_kernel<21, 4, 3, 1>), dim3(grid8), dim3(AGT_WAVE * 4), lk_lds, stream, P, T);
+        else hipLaunchKernelGGL((lk_group_kernel<21, 4, AGT_MAX_LEVELS, 1>), dim3(grid8), dim3(AGT_WAVE * 4), lk_lds, stream, P, T);
+        return hipGetLastError();
+    }
+    if (!(roles & (AGT_STEP_LK | AGT_STEP_PNP))) return hipErrorInvalidValue;       // (LK | PnP without the pyramid role: diagnostics)
+    // The FP64 PnP role gets the whole register file (256 VGPR + AGPR spill space): one workgroup per CU, which is why the fused
+    // launch is only used while <= 256 corners are in flight (agt_step_fits).  Round 2 also shipped an OCC = 2 build for 257-2048
+    // corners (registers capped at 256: ~500 VGPR spills, 1 KB of scratch in the PnP role); round 3's split mode with the LK role
+    // as one group launch beats it at every stream count (profiles/r03_stream_sweep.txt), so it is gone.
+    if (small) hipLaunchKernelGGL((step_kernel<21, 4, 3, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T);
+    else return agt_launch_step_deep(stream, P, T, blocks, lds);
+    return hipGetLastError();
 }
 #endif      // !AGT_STEP_NOLICM_TU

@@ -3,5 +3,4 @@
 // Reason, numbers and the rest of the file: agt_step.hip, at pnp_group_coop_kernel.
 #define AGT_STEP_NOLICM_TU
 #undef AGT_STEP_STAMPS          // (the diagnostic build's role stamps and their accessors live in agt_step.hip's own object)
-#undef AGT_STEP_LK_STAMPS
 #include "agt_step.hip"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One 1280x720 stream through the fused chained step on the DIAGNOSTIC library (make -C csrc dbg), so that its
-environment knobs apply: AGT_LK_WIDE_MAX=0 (one wave per corner in the LK role), AGT_LK_RS=0 (general LK body only),
-AGT_CHAIN=0 (PnP one launch behind LK).  Prints frames/s of a 400-frame clip at the given depth (default 16)."""
+environment knobs apply: AGT_LK_RS=0 (general LK body only), AGT_REPS (below).  Prints frames/s of a 400-frame clip at the
+given depth (default 16)."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

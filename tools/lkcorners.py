@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-corner residence of ONE one-wave-per-corner LK launch on a 64 x 1280x720 batch (BASELINE configs[2] geometry), from the
 diagnostic library's per-corner log (entry / exit s_memtime of every corner): when do waves start, how long do they live, who is last.
-LKB streams (default 64); AGT_LK_WIDE_MAX=0 is not needed (3,072 corners take the one-wave kernel)."""
+LKB streams (default 64: 3,072 corners, which the library gives the one-wave kernel)."""
 import ctypes as C, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
