@@ -197,6 +197,18 @@ def test_c5_stream_matches_oracle_chain(oracle, reseed, cam, tmp_path):
     reference-validated PoseDetector mirror on the oracle backend and oracle.dense_refine, frame by frame.
     cam = "tilt" (round 5): the same chain through the 14-coefficient model with a (small) sensor tilt -- solver, dense stage and the
     re-seed's projection all go through the tilted projection; the frames are the renderer's (no tilt), so only HIP = oracle is asserted."""
+    _c5_chain(oracle, reseed, cam, tmp_path, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("reseed", [False, True], ids=["L3", "L3_reseed"])
+def test_c5_stream_matches_oracle_chain_at_depth_3(oracle, reseed, tmp_path):
+    """the same chain with pyramids of depth 3 on both sides: LK(240) and the cooperative pose solve go out as ONE launch of the
+    six-level kernel (agt_step_dense.hip lk_pnp_coop_kernel<6>)"""
+    _c5_chain(oracle, reseed, "pinhole", tmp_path, 3)
+
+
+def _c5_chain(oracle, reseed, cam, tmp_path, max_level):
     dist = TILT14 if cam == "tilt" else None
     import json, logging
     import torch
@@ -213,7 +225,8 @@ def test_c5_stream_matches_oracle_chain(oracle, reseed, cam, tmp_path):
     tol = 1e-6 if reseed else 1e-8        # re-seeded corners are rounded to float32: an ulp flip costs ~1e-7 downstream
     F = len(s)
     frames = torch.from_numpy(s.frames()).cuda()
-    trk = StreamTracker(s.width, s.height, s.obj, s.K, dist, n_streams=1)
+    trk = StreamTracker(s.width, s.height, s.obj, s.K, dist, n_streams=1, max_level=max_level)
+    assert trk.ctx.eff_max_level == max_level
     mxg, Tg = torch.from_numpy(mx).cuda(), torch.from_numpy(T).cuda()
     trk.dense_model(mxg, Tg, iters=iters, photo_weight=pw, reseed=reseed)
     trk.reset(frames[0:1].contiguous(), torch.from_numpy(s.corners(0)[None]).cuda().contiguous())
@@ -231,10 +244,15 @@ def test_c5_stream_matches_oracle_chain(oracle, reseed, cam, tmp_path):
     log = logging.getLogger("c5"); log.setLevel(logging.CRITICAL)
     det = Det(log, s.K, dist, True, cv=cv2_shim.make_cv2())
     obj32 = s.obj.astype(np.float32)
-    pts = s.corners(0); alive = np.ones(n, bool); pyr = oracle.Pyramid(s.frame(0))
+    pts = s.corners(0); alive = np.ones(n, bool); pyr = oracle.Pyramid(s.frame(0), 21, max_level)
+    assert pyr.levels == max_level
     for k in range(1, F):
-        npyr = oracle.Pyramid(s.frame(k))
-        nx, status, _ = oracle.calcOpticalFlowPyrLK(pyr, npyr, pts, maxLevel=2)
+        npyr = oracle.Pyramid(s.frame(k), 21, max_level)
+        nx, status, _ = oracle.calcOpticalFlowPyrLK(pyr, npyr, pts, maxLevel=max_level)
+        if k == 1 and max_level != 2:
+            # the scene tells the depth from depth 2: some corner lands elsewhere
+            n2, _, _ = oracle.calcOpticalFlowPyrLK(pyr, npyr, pts, maxLevel=2)
+            assert (n2.view(np.uint32) != nx.view(np.uint32)).any()
         nx = nx.reshape(-1, 2); status = status.ravel().astype(bool)
         nx[~alive] = pts[~alive]; alive &= status
         il = [nx[i].reshape(1, 1, 2) for i in range(n) if alive[i]]
@@ -270,6 +288,19 @@ def test_dense_clip_submission_equals_single_calls(oracle, n_tags, reseed):
     launch of frame k: the four-wave PnP launch (240 corners) or the second dense launch (48 corners) -- leaves bitwise the
     records of agt_track_frame_dense called frame by frame; clips cut at arbitrary places, a clip of one frame, a single call
     between two clips."""
+    _dense_clip_equals_single_calls(n_tags, reseed, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_tags,reseed", [(60, True), (12, True), (60, False), (12, False)], ids=["L3-60-reseed", "L3-12-reseed", "L3-60", "L3-12"])
+def test_dense_clip_submission_equals_single_calls_at_depth_3(oracle, n_tags, reseed):
+    """the same at pyramid depth 3, where no pyramid pass rides (that form is built for depth 2): the clip form differs from the single
+    calls only by the deferred last dense step -- lk_pnp_coop_kernel<6> takes it as its prologue with 240 corners, lk_reseed_kernel<6>
+    with 48"""
+    _dense_clip_equals_single_calls(n_tags, reseed, 3)
+
+
+def _dense_clip_equals_single_calls(n_tags, reseed, max_level):
     import torch
     from accurate_aprilgroup_tracking_amd import hiplib as H
     from accurate_aprilgroup_tracking_amd.tracker import StreamTracker
@@ -282,7 +313,8 @@ def test_dense_clip_submission_equals_single_calls(oracle, n_tags, reseed):
     K = len(order)
     outs = []
     for cuts in (None, [K], [1, 4, 1, 6], [5, 0, 6]):
-        trk = StreamTracker(s.width, s.height, s.obj, s.K, None, n_streams=1)
+        trk = StreamTracker(s.width, s.height, s.obj, s.K, None, n_streams=1, max_level=max_level)
+        assert trk.ctx.eff_max_level == max_level
         trk.dense_model(torch.from_numpy(mx).cuda(), torch.from_numpy(T).cuda(), iters=4, photo_weight=0.05, reseed=reseed)
         trk.reset(frames[0:1].contiguous(), torch.from_numpy(s.corners(0)[None]).cuda().contiguous())
         so = trk.new_state_buffer(K)

@@ -241,15 +241,26 @@ def test_stream_backend_frame_buffer_and_errors(tmp_path, seq10):
 def test_track_host_frame_record_paths(seq10):
     """agt_track_host_frame (include/agt_hip.h) called through the C ABI with a pinned and with a pageable h_state returns the
     16 doubles that agt_track_frame + agt_tracker_join + agt_download return"""
+    _host_frame_record_paths(seq10, 2)
+
+
+@pytest.mark.parametrize("max_level", [0, 3], ids=["L0", "L3"])
+def test_track_host_frame_record_paths_at_depth(seq10, max_level):
+    """the same at pyramid depths where the one-launch upload of a pinned frame does not apply (it needs depth 2): the frame is
+    copied and goes through agt_track_frame -- at depth 0 without any pyramid stage, at depth 3 through the six-level kernels"""
+    _host_frame_record_paths(seq10, max_level)
+
+
+def _host_frame_record_paths(s, max_level):
     import ctypes as C
     import torch
     from accurate_aprilgroup_tracking_amd import hiplib as H
     from accurate_aprilgroup_tracking_amd.tracker import StreamTracker
-    s = seq10
     W, Hh = s.width, s.height
 
     def run(kind):
-        trk = StreamTracker(W, Hh, s.obj, s.K, None, n_streams=1)
+        trk = StreamTracker(W, Hh, s.obj, s.K, None, n_streams=1, max_level=max_level)
+        assert trk.ctx.eff_max_level == max_level
         trk.pipeline(1)
         trk.reset(torch.from_numpy(s.frame(0)[None]).cuda().contiguous(), torch.from_numpy(s.corners(0)[None]).cuda().contiguous())
         L, h = trk.ctx.L, trk.ctx.h

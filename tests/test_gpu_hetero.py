@@ -39,9 +39,9 @@ TILT14 = np.array([[0.01, -0.005, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.004, -0.003]])
 
 
 def make_streams(width, height, B, steps, det_steps=(), n_tags=12, group_seed=0, n_frames=6, supersample=2, base_seed=100,
-                 kinds=True, camera="pinhole"):
+                 kinds=True, camera="pinhole", speed_scale=1.0):
     """B distinct streams showing the SAME AprilGroup (the object points are shared by the streams of a tracker).
-    Stream b: seed base_seed + b (trajectory phases, background), speed 0.6 ... 2.4, its own walk over its frames.
+    Stream b: seed base_seed + b (trajectory phases, background), speed (0.6 ... 2.4) * speed_scale, its own walk over its frames.
     kinds: stream 1 loses two corners at the first step, stream 2 (when B >= 3) keeps only 6 corners (below the gate
     until the detector speaks), the last stream's detector tables hold one tag only (no pose, guess cleared)."""
     from accurate_aprilgroup_tracking_amd import synthetic as syn
@@ -49,7 +49,8 @@ def make_streams(width, height, B, steps, det_steps=(), n_tags=12, group_seed=0,
     out = []
     for b in range(B):
         s = syn.Sequence(width, height, n_tags=n_tags, n_frames=n_frames, seed=base_seed + b, group_seed=group_seed,
-                         supersample=supersample, speed=0.6 + 1.8 * ((b * 7) % 11) / 10.0, dist=syn.MILD_DIST if camera == "lens" else None)
+                         supersample=supersample, speed=(0.6 + 1.8 * ((b * 7) % 11) / 10.0) * speed_scale,
+                         dist=syn.MILD_DIST if camera == "lens" else None)
         if camera == "tilt":
             s.dist = TILT14                                    # (camera model of the solver only: see TILT14)
         n = s.obj.shape[0]
@@ -77,8 +78,9 @@ def make_streams(width, height, B, steps, det_steps=(), n_tags=12, group_seed=0,
     return out
 
 
-def cpu_chain(oracle, st, tmp_path, tag):
-    """the stream's own CPU chain -> (records, final points, final status)"""
+def cpu_chain(oracle, st, tmp_path, tag, max_level=2, win=21, trace=None):
+    """the stream's own CPU chain -> (records, final points, final status).  The pyramids are built to max_level (a pre-built
+    pyramid caps the depth of the LK call); trace (a list): receives (points, status) of every step."""
     from oracle import cv2_shim
     from accurate_aprilgroup_tracking_amd.pose_detector import PoseDetector
     s = st.seq
@@ -95,7 +97,7 @@ def cpu_chain(oracle, st, tmp_path, tag):
 
     def pyr_of(k):
         if k not in pyrs:
-            pyrs[k] = oracle.Pyramid(s.frame(k))
+            pyrs[k] = oracle.Pyramid(s.frame(k), win, max_level)
         return pyrs[k]
     pts = st.c0.astype(np.float32).copy(); alive = np.ones(n, bool); pyr = pyr_of(0)
     recs = []
@@ -105,10 +107,12 @@ def cpu_chain(oracle, st, tmp_path, tag):
             tab, mask = st.det[i]
             nx = tab.astype(np.float32).copy(); alive = mask.astype(bool).copy()
         else:
-            nx, status, _ = oracle.calcOpticalFlowPyrLK(pyr, npyr, pts, maxLevel=2)
+            nx, status, _ = oracle.calcOpticalFlowPyrLK(pyr, npyr, pts, winSize=(win, win), maxLevel=max_level)
             nx = nx.reshape(-1, 2); status = status.ravel().astype(bool)
             nx[~alive] = pts[~alive]
             alive = alive & status
+        if trace is not None:
+            trace.append((nx.astype(np.float32).copy(), alive.copy()))
         il = [nx[j].reshape(1, 1, 2) for j in range(n) if alive[j]]
         ol = [obj32[j].reshape(1, 3) for j in range(n) if alive[j]]
         guided = det.extrinsic_guess[0] is not None
@@ -121,8 +125,10 @@ def cpu_chain(oracle, st, tmp_path, tag):
     return recs, pts, alive
 
 
-def run_device(streams, depth, width, height, perm=None, reproject=False):
-    """all streams through ONE StreamTracker -> (records [steps, B, 16], corners [B, n, 2], status [B, n])"""
+def run_device(streams, depth, width, height, perm=None, reproject=False, max_level=2, win=21, pitch=None, expect_max_level=None):
+    """all streams through ONE StreamTracker -> (records [steps, B, 16], corners [B, n, 2], status [B, n]).
+    pitch: the frames' row pitch in bytes (default: the width, packed), the bytes past the width hold a fill pattern;
+    expect_max_level: the depth the context must have trimmed its pyramid to."""
     import torch
     from accurate_aprilgroup_tracking_amd import hiplib as H
     from accurate_aprilgroup_tracking_amd.tracker import StreamTracker
@@ -133,15 +139,26 @@ def run_device(streams, depth, width, height, perm=None, reproject=False):
     n = s0.obj.shape[0]
     steps = len(ss[0].order)
     dev_frames = [torch.from_numpy(st.seq.frames()).cuda() for st in ss]          # per stream [F, H, W]
-    trk = StreamTracker(width, height, s0.obj, s0.K, s0.dist, n_streams=B, reproject=reproject)
+
+    def batch(ks):
+        """frame ks[b] of every stream b as one [B, H, W] batch"""
+        if pitch is None:
+            return torch.stack([dev_frames[b][ks[b]] for b in range(B)]).contiguous()
+        f = torch.full((B, height, pitch), 0xA5, dtype=torch.uint8, device="cuda")
+        for b in range(B):
+            f[b, :, :width] = dev_frames[b][ks[b]]
+        return f[:, :, :width]
+    trk = StreamTracker(width, height, s0.obj, s0.K, s0.dist, n_streams=B, reproject=reproject, max_level=max_level, win=win)
+    if expect_max_level is not None:
+        assert trk.ctx.eff_max_level == expect_max_level, "the device pyramid has %d levels" % (trk.ctx.eff_max_level + 1)
     trk.pipeline(depth)
-    f0 = torch.stack([dev_frames[b][0] for b in range(B)]).contiguous()
+    f0 = batch([0] * B)
     c0 = torch.from_numpy(np.stack([st.c0 for st in ss]).astype(np.float32)).cuda().contiguous()
     trk.reset(f0, c0)
     so = torch.zeros((steps, B, H.STATE_STRIDE), dtype=torch.float64, device="cuda")
     keep = [f0]
     for i in range(steps):
-        f = torch.stack([dev_frames[b][ss[b].order[i]] for b in range(B)]).contiguous()
+        f = batch([ss[b].order[i] for b in range(B)])
         keep.append(f)
         if i in ss[0].det:
             tab = torch.from_numpy(np.stack([st.det[i][0] for st in ss]).astype(np.float32)).cuda().contiguous()

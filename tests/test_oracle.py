@@ -289,6 +289,30 @@ def test_lk_oracle_equals_numpy_statement(oracle, seq640):
     assert seen_neg, "the edge-case set no longer reaches iw11 <= 0"
 
 
+@pytest.mark.parametrize("win,max_level", [(21, 5), (15, 4), (31, 4)], ids=["win21_L5", "win15_L4", "win31_L4"])
+def test_lk_oracle_equals_numpy_statement_deep(oracle, win, max_level):
+    """The same statement at the deepest pyramids the library builds: a 1280x720 pair with large motion (frames 0 -> 2 at six
+    times the default speed) at maxLevel 5, and the windows 15 and 31 at maxLevel 4 -- the depths the tracker's six-level kernels
+    are held to; the scene's corners and points at / beyond the borders, exact-sum mode, bit-exact."""
+    from tests import lk_numpy
+    s = syn.Sequence(1280, 720, n_tags=12, n_frames=3, seed=12, supersample=1, speed=6.0)
+    a, b = s.frame(0), s.frame(2)
+    h, w = a.shape
+    border = np.array([[0.0, 0.0], [w - 1.0, h - 1.0], [-5.5, 10.25], [w + 3.0, 7.0], [3.2, h + 8.9], [w - 11.0, h - 11.0],
+                       [1.0, h / 2.0], [w / 2.0, 2.5]], np.float32)
+    pts = np.concatenate([s.corners(0)[::2 if win != 21 else 1], border])
+    assert oracle.Pyramid(a, win, max_level).levels == max_level, "the pyramid is not trimmed"
+    o = oracle.calcOpticalFlowPyrLK(a, b, pts, winSize=(win, win), maxLevel=max_level)
+    m = lk_numpy.calc_optical_flow_pyr_lk(a, b, pts, win=win, max_level=max_level)
+    assert np.array_equal(o[1], m[1]), "status"
+    assert np.array_equal(o[0].view(np.uint32), m[0].view(np.uint32)), "nextPts differ by %g" % np.abs(o[0] - m[0]).max()
+    assert np.array_equal(o[2].view(np.uint32), m[2].view(np.uint32)), "err"
+    assert o[1].sum() >= len(pts) - len(border)
+    # the pair needs the top level: one level less tracks some corner differently
+    o1 = oracle.calcOpticalFlowPyrLK(a, b, pts, winSize=(win, win), maxLevel=max_level - 1)
+    assert (o1[0].view(np.uint32) != o[0].view(np.uint32)).any()
+
+
 def test_exact_vs_float_accumulation_bounded_at_pose_level(oracle, seq720_long):
     """DESIGN.md section 2 deviation 1 carried to the quantity north_star bounds (pose, <= 1e-4): the chained c2 stream
     (1280x720, 60 frames, raw LK chaining, no corner refresh) tracked twice by the oracle, with exact integer window sums
