@@ -308,7 +308,7 @@ int agt_create(const agt_config* cfg, void* hip_stream, agt_ctx** out)
         c->hseq_host = (unsigned long long*)((char*)c->fault_host + 192); c->hseq_dev = (unsigned long long*)((char*)c->fault_dev + 192);
     }
     if (!ok) { hip_fail(nullptr, hipGetLastError()); agt_destroy(c); return AGT_ERR_ALLOC; }
-    c->last_p_ev = -1; c->l_ev_hist[0] = c->l_ev_hist[1] = c->l_ev_hist[2] = -1; c->y_ev_hist[0] = c->y_ev_hist[1] = -1;
+    c->split.reset_history();
     c->pipeline = agt_step_supported(cfg->win) ? 1 : 0;
     c->reproject = 0; c->min_points = 8; c->gate_px = 2.0;
     // knobs: fixed iteration counts (AGT_LK_MAX_COUNT=n AGT_LK_EPS=0) separate the per-iteration cost of the LK role from its per-frame cost
@@ -329,7 +329,7 @@ int agt_destroy(agt_ctx* c)
     }
     if (c->ms_pool_slot >= 0) {                      // (also after an ms_init that stopped half-way: the slot and the events it did create)
         for (int i = 0; i < 3; i++) (void)hipStreamSynchronize(c->ms_stream[i]);
-        for (int k = 0; k < 5; k++) for (int i = 0; i < AGT_EV_SLOTS; i++) if (c->ms_ev[k][i]) (void)hipEventDestroy(c->ms_ev[k][i]);
+        for (int k = 0; k < SplitEvents::ROWS; k++) for (int i = 0; i < AGT_EV_SLOTS; i++) if (c->split.ev[k][i]) (void)hipEventDestroy(c->split.ev[k][i]);
         ms_pool_release(c->ms_pool_slot);            // (the streams go back to the process's pool: see ms_pool_acquire)
     }
     if (c->lkerr) (void)hipFree(c->lkerr);

@@ -6,6 +6,30 @@
 #include <string.h>
 #include <stdio.h>
 
+// ---- the idioms of the unit: ring entry of tracker frame `frame`; level l of the pyramid in ring entry `slot` (level 0 is the caller's frame)
+static inline int ring_slot(const agt_ctx* c, long frame) { return (int)(frame % c->live_ring); }
+static inline const uint8_t* level_ptr(const agt_ctx* c, int slot, int l) { return l == 0 ? c->l0_ptr[slot] : c->lmem[slot][l]; }
+static inline bool frame_args_ok(const agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride)
+{
+    return !((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width);
+}
+// A frame takes ring entry `slot`: level 0 is the caller's buffer, B streams of it; state_out: where its record goes (fused pipeline).
+// (pyramid_build_on registers the same, but built_B only once its launches are out.)
+static inline void register_frame(agt_ctx* c, int slot, const uint8_t* ptr, size_t pitch, size_t batch_stride, int B, double* state_out)
+{
+    c->l0_ptr[slot] = ptr; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
+    c->built_B[slot] = B; c->so_ring[slot] = state_out;
+}
+// frame t is the newest frame and complete in every stage
+static inline void frame_complete(agt_ctx* c, long t)
+{
+    c->trk_frame = c->n_lk = c->n_pnp = t;
+    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = t;
+}
+// stage spans are being recorded (agt_profile_begin) and there is room for another frame's; that frame's events (null: none)
+static inline bool profiling_armed(const agt_ctx* c) { return c->prof_ev && c->prof_n < c->prof_cap; }
+static inline hipEvent_t* profile_events(const agt_ctx* c) { return profiling_armed(c) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr; }
+
 // scratch of the dense refinement: `need` doubles of block partials and one done word per stream; the two
 // capacities are tracked separately (a later call may bring more streams with fewer samples)
 int dense_scratch(agt_ctx* c, size_t need, int B)
@@ -31,7 +55,7 @@ int dense_scratch(agt_ctx* c, size_t need, int B)
 int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B)
 {
     if (!c || !d_frames || slot < 0 || slot >= c->ring || B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
-    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
     c->l0_ptr[slot] = d_frames; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
     const uint8_t* src = d_frames; long sp = (long)pitch, sb = (long)batch_stride;
     int l0 = 1;
@@ -66,9 +90,9 @@ int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_
 static void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
 {
     for (int l = 0; l <= c->eff_max_level; l++) {
-        L[l].w = c->lw[l]; L[l].h = c->lh[l];
-        if (l == 0) { L[l].ptr = c->l0_ptr[slot]; L[l].pitch = c->l0_pitch[slot]; L[l].bstride = c->l0_bstride[slot]; }
-        else { L[l].ptr = c->lmem[slot][l]; L[l].pitch = c->lpitch[l]; L[l].bstride = (long)c->lh[l] * c->lpitch[l]; }
+        L[l].w = c->lw[l]; L[l].h = c->lh[l]; L[l].ptr = level_ptr(c, slot, l);
+        if (l == 0) { L[l].pitch = c->l0_pitch[slot]; L[l].bstride = c->l0_bstride[slot]; }
+        else { L[l].pitch = c->lpitch[l]; L[l].bstride = (long)c->lh[l] * c->lpitch[l]; }
     }
 }
 
@@ -92,28 +116,37 @@ static int fill_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int next_slo
     return AGT_OK;
 }
 
+// the tracker's own LK from the frame in ring entry prev_slot to the one in `slot`: their corner / status entries, the tracker's criteria
+static void fill_tracker_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int slot)
+{
+    fill_lk(c, p, prev_slot, slot, c->corners[prev_slot], c->status[prev_slot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
+            AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
+}
+
+// image k of an LK group per level (k = 0: frame f0, the one before the group) and the corner / status entries of frames f0 + 1 .. f0 + count
+static void fill_lk_table(const agt_ctx* c, AgtLkTables& t, long f0, int count)
+{
+    for (int k = 0; k <= count; k++) {
+        const int q = ring_slot(c, f0 + k);
+        for (int l = 0; l <= c->eff_max_level; l++) t.img[k][l] = level_ptr(c, q, l);
+        if (k) { t.next[k - 1] = c->corners[q]; t.status[k - 1] = c->status[q]; }
+    }
+}
+
 #define AGT_SPLIT_LK_CU 10       // (see agt_lk_occupancy_cu)
 #define AGT_SPLIT_PYR_OH 6       // strip height (level-2 rows) of the split pipeline's pyramid role (agt_pyramid.hip agt_pyr2_plan) ...
 #define AGT_SPLIT_PYR_OH_B0 12   // ... for batches of 12 .. 96 streams: measured (session r6ar, us per step, strips of 6 / 16) 8 streams 20.1 / 19.8,
 #define AGT_SPLIT_PYR_OH_B1 96   // 16: 27.5 / 28.3, 32: 29.4 / 29.9, 64: 35.1-35.9 / 36.7-37.6, 128: 63.7 / 62.4
-int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
-                const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
-                int n, int B, int crit_type, int crit_max_count, double crit_eps,
-                int flags, double min_eig_threshold, int b0, int waves)
+// The stand-alone LK launch of a filled parameter block.  b0: first stream of the launch (streams b0 .. b0 + B - 1 of the slots and of
+// the point arrays); waves: see agt_launch_lk
+static int lk_launch_on(agt_ctx* c, hipStream_t stream, AgtLkParams& p, int prev_slot, int next_slot, int B, int b0, int waves)
 {
-    // b0: first stream of the launch (streams b0 .. b0 + B - 1 of the slots and of the point arrays); waves: see agt_launch_lk
-    if (!c || !d_prev_pts || !d_next_pts || !d_status) return AGT_ERR_ARG;
-    if (prev_slot < 0 || prev_slot >= c->ring || next_slot < 0 || next_slot >= c->ring) return AGT_ERR_ARG;
-    if (n < 0 || B <= 0 || b0 < 0) return AGT_ERR_ARG;
-    if (n == 0) return AGT_OK;
     if (c->built_B[prev_slot] < b0 + B || c->built_B[next_slot] < b0 + B) return AGT_ERR_STATE;
-    AgtLkParams p;
-    fill_lk(c, &p, prev_slot, next_slot, d_prev_pts, d_prev_status, d_next_pts, d_status, d_err, n, crit_type, crit_max_count, crit_eps,
-            flags & 0xffff, min_eig_threshold);          // (the bits above 0xffff are internal launch flags)
     // (waves == 1: a half-batch launch of the split pipeline -- beside the other half's launch and the pyramid launch of the frames ahead)
     p.lds_min = lk_lds_min(c->lk_cap_cu >= 0 ? c->lk_cap_cu : (waves == 1 ? AGT_SPLIT_LK_CU : 0));
     if (c->lk_cap_cu > 0) p.flags |= AGT_LK_FLAG_COTENANT;        // (declared by the caller: agt_lk_occupancy_cu; see agt_lk.hip lk_kernel)
     if (b0) {
+        const int n = p.n;
         for (int l = 0; l <= c->eff_max_level; l++) { p.prev[l].ptr += (long)b0 * p.prev[l].bstride; p.next[l].ptr += (long)b0 * p.next[l].bstride; }
         p.prev_pts += (size_t)b0 * n * 2; p.next_pts += (size_t)b0 * n * 2; p.status += (size_t)b0 * n;
         if (p.prev_status) p.prev_status += (size_t)b0 * n;
@@ -121,6 +154,29 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
     }
     hipError_t e = agt_launch_lk(stream, p, c->cfg.win, B, c->cfg.win == 21 ? waves : 0);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
+                const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
+                int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                int flags, double min_eig_threshold, int b0, int waves)
+{
+    if (!c || !d_prev_pts || !d_next_pts || !d_status) return AGT_ERR_ARG;
+    if (prev_slot < 0 || prev_slot >= c->ring || next_slot < 0 || next_slot >= c->ring) return AGT_ERR_ARG;
+    if (n < 0 || B <= 0 || b0 < 0) return AGT_ERR_ARG;
+    if (n == 0) return AGT_OK;
+    AgtLkParams p;
+    fill_lk(c, &p, prev_slot, next_slot, d_prev_pts, d_prev_status, d_next_pts, d_status, d_err, n, crit_type, crit_max_count, crit_eps,
+            flags & 0xffff, min_eig_threshold);          // (the bits above 0xffff are internal launch flags)
+    return lk_launch_on(c, stream, p, prev_slot, next_slot, B, b0, waves);
+}
+
+// the tracker's LK launch of streams b0 .. b0 + B - 1 between two of its ring entries (B >= 1 and trk_n >= 4 by agt_tracker_reset)
+static int track_lk_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B, int b0 = 0, int waves = 0)
+{
+    AgtLkParams p;
+    fill_tracker_lk(c, &p, prev_slot, slot);
+    return lk_launch_on(c, stream, p, prev_slot, slot, B, b0, waves);
 }
 
 int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float* d_obj, int n, int B,
@@ -158,8 +214,8 @@ int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float*
     if (e != hipSuccess) return hip_fail(c, e);
     c->prebuilt_t = -1;
     c->hseq_off = c->hseq_last + 1;          // (sequence numbers of agt_track_host_frame stay monotonic across runs)
-    c->trk_n = n; c->trk_B = B; c->trk_frame = 0; c->n_lk = c->n_pnp = 0; c->enhance_ape = enhance_ape ? 1 : 0;
-    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = 0;
+    c->trk_n = n; c->trk_B = B; c->enhance_ape = enhance_ape ? 1 : 0;
+    frame_complete(c, 0);
     c->trk_ready = d_corners ? 2 : 1;
     return AGT_OK;
 }
@@ -264,9 +320,11 @@ static int ms_init(agt_ctx* c)
     if (c->ms_ready) return AGT_OK;
     if (c->ms_pool_slot < 0) c->ms_pool_slot = ms_pool_acquire(c->cfg.device, c->ms_stream);        // (a retry after a failed event creation keeps its slot)
     if (c->ms_pool_slot < 0) return hip_fail(c, hipGetLastError());
-    for (int k = 0; k < 5; k++)
-        for (int i = 0; i < AGT_EV_SLOTS; i++)
-            if (!c->ms_ev[k][i] && hipEventCreateWithFlags(&c->ms_ev[k][i], hipEventDisableTiming) != hipSuccess) { c->ms_ev[k][i] = nullptr; return hip_fail(c, hipGetLastError()); }
+    for (int k = 0; k < SplitEvents::ROWS; k++)
+        for (int i = 0; i < AGT_EV_SLOTS; i++) {
+            hipEvent_t& ev = c->split.ev[k][i];
+            if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; return hip_fail(c, hipGetLastError()); }
+        }
     c->ms_ready = 1;
     return AGT_OK;
 }
@@ -275,7 +333,8 @@ static int ms_init(agt_ctx* c)
 static int ms_join(agt_ctx* c)
 {
     if (!c->ms_active) return AGT_OK;
-    hipEvent_t ev1 = c->ms_ev[2][0], ev2 = c->ms_ev[2][1], ev0 = c->ms_ev[2][3];
+    hipEvent_t* join = c->split.ev[SplitEvents::MISC];
+    hipEvent_t ev1 = join[SplitEvents::JOIN_LK], ev2 = join[SplitEvents::JOIN_POSE], ev0 = join[SplitEvents::JOIN_LK2];
     hipError_t e = hipEventRecord(ev1, c->ms_stream[1]);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev1, 0);
     if (e == hipSuccess) e = hipEventRecord(ev0, c->ms_stream[0]);
@@ -284,11 +343,305 @@ static int ms_join(agt_ctx* c)
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev2, 0);
     if (e != hipSuccess) return hip_fail(c, e);
     c->ms_active = 0;
-    c->last_p_ev = -1; c->l_ev_hist[0] = c->l_ev_hist[1] = c->l_ev_hist[2] = -1; c->y_ev_hist[0] = c->y_ev_hist[1] = -1;     // everything issued so far is ordered before the caller's next work
+    c->split.reset_history();            // everything issued so far is ordered before the caller's next work
     return AGT_OK;
 }
 
-// One fused launch: every pipeline stage advances by up to `group` frames whose input is complete.
+// ---- One group launch: every pipeline stage advances by up to `group` frames whose input is complete.  launch_group (below) takes
+// a snapshot of the pipeline, PLANS the three roles (plan_pyramid, plan_lk, plan_pose: each fills its part of the launch's parameters
+// S and per-frame tables T and advances its own counters of the context: n_stage, n_lk, n_pnp + lk_target), and ISSUES the launch
+// in the fused or the split form.  Whatever has to be decided on the state BEFORE the launch is decided on the snapshot.
+struct GroupEntry {
+    int L, F, B;                                 // pyramid stages 0..L-1 (stage s: level s -> s+1); the most frames a role advances by; streams
+    // agt_step_fits: the fused launch (one kernel, all roles), otherwise the split form.  The fused launch is also CHAINED: its PnP role
+    // follows the LK role of the SAME launch frame by frame through arrival counters (agt_step.hip pnp_role), instead of one launch behind it.
+    bool fits;
+    // a launch that will carry pyramid work ONLY (the first one of a run: no frame is ready for the LK role, none for the pose role)
+    // goes out as the pyramid kernel proper (issue_fused), which has the register-rolling two-level pass -- the fused step kernel has not
+    bool pyr_only;
+    long done_before[AGT_MAX_LEVELS + 1];        // [s] = frames available as input of stage s (s = L: input of LK)
+    long lk_before;                              // frames tracked so far: the LK role's group starts behind this frame
+};
+
+// geometry of pyramid stage s (level s -> s + 1); stage 0's source pitch and stream stride are those of the caller's frames
+static void stage_geometry(const agt_ctx* c, int s, int B, AgtPyrArgs& A)
+{
+    A.sw = c->lw[s]; A.sh = c->lh[s]; A.dw = c->lw[s + 1]; A.dh = c->lh[s + 1]; A.B = B;
+    if (s) { A.spitch = c->lpitch[s]; A.sbatch = (long)c->lh[s] * c->lpitch[s]; }
+    A.dpitch = c->lpitch[s + 1]; A.dbatch = (long)c->lh[s + 1] * c->lpitch[s + 1];
+}
+
+// Stage 0 as the two-level pass (levels 1 and 2 from level 0): the level 1 -> 2 geometry and buffers ride in stage 1's slots; the pass's
+// grid in pyr[0]: 64 x 16 tiles of level 2 (tiled form) or workgroups per image with the strip height in pad (register-rolling form,
+// agt_pyramid4_body.h).  Stage 0's single-level plan of frames first .. first + cnt - 1 is in S.pyr[0] / T; returns whether the
+// two-level pass replaces it (`fused` on entry: it has to, the batch is small).
+static bool plan_two_level(agt_ctx* c, const GroupEntry& G, AgtStepParams& S, AgtStepTables& T, long first, int cnt,
+                           uintptr_t src_align, uintptr_t dst_align, bool fused)
+{
+    const int B = G.B;
+    AgtPyrArgs A0 = S.pyr[0], A1 = S.pyr[1];
+    stage_geometry(c, 1, B, A1);
+    uintptr_t d2_align = 0;
+    for (int k = 0; k < cnt; k++) d2_align |= (uintptr_t)c->lmem[ring_slot(c, first + k)][2];
+    // (fused step: agt_step_fits, <= 256 corners in flight -- its kernel carries the tiled two-level pass only: plan as ONE frame, which
+    // keeps the launch below the rolling form's 16 images.  Round 5: except the pyramid-only launch at the head of a run, which is
+    // pyr_group_kernel -- 20 frames of 1280x720, the driver's block: 15.1 us tiled, see DESIGN.md section 6 for the rolling figure)
+    agt_pyr2_plan(&A0, &A1, src_align, dst_align | d2_align, (G.fits && !G.pyr_only) ? 1 : cnt,
+                  (G.fits || B < AGT_SPLIT_PYR_OH_B0 || B > AGT_SPLIT_PYR_OH_B1) ? 16 : AGT_SPLIT_PYR_OH);
+    if (!fused && A0.pad != 0 && c->n_stage[1] == first - 1) fused = true;       // big batch, rolling form, no backlog (stage 1 is where stage 0 is)
+    if (fused) {
+        S.pyr[0] = A0; S.pyr[1] = A1;
+        for (int k = 0; k < cnt; k++) T.pyr_dst[1][k] = c->lmem[ring_slot(c, first + k)][2];
+        c->n_stage[1] += cnt;            // (same frames: level 2 is complete when level 1 is)
+    }
+    return fused;
+}
+
+// Pyramid role: stage s takes up to F of the frames whose level s is complete.  Returns whether any stage has work.
+static bool plan_pyramid(agt_ctx* c, const GroupEntry& G, AgtStepParams& S, AgtStepTables& T)
+{
+    const int L = G.L, B = G.B;
+    bool any = false;
+    // stage 0 builds levels 1 and 2 in one pass (stage 1 then only keeps the books): always while the batch is small (tiled or
+    // register-rolling two-level pass), for big batches where the rolling form applies to every frame of the launch (plan_two_level)
+    // and stage 1 has no backlog from an earlier launch that ran the levels as two passes
+    bool fused = L >= 2 && B <= AGT_PYR2_MAX_B;
+    for (int s = 0; s < L; s++) {
+        if (fused && s == 1) continue;
+        const long first = c->n_stage[s] + 1;    // the stage's next frame
+        long cnt = G.done_before[s] - c->n_stage[s];
+        if (cnt <= 0) continue;
+        if (cnt > G.F) cnt = G.F;
+        AgtPyrArgs& A = S.pyr[s];
+        stage_geometry(c, s, B, A);
+        uintptr_t src_align = 0, dst_align = 0;
+        for (long k = 0; k < cnt; k++) {
+            const int slot = ring_slot(c, first + k);
+            if (s == 0) {
+                // level 0 is the caller's frame: the frames of a group must share pitch and stream stride
+                if (k == 0) { A.spitch = c->l0_pitch[slot]; A.sbatch = c->l0_bstride[slot]; }
+                else if (A.spitch != c->l0_pitch[slot] || A.sbatch != c->l0_bstride[slot]) { cnt = k; break; }
+            }
+            T.pyr_src[s][k] = level_ptr(c, slot, s);
+            T.pyr_dst[s][k] = c->lmem[slot][s + 1];
+            src_align |= (uintptr_t)T.pyr_src[s][k]; dst_align |= (uintptr_t)T.pyr_dst[s][k];
+        }
+        A.src = T.pyr_src[s][0]; A.dst = T.pyr_dst[s][0];
+        agt_pyr_plan(&A, src_align, dst_align, (int)cnt);          // tiled or register-rolling form (A.pad), workgroups per image in A.gx * A.gy
+        if (s == 0 && L >= 2) fused = plan_two_level(c, G, S, T, first, (int)cnt, src_align, dst_align, fused);
+        S.pyr_nf[s] = (int)cnt;
+        S.n_pyr[s] = A.gx * A.gy * B * (int)cnt;
+        c->n_stage[s] += cnt;
+        any = true;
+    }
+    S.pyr_fused = fused ? 1 : 0;
+    return any;
+}
+
+// LK role: up to F of the frames whose pyramid is complete, behind frame G.lk_before.  Returns the frames tracked once the launch is through.
+static long plan_lk(agt_ctx* c, const GroupEntry& G, AgtStepParams& S, AgtStepTables& T)
+{
+    const long f0 = G.lk_before;                 // the frame before the group
+    long cnt = G.done_before[G.L] - f0;
+    if (cnt <= 0) return c->n_lk;
+    if (cnt > G.F) cnt = G.F;
+    // level 0 geometry comes from the frame's own registration; a group needs it uniform
+    const int pslot = ring_slot(c, f0);
+    for (long k = 1; k <= cnt; k++) {
+        const int q = ring_slot(c, f0 + k);
+        if (c->l0_pitch[q] != c->l0_pitch[pslot] || c->l0_bstride[q] != c->l0_bstride[pslot]) { cnt = k > 1 ? k - 1 : 1; break; }
+    }
+    fill_tracker_lk(c, &S.lk, pslot, ring_slot(c, f0 + 1));
+    fill_lk_table(c, T.lk, f0, (int)cnt);        // (arrival counters: attached by plan_pose)
+    S.lk_nf = (int)cnt;
+    S.n_lk = 1; S.lk_B = G.B;
+    return c->n_lk += cnt;
+}
+
+// Pose role.  Frames it may take: everything tracked before this launch; chained, also the frames tracked BY it (lk_before + 1 ..
+// lk_after), waiting for each one's counter -- all of them when nothing more is registered (a drain: the last frames' latency counts),
+// all but the newest while frames keep coming (the role then never stalls: the LK role works one frame ahead of it)
+static void plan_pose(agt_ctx* c, const GroupEntry& G, long lk_after, AgtStepParams& S, AgtStepTables& T)
+{
+    long avail = G.lk_before;
+    if (G.fits) avail = lk_after - (lk_after < c->trk_frame && lk_after > G.lk_before ? 1 : 0);
+    long cnt = avail - c->n_pnp;
+    if (cnt <= 0) return;
+    if (cnt > G.F) cnt = G.F;
+    const long first = c->n_pnp + 1;
+    const int slot = ring_slot(c, first);
+    fill_estimate(c, &S.pnp, c->corners[slot], c->status[slot], c->so_ring[slot], nullptr);
+    arm_host_seq(c, &S.pnp, first);
+    for (long k = 0; k < cnt; k++) {
+        const long f = first + k;
+        const int q = ring_slot(c, f);
+        T.pnp.img[k] = c->corners[q]; T.pnp.mask[k] = c->status[q]; T.pnp.so[k] = c->so_ring[q];
+        if (f > G.lk_before) {
+            // tracked by this launch (frame f - lk_before - 1 of its LK group): the LK role counts the frame's corners in (device-scope
+            // stores + acknowledgement, only for the frames somebody waits for), the PnP wave waits for the count
+            c->lk_target[q] += (unsigned)c->trk_n;
+            T.lk.done[f - G.lk_before - 1] = c->lk_done + (size_t)q * c->cfg.max_streams;
+            T.pnp.wait[k] = T.lk.done[f - G.lk_before - 1]; T.pnp.target[k] = c->lk_target[q];
+        }
+    }
+    S.pnp_nf = (int)cnt;
+    S.n_pnp = G.B;
+    c->n_pnp += cnt;
+}
+
+// The fault-injection knobs of the diagnostic libraries, between plan and issue (the product: nothing).  Each counts, process-wide, the
+// launches that satisfy ITS condition: tests/test_gpu_tracker.py addresses a launch by that count.
+static void debug_inject(const AgtStepParams& S, AgtStepTables& T)
+{
+    // AGT_CHAIN_WITHHOLD=k makes the k-th launch with chained waits expect one arrival more than its LK role delivers for the SECOND
+    // waited frame (the first if there is only one): the give-up path
+    if (const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD", 0)) {
+        static long seen = 0;
+        int waited[2] = { -1, -1 }, nw = 0;
+        for (int k = 0; k < S.pnp_nf && nw < 2; k++) if (T.pnp.wait[k]) waited[nw++] = k;
+        if (wh > 0 && nw > 0 && ++seen == wh) T.pnp.target[waited[nw - 1]] += 1;
+    }
+    // AGT_TABLE_POISON_PNP=k / AGT_TABLE_POISON_LK=k put a word that cannot be an address (the bits of a NaN) into the second frame's
+    // entry of the k-th launch whose pose / LK role runs more than one frame -- what a stale or clobbered LDS table would hand the
+    // role: the launch must drain, flag and report, not fault
+    const long pk = AGT_KNOB("AGT_TABLE_POISON_PNP", 0), lk = AGT_KNOB("AGT_TABLE_POISON_LK", 0);
+    static long seen_p = 0, seen_l = 0;
+    if (pk > 0 && S.pnp_nf > 1 && ++seen_p == pk) T.pnp.img[1] = (const float*)0x7ff8dead00000000ull;
+    if (lk > 0 && S.lk_nf > 1 && ++seen_l == lk) T.lk.img[2][0] = (const uint8_t*)0x7ff8dead00000000ull;
+}
+
+static int issue_fused(agt_ctx* c, const AgtStepParams& S, const AgtStepTables& T)
+{
+    // a launch with pyramid work only (the first one of a run) goes out as the pyramid kernel proper: eight workgroups per
+    // CU instead of the one the fused kernel's register budget leaves (16 frames of 720p: ~7 us instead of ~12)
+    const int roles = (S.n_lk > 0 || S.n_pnp > 0) ? AGT_STEP_ALL : AGT_STEP_PYR;
+    hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, roles);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// ---- split mode (issue_split).  The pyramid and the pose role alike: `stream` waits for both halves of LK launch `lk_wait` (its event
+// slot; -1 = none to wait for), the role's launch, its event `done`.
+static int split_role(agt_ctx* c, const AgtStepParams& S, const AgtStepTables& T, int roles, hipStream_t stream, int lk_wait, hipEvent_t done)
+{
+    const SplitEvents& E = c->split;
+    hipError_t e = hipSuccess;
+    if (lk_wait >= 0) {
+        e = hipStreamWaitEvent(stream, E.ev[SplitEvents::LK_DONE][lk_wait], 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream, E.ev[SplitEvents::LK2_DONE][lk_wait], 0);
+    }
+    if (e == hipSuccess) e = agt_launch_step(stream, S, T, c->cfg.win, roles);
+    if (e == hipSuccess) e = hipEventRecord(done, stream);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// One stand-alone LK launch per frame f0 + 1 .. f0 + nf (and half: streams [0, B1) on sL, [B1, B) on sL2), back to back on its stream
+// (as a role with an in-kernel frame loop the one-wave-per-corner kernel needs 240 B of scratch per lane at its 128-register budget
+// and runs at half speed)
+static int split_lk_frames(agt_ctx* c, hipStream_t sL, hipStream_t sL2, long f0, int nf, int B, int B1)
+{
+    const bool two = B1 < B;
+    for (int k = 1; k <= nf; k++) {
+        const int ps = ring_slot(c, f0 + k - 1), sl = ring_slot(c, f0 + k);
+        // (waves = 1: a half is sized by the whole batch's kernel choice, not by its own corner count)
+        int rc = track_lk_on(c, sL, ps, sl, B1, 0, two ? 1 : 0);
+        if (rc == AGT_OK && two) rc = track_lk_on(c, sL2, ps, sl, B - B1, B1, 1);
+        if (rc) return rc;
+    }
+    return AGT_OK;
+}
+
+// The LK role of the group; p_before: event slot of the pyramid launch BEFORE this group's (-1 = none since the last join)
+static int split_lk(agt_ctx* c, const GroupEntry& G, const AgtStepParams& S, const AgtStepTables& T, int p_before)
+{
+    SplitEvents& E = c->split;
+    const int B = G.B, slot = E.next_slot(SplitEvents::LK);
+    hipStream_t sL = c->ms_stream[1], sL2 = c->ms_stream[0];
+    // The per-frame LK launches of a group depend on each other (a corner starts where it ended), leave ~4 us between one
+    // kernel's end and the next one's start on their stream, and each lasts as long as its slowest corner.  A batch of the
+    // one-wave-per-corner kernel whose halves still hold >= 512 corners goes out as two launches per frame on two streams,
+    // streams [0, B1) and [B1, B), both with the one-wave kernel: each half's gaps and tails are filled by the other half's
+    // kernel.  Every wait on / record of the LK role is done for both streams.  (Round 3: the halves used to be taken
+    // only from 44 streams of 48 corners on; 22 .. 43 streams gain 12-20 % -- 42 streams 43.9 -> 36.6 us per step.  Four
+    // quarters on four streams lose badly -- 64 streams 160 us, 86 with GPU_MAX_HW_QUEUES=8 against 49.7: more streams than
+    // hardware queues, and four kernels of <= 1 wave per SIMD each stretch one another.)
+    // Up to 1024 corners in flight (the four-waves-per-corner body): the LK role of the WHOLE group as one launch --
+    // lk_group_kernel, the frame-chained body of the fused step with its own register budget (153 VGPRs, three workgroups
+    // per CU) -- instead of one ~17 us launch + ~5 us gap per frame (round 3: 16 streams 33.9 -> see profiles/r03_stream_sweep.txt).
+    const bool lk_group = agt_lk_wide(c->trk_n, B);
+    const int B1 = (!lk_group && (long)c->trk_n * (B / 2) >= 512) ? B / 2 : B;
+    const bool two = B1 < B;
+    hipError_t e = hipSuccess;
+    hipEvent_t first = nullptr;
+    if (p_before >= 0) first = E.ev[SplitEvents::PYR_DONE][p_before];
+    else {
+        // no pyramid launch since the last join (single-level pyramids, or the first LK of a run): order the LK streams
+        // behind the caller's stream explicitly (reset's corner copy, earlier modes' pyramids)
+        first = E.ev[SplitEvents::MISC][SplitEvents::HANDOVER];
+        e = hipEventRecord(first, c->stream);
+    }
+    for (int h = 0; h < (two ? 2 : 1) && e == hipSuccess; h++) {
+        hipStream_t sh = h ? sL2 : sL;
+        e = hipStreamWaitEvent(sh, first, 0);
+        if (e == hipSuccess && E.pose_hist[1] >= 0) e = hipStreamWaitEvent(sh, E.ev[SplitEvents::POSE_DONE][E.pose_hist[1]], 0);
+    }
+    if (e == hipSuccess && lk_group) e = agt_launch_step(sL, S, T, c->cfg.win, AGT_STEP_LK);
+    if (e != hipSuccess) return hip_fail(c, e);
+    if (!lk_group) {
+        int rc = split_lk_frames(c, sL, sL2, G.lk_before, S.lk_nf, B, B1);
+        if (rc) return rc;
+    }
+    e = hipEventRecord(E.ev[SplitEvents::LK_DONE][slot], sL);
+    // (recorded on the second stream in any case: an idle stream's event is complete at once, the waits stay uniform)
+    if (e == hipSuccess) e = hipEventRecord(E.ev[SplitEvents::LK2_DONE][slot], two ? sL2 : sL);
+    if (e != hipSuccess) return hip_fail(c, e);
+    E.pushed_lk(slot);
+    c->ms_active = 1;
+    return AGT_OK;
+}
+
+// The same group as three launches, one per role, each with its own LDS size and register budget:
+// pyramid on the caller's stream (the frames come from there), LK and PnP on two library streams.  The roles of one
+// group are independent (the pipeline skews them across frames), so the three launches overlap; ordering is by events:
+//   LK(k)  waits for pyramid(k-1)   (its images)          and for PnP(k-2)  (ring reuse of corner / status entries)
+//   PnP(k) waits for LK(k-1)        (its corners)
+//   pyramid(k) waits for LK(k-3)    (ring reuse of level entries: split mode keeps AGT_SPLIT_SLACK = 2 groups of extra
+//                                    ring entries, so the HBM-bound pyramid launches run AHEAD of the LK launches they share
+//                                    the chip with and never sit on the critical path; the wait also keeps the caller's
+//                                    stream behind the readers of frames handed over (L + 6) groups ago, so stream-ordered
+//                                    allocators may recycle those)
+// Ten HIP calls per GROUP of F frames (round 1 issued thirteen per frame).
+// A role's n-th launch records event slot n % AGT_EV_SLOTS, so the slot a wait names (at most three launches of its role old) is not
+// re-recorded before it.  (The slots used to follow the group count: a role that sat groups out could wait on a slot that a NEWER
+// launch of the same role and stream had re-recorded -- later completion, so that could only over-synchronise.)
+static int issue_split(agt_ctx* c, const GroupEntry& G, const AgtStepParams& S, const AgtStepTables& T)
+{
+    int rc = ms_init(c);
+    if (rc) return rc;
+    SplitEvents& E = c->split;
+    // the roles of this group wait for the launches of the groups BEFORE it: read before this group's launches enter the histories
+    const int p_before = E.last_pyr, l_before = E.lk_hist[0];
+    bool p_work = false;
+    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) p_work |= S.n_pyr[s] > 0;
+    if (p_work) {
+        const int slot = E.next_slot(SplitEvents::PYR);
+        rc = split_role(c, S, T, AGT_STEP_PYR, c->stream, E.lk_hist[AGT_SPLIT_SLACK], E.ev[SplitEvents::PYR_DONE][slot]);
+        if (rc) return rc;
+        E.pushed_pyr(slot);
+    }
+    if (S.n_lk > 0) {
+        rc = split_lk(c, G, S, T, p_before);
+        if (rc) return rc;
+    }
+    if (S.n_pnp > 0) {
+        const int slot = E.next_slot(SplitEvents::POSE);
+        rc = split_role(c, S, T, AGT_STEP_PNP, c->ms_stream[2], l_before, E.ev[SplitEvents::POSE_DONE][slot]);
+        if (rc) return rc;
+        E.pushed_pose(slot);
+        c->ms_active = 1;
+    }
+    return AGT_OK;
+}
+
 // fmax: the most frames a stage advances by in this call (0 = c->group).  The split pipeline (big batches: three launches per group)
 // runs groups of c->group frames in the steady state but SMALLER ones while it fills and drains (round 6, tools/trace_blocks.py: of a
 // 256-frame block of 64 streams 8 % was the first pyramid launch with nothing beside it and the last pose launch with nothing beside it --
@@ -296,290 +649,50 @@ static int ms_join(agt_ctx* c)
 static int split_ramp(const agt_ctx* c) { const int r = c->group / 4; return r < 2 ? (c->group < 2 ? c->group : 2) : r; }
 static int launch_group(agt_ctx* c, int B, int fmax = 0)
 {
-    const int L = c->eff_max_level;              // pyramid stages 0..L-1 (stage s: level s -> s+1)
-    const int F = (fmax > 0 && fmax < c->group) ? fmax : c->group, M = c->live_ring;
-    AgtStepParams S;
-    AgtStepTables T;
-    memset(&S, 0, sizeof(S));
-    memset(&T, 0, sizeof(T));
+    GroupEntry G;
+    G.L = c->eff_max_level; G.F = (fmax > 0 && fmax < c->group) ? fmax : c->group; G.B = B;
+    G.fits = agt_step_fits(c->trk_n, B);
+    G.done_before[0] = c->trk_frame;
+    for (int s = 0; s < G.L; s++) G.done_before[s + 1] = c->n_stage[s];
+    G.lk_before = c->n_lk;
+    G.pyr_only = c->n_lk >= G.done_before[G.L] && c->n_pnp >= c->n_lk;
+    AgtStepParams S; AgtStepTables T;
+    memset(&S, 0, sizeof(S)); memset(&T, 0, sizeof(T));
     S.pnp.fault = c->fault_dev;                  // (also where the launch has no pose role: the LK role reports a table it cannot use through it)
-    long done_before[AGT_MAX_LEVELS + 1];        // [s] = frames available as input of stage s (s = L: input of LK)
-    done_before[0] = c->trk_frame;
-    for (int s = 0; s < L; s++) done_before[s + 1] = c->n_stage[s];
-    const long lk_before = c->n_lk;
-    long lk_f0 = 0;                              // LK role: the frame before its group
-    bool any = false;
-    // Chained launch (fused step only): the PnP role follows the LK role of the SAME launch frame by frame through arrival
-    // counters (agt_step.hip pnp_role), instead of one launch behind it.
-    const bool chain = agt_step_fits(c->trk_n, B);
-    // stage 0 builds levels 1 and 2 in one pass (stage 1 then only keeps the books): always while the batch is small (tiled or
-    // register-rolling two-level pass), for big batches where the rolling form applies to every frame of the launch (decided below,
-    // in the s = 0 trip) and stage 1 has no backlog from an earlier launch that ran the levels as two passes
-    bool fused = L >= 2 && B <= AGT_PYR2_MAX_B;
-    // a launch that will carry pyramid work ONLY (the first one of a run: no frame is ready for the LK role, none for the pose role)
-    // goes out as the pyramid kernel proper (below), which has the register-rolling two-level pass -- the fused step kernel has not
-    const bool pyr_only = c->n_lk >= done_before[L] && c->n_pnp >= c->n_lk;
-    for (int s = 0; s < L; s++) {
-        if (fused && s == 1) continue;
-        long cnt = done_before[s] - c->n_stage[s];
-        if (cnt <= 0) continue;
-        if (cnt > F) cnt = F;
-        AgtPyrArgs& A = S.pyr[s];
-        A.sw = c->lw[s]; A.sh = c->lh[s];
-        A.dw = c->lw[s + 1]; A.dh = c->lh[s + 1];
-        A.dpitch = c->lpitch[s + 1]; A.dbatch = (long)c->lh[s + 1] * c->lpitch[s + 1];
-        A.B = B;
-        uintptr_t src_align = 0, dst_align = 0;
-        for (long k = 0; k < cnt; k++) {
-            const int slot = (int)((c->n_stage[s] + 1 + k) % M);
-            if (s == 0) {
-                // level 0 is the caller's frame: the frames of a group must share pitch and stream stride
-                if (k == 0) { A.spitch = c->l0_pitch[slot]; A.sbatch = c->l0_bstride[slot]; }
-                else if (A.spitch != c->l0_pitch[slot] || A.sbatch != c->l0_bstride[slot]) { cnt = k; break; }
-                T.pyr_src[s][k] = c->l0_ptr[slot];
-            } else {
-                A.spitch = c->lpitch[s]; A.sbatch = (long)c->lh[s] * c->lpitch[s];
-                T.pyr_src[s][k] = c->lmem[slot][s];
-            }
-            T.pyr_dst[s][k] = c->lmem[slot][s + 1];
-            src_align |= (uintptr_t)T.pyr_src[s][k]; dst_align |= (uintptr_t)T.pyr_dst[s][k];
-        }
-        A.src = T.pyr_src[s][0]; A.dst = T.pyr_dst[s][0];
-        agt_pyr_plan(&A, src_align, dst_align, (int)cnt);          // tiled or register-rolling form (A.pad), workgroups per image in A.gx * A.gy
-        if (s == 0 && L >= 2) {
-            // the level 1 -> 2 geometry and buffers ride in stage 1's slots; the pass's grid in A: 64 x 16 tiles of level 2 (tiled
-            // form) or workgroups per image with the strip height in A.pad (register-rolling form, agt_pyramid4_body.h)
-            AgtPyrArgs A0 = A, A1 = S.pyr[1];
-            A1.sw = c->lw[1]; A1.sh = c->lh[1]; A1.dw = c->lw[2]; A1.dh = c->lh[2];
-            A1.spitch = c->lpitch[1]; A1.sbatch = (long)c->lh[1] * c->lpitch[1];
-            A1.dpitch = c->lpitch[2]; A1.dbatch = (long)c->lh[2] * c->lpitch[2];
-            A1.B = B; A1.src = nullptr; A1.dst = nullptr;
-            uintptr_t d2_align = 0;
-            for (long k = 0; k < cnt; k++) d2_align |= (uintptr_t)c->lmem[(int)((c->n_stage[0] + 1 + k) % M)][2];
-            // (fused step: agt_step_fits, <= 256 corners in flight -- its kernel carries the tiled two-level pass only: plan as ONE frame, which
-            // keeps the launch below the rolling form's 16 images.  Round 5: except the pyramid-only launch at the head of a run, which is
-            // pyr_group_kernel -- 20 frames of 1280x720, the driver's block: 15.1 us tiled, see DESIGN.md section 6 for the rolling figure)
-            agt_pyr2_plan(&A0, &A1, src_align, dst_align | d2_align, (agt_step_fits(c->trk_n, B) && !pyr_only) ? 1 : (int)cnt,
-                          (agt_step_fits(c->trk_n, B) || B < AGT_SPLIT_PYR_OH_B0 || B > AGT_SPLIT_PYR_OH_B1) ? 16 : AGT_SPLIT_PYR_OH);
-            if (!fused && A0.pad != 0 && c->n_stage[1] == c->n_stage[0]) fused = true;       // big batch, rolling form, no backlog
-            if (fused) {
-                A = A0; S.pyr[1] = A1;
-                for (long k = 0; k < cnt; k++) T.pyr_dst[1][k] = c->lmem[(int)((c->n_stage[0] + 1 + k) % M)][2];
-                c->n_stage[1] += cnt;            // (same frames: level 2 is complete when level 1 is)
-            }
-        }
-        S.pyr_nf[s] = (int)cnt;
-        S.n_pyr[s] = A.gx * A.gy * B * (int)cnt;
-        c->n_stage[s] += cnt;
-        any = true;
-    }
-    S.pyr_fused = fused ? 1 : 0;
-    if (c->n_lk < done_before[L]) {
-        long cnt = done_before[L] - c->n_lk;
-        if (cnt > F) cnt = F;
-        const long f0 = c->n_lk;                 // the frame before the group
-        lk_f0 = f0;
-        // level 0 geometry comes from the frame's own registration; a group needs it uniform
-        for (long k = 1; k <= cnt; k++) {
-            const int a = (int)(f0 % M), q = (int)((f0 + k) % M);
-            if (c->l0_pitch[q] != c->l0_pitch[a] || c->l0_bstride[q] != c->l0_bstride[a]) { cnt = k > 1 ? k - 1 : 1; break; }
-        }
-        const int pslot = (int)(f0 % M), slot = (int)((f0 + 1) % M);
-        fill_lk(c, &S.lk, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
-                AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
-        S.lk_nf = (int)cnt;
-        for (long k = 0; k <= cnt; k++) {
-            const int q = (int)((f0 + k) % M);
-            for (int l = 0; l <= L; l++) T.lk.img[k][l] = l == 0 ? c->l0_ptr[q] : c->lmem[q][l];
-            if (k) { T.lk.next[k - 1] = c->corners[q]; T.lk.status[k - 1] = c->status[q]; }     // (arrival counters: attached below)
-        }
-        S.n_lk = 1; S.lk_B = B;
-        c->n_lk += cnt;
-        any = true;
-    }
-    // frames the PnP role may take: everything tracked before this launch; chained, also the frames tracked BY it, waiting
-    // for each one's counter -- all of them when nothing more is registered (a drain: the last frames' latency counts), all
-    // but the newest while frames keep coming (the role then never stalls: the LK role works one frame ahead of it)
-    long pnp_avail = lk_before;
-    if (chain) pnp_avail = c->n_lk - (c->n_lk < c->trk_frame && c->n_lk > lk_before ? 1 : 0);
-    if (c->n_pnp < pnp_avail) {
-        long cnt = pnp_avail - c->n_pnp;
-        if (cnt > F) cnt = F;
-        const int slot = (int)((c->n_pnp + 1) % M);
-        fill_estimate(c, &S.pnp, c->corners[slot], c->status[slot], c->so_ring[slot], nullptr);
-        arm_host_seq(c, &S.pnp, c->n_pnp + 1);
-        for (long k = 0; k < cnt; k++) {
-            const long f = c->n_pnp + 1 + k;
-            const int q = (int)(f % M);
-            T.pnp.img[k] = c->corners[q]; T.pnp.mask[k] = c->status[q]; T.pnp.so[k] = c->so_ring[q];
-            if (f > lk_before) {
-                // tracked by this launch: the LK role counts the frame's corners in (device-scope stores + acknowledgement, only
-                // for the frames somebody waits for), the PnP wave waits for the count
-                c->lk_target[q] += (unsigned)c->trk_n;
-                T.lk.done[f - lk_f0 - 1] = c->lk_done + (size_t)q * c->cfg.max_streams;
-                T.pnp.wait[k] = T.lk.done[f - lk_f0 - 1]; T.pnp.target[k] = c->lk_target[q];
-            }
-        }
-        S.pnp_nf = (int)cnt;
-        S.n_pnp = B;
-        c->n_pnp += cnt;
-        any = true;
-        // knobs: AGT_CHAIN_WITHHOLD=k makes the k-th launch with chained waits expect one arrival more than its LK role delivers for the
-        // SECOND waited frame (the first if there is only one): tests/test_gpu_tracker.py drives the give-up path with it
-        if (const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD", 0)) {
-            static long seen = 0;
-            int waited[2] = { -1, -1 }, nw = 0;
-            for (long k = 0; k < cnt && nw < 2; k++) if (T.pnp.wait[k]) waited[nw++] = (int)k;
-            if (wh > 0 && nw > 0 && ++seen == wh) T.pnp.target[waited[nw - 1]] += 1;
-        }
-    }
-    if (!any) return AGT_OK;
-    // knobs: AGT_TABLE_POISON_PNP=k / AGT_TABLE_POISON_LK=k put a word that cannot be an address (the bits of a NaN) into the second
-    // frame's entry of the k-th launch whose pose / LK role runs more than one frame -- what a stale or clobbered LDS table would hand
-    // the role.  tests/test_gpu_tracker.py: the launch must drain, flag and report, not fault.
-    {
-        const long pk = AGT_KNOB("AGT_TABLE_POISON_PNP", 0), lk = AGT_KNOB("AGT_TABLE_POISON_LK", 0);
-        static long seen_p = 0, seen_l = 0;
-        if (pk > 0 && S.pnp_nf > 1 && ++seen_p == pk) T.pnp.img[1] = (const float*)0x7ff8dead00000000ull;
-        if (lk > 0 && S.lk_nf > 1 && ++seen_l == lk) T.lk.img[2][0] = (const uint8_t*)0x7ff8dead00000000ull;
-    }
-    if (agt_step_fits(c->trk_n, B)) {
-        // a launch with pyramid work only (the first one of a run) goes out as the pyramid kernel proper: eight workgroups per
-        // CU instead of the one the fused kernel's register budget leaves (16 frames of 720p: ~7 us instead of ~12)
-        const int roles = (S.n_lk > 0 || S.n_pnp > 0) ? AGT_STEP_ALL : AGT_STEP_PYR;
-        hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, roles);
-        return e == hipSuccess ? AGT_OK : hip_fail(c, e);
-    }
-    // ---- split mode: the same group as three launches, one per role, each with its own LDS size and register budget:
-    // pyramid on the caller's stream (the frames come from there), LK and PnP on two library streams.  The roles of one
-    // group are independent (the pipeline skews them across frames), so the three launches overlap; ordering is by events:
-    //   LK(k)  waits for pyramid(k-1)   (its images)          and for PnP(k-2)  (ring reuse of corner / status entries)
-    //   PnP(k) waits for LK(k-1)        (its corners)
-    //   pyramid(k) waits for LK(k-3)    (ring reuse of level entries: split mode keeps AGT_SPLIT_SLACK = 2 groups of extra
-    //                                    ring entries, so the HBM-bound pyramid launches run AHEAD of the LK launches they share
-    //                                    the chip with and never sit on the critical path; the wait also keeps the caller's
-    //                                    stream behind the readers of frames handed over (L + 6) groups ago, so stream-ordered
-    //                                    allocators may recycle those)
-    // Ten HIP calls per GROUP of F frames (round 1 issued thirteen per frame).
-    int rc = ms_init(c);
-    if (rc) return rc;
-    hipStream_t sL = c->ms_stream[1], sL2 = c->ms_stream[0], sY = c->ms_stream[2];
-    hipEvent_t *evP = c->ms_ev[0], *evL = c->ms_ev[1], *evY = c->ms_ev[3], *evL2 = c->ms_ev[4];
-    // The per-frame LK launches of a group depend on each other (a corner starts where it ended), leave ~4 us between one
-    // kernel's end and the next one's start on their stream, and each lasts as long as its slowest corner.  A batch of the
-    // one-wave-per-corner kernel whose halves still hold >= 512 corners goes out as two launches per frame on two streams,
-    // streams [0, B1) and [B1, B), both with the one-wave kernel: each half's gaps and tails are filled by the other half's
-    // kernel.  Every wait on / record of the LK role below is done for both streams.  (Round 3: the halves used to be taken
-    // only from 44 streams of 48 corners on; 22 .. 43 streams gain 12-20 % -- 42 streams 43.9 -> 36.6 us per step.  Four
-    // quarters on four streams lose badly -- 64 streams 160 us, 86 with GPU_MAX_HW_QUEUES=8 against 49.7: more streams than
-    // hardware queues, and four kernels of <= 1 wave per SIMD each stretch one another.)
-    const int B1 = (!agt_lk_wide(c->trk_n, B) && (long)c->trk_n * (B / 2) >= 512) ? B / 2 : B;
-    const bool two = B1 < B;
-    // A role's n-th launch records event slot n % AGT_EV_SLOTS, so the slot a wait names (at most three launches of its role old) is not
-    // re-recorded before it.  (The slots used to follow the group count: a role that sat groups out could wait on a slot that a NEWER
-    // launch of the same role and stream had re-recorded -- later completion, so that could only over-synchronise.)
-    const int p_slot = (int)(c->split_n[0] % AGT_EV_SLOTS), l_slot = (int)(c->split_n[1] % AGT_EV_SLOTS), y_slot = (int)(c->split_n[2] % AGT_EV_SLOTS);
-    bool p_work = false;
-    for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) p_work |= S.n_pyr[s] > 0;
-    const int p_before = c->last_p_ev, l_before = c->l_ev_hist[0];
-    hipError_t e = hipSuccess;
-    if (p_work) {
-        if (c->l_ev_hist[AGT_SPLIT_SLACK] >= 0) {
-            e = hipStreamWaitEvent(c->stream, evL[c->l_ev_hist[AGT_SPLIT_SLACK]], 0);
-            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, evL2[c->l_ev_hist[AGT_SPLIT_SLACK]], 0);
-        }
-        if (e == hipSuccess) e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
-        if (e == hipSuccess) e = hipEventRecord(evP[p_slot], c->stream);
-        if (e != hipSuccess) return hip_fail(c, e);
-        c->last_p_ev = p_slot; c->split_n[0]++;
-    }
-    if (S.n_lk > 0) {
-        hipEvent_t first = nullptr;
-        if (p_before >= 0) first = evP[p_before];
-        else {
-            // no pyramid launch since the last join (single-level pyramids, or the first LK of a run): order the LK streams
-            // behind the caller's stream explicitly (reset's corner copy, earlier modes' pyramids)
-            e = hipEventRecord(c->ms_ev[2][2], c->stream);
-            first = c->ms_ev[2][2];
-        }
-        for (int h = 0; h < (two ? 2 : 1) && e == hipSuccess; h++) {
-            hipStream_t sh = h ? sL2 : sL;
-            e = hipStreamWaitEvent(sh, first, 0);
-            if (e == hipSuccess && c->y_ev_hist[1] >= 0) e = hipStreamWaitEvent(sh, evY[c->y_ev_hist[1]], 0);
-        }
-        if (e != hipSuccess) return hip_fail(c, e);
-        // Up to 1024 corners in flight (the four-waves-per-corner body): the LK role of the WHOLE group as one launch --
-        // lk_group_kernel, the frame-chained body of the fused step with its own register budget (153 VGPRs, three workgroups
-        // per CU) -- instead of one ~17 us launch + ~5 us gap per frame (round 3: 16 streams 33.9 -> see profiles/r03_stream_sweep.txt).
-        const bool lk_group = agt_lk_wide(c->trk_n, B);
-        if (lk_group) {
-            e = agt_launch_step(sL, S, T, c->cfg.win, AGT_STEP_LK);
-            if (e != hipSuccess) return hip_fail(c, e);
-        }
-        // otherwise one stand-alone LK launch per frame of the group (and half), back to back on its stream (as a role with an in-kernel
-        // frame loop the one-wave-per-corner kernel needs 240 B of scratch per lane at its 128-register budget and runs at half speed)
-        for (int k = 1; k <= S.lk_nf && !lk_group; k++) {
-            const int ps = (int)((lk_f0 + k - 1) % M), sl = (int)((lk_f0 + k) % M);
-            // (waves = 1: a half is sized by the whole batch's kernel choice, not by its own corner count)
-            rc = lk_track_on(c, sL, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B1,
-                             AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, 0, two ? 1 : 0);
-            if (rc == AGT_OK && two)
-                rc = lk_track_on(c, sL2, ps, sl, c->corners[ps], c->status[ps], c->corners[sl], c->status[sl], nullptr, c->trk_n, B - B1,
-                                 AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, B1, 1);
-            if (rc) return rc;
-        }
-        e = hipEventRecord(evL[l_slot], sL);
-        // (recorded on the second stream in any case: an idle stream's event is complete at once, the waits stay uniform)
-        if (e == hipSuccess) e = hipEventRecord(evL2[l_slot], two ? sL2 : sL);
-        if (e != hipSuccess) return hip_fail(c, e);
-        c->l_ev_hist[2] = c->l_ev_hist[1]; c->l_ev_hist[1] = c->l_ev_hist[0]; c->l_ev_hist[0] = l_slot; c->split_n[1]++;
-        c->ms_active = 1;
-    }
-    if (S.n_pnp > 0) {
-        if (l_before >= 0) {
-            e = hipStreamWaitEvent(sY, evL[l_before], 0);
-            if (e == hipSuccess) e = hipStreamWaitEvent(sY, evL2[l_before], 0);
-        }
-        if (e == hipSuccess) e = agt_launch_step(sY, S, T, c->cfg.win, AGT_STEP_PNP);
-        if (e == hipSuccess) e = hipEventRecord(evY[y_slot], sY);
-        if (e != hipSuccess) return hip_fail(c, e);
-        c->y_ev_hist[1] = c->y_ev_hist[0]; c->y_ev_hist[0] = y_slot; c->split_n[2]++;
-        c->ms_active = 1;
-    }
-    return AGT_OK;
+    const bool pyr_work = plan_pyramid(c, G, S, T);
+    const long lk_after = plan_lk(c, G, S, T);
+    plan_pose(c, G, lk_after, S, T);
+    if (!pyr_work && S.n_lk == 0 && S.n_pnp == 0) return AGT_OK;
+    debug_inject(S, T);
+    return G.fits ? issue_fused(c, S, T) : issue_split(c, G, S, T);
 }
 
-// The part of registering frame T+1 that comes before the registration itself: ring modulus of the mode, a free ring entry.
-static int pipelined_entry(agt_ctx* c, int B)
+// The part of registering frame T+1 that comes before the registration itself: ring modulus of the mode (fits: agt_step_fits of the
+// batch, the fused form; otherwise the split one), a free ring entry.
+static int pipelined_entry(agt_ctx* c, int B, bool fits)
 {
     c->prebuilt_t = -1;
     // ring modulus of this mode: (L + 2) groups, plus the split mode's slack when the entries are available
-    {
-        const bool split = !agt_step_fits(c->trk_n, B);
-        int groups = c->eff_max_level + 2 + (split ? AGT_SPLIT_SLACK : 0);
-        if (groups * c->group > AGT_RING_MAX) groups = c->eff_max_level + 2;
-        const int want = groups * c->group > AGT_SLOTS ? groups * c->group : AGT_SLOTS;
-        if (want != c->live_ring) {
-            int rc = join_pipeline(c);            // only the newest frame is live afterwards
-            if (rc) return rc;
-            rc = ensure_ring(c, want);
-            if (rc) return rc;
-            ring_move(c, c->trk_frame, c->live_ring, want);
-            c->live_ring = want;
-        }
+    int groups = c->eff_max_level + 2 + (fits ? 0 : AGT_SPLIT_SLACK);
+    if (groups * c->group > AGT_RING_MAX) groups = c->eff_max_level + 2;
+    const int want = groups * c->group > AGT_SLOTS ? groups * c->group : AGT_SLOTS;
+    if (want != c->live_ring) {
+        int rc = join_pipeline(c);            // only the newest frame is live afterwards
+        if (rc) return rc;
+        rc = ensure_ring(c, want);
+        if (rc) return rc;
+        ring_move(c, c->trk_frame, c->live_ring, want);
+        c->live_ring = want;
     }
-    const long t = c->trk_frame + 1;
     // The ring entry frame t takes must be free: its previous tenant, frame t - M, has to be past its pose solve and past the
     // LK of the frame after it (which reads it as the previous image).  The ring size follows from every stage advancing F
     // frames per launch; groups cut short (frames of differing pitch) let stages fall behind that rhythm.
-    {
-        const long M = c->live_ring;
-        while (c->n_pnp < t - M || c->n_lk < t - M + 1) {
-            const long before = c->n_pnp + c->n_lk + c->n_stage[0];
-            int rc = launch_group(c, B);
-            if (rc) return rc;
-            if (c->n_pnp + c->n_lk + c->n_stage[0] == before) return AGT_ERR_STATE;      // (cannot happen: work was pending)
-        }
+    const long t = c->trk_frame + 1, M = c->live_ring;
+    while (c->n_pnp < t - M || c->n_lk < t - M + 1) {
+        const long before = c->n_pnp + c->n_lk + c->n_stage[0];
+        int rc = launch_group(c, B);
+        if (rc) return rc;
+        if (c->n_pnp + c->n_lk + c->n_stage[0] == before) return AGT_ERR_STATE;      // (cannot happen: work was pending)
     }
     return AGT_OK;
 }
@@ -587,16 +700,14 @@ static int pipelined_entry(agt_ctx* c, int B)
 // Register frame T+1 of the fused pipeline; a launch goes out once `group` frames wait for their first stage.
 static int step_pipelined(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B, double* d_state_out)
 {
-    int rc = pipelined_entry(c, B);
+    const bool fits = agt_step_fits(c->trk_n, B);
+    int rc = pipelined_entry(c, B, fits);
     if (rc) return rc;
     const long t = c->trk_frame + 1;
-    const int slot = (int)(t % c->live_ring);
-    c->l0_ptr[slot] = d_frames; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
-    c->built_B[slot] = B;
-    c->so_ring[slot] = d_state_out;
+    register_frame(c, ring_slot(c, t), d_frames, pitch, batch_stride, B, d_state_out);
     c->trk_frame = t;
     const long first_done = c->eff_max_level > 0 ? c->n_stage[0] : c->n_lk;
-    if (agt_step_fits(c->trk_n, B)) {
+    if (fits) {
         if (t - first_done < c->group) return AGT_OK;
         return launch_group(c, B);
     }
@@ -612,22 +723,20 @@ static int step_pipelined(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
 // two-level register-rolling pass reads the frame over PCIe, stores its level 0 to d_gray and levels 1 / 2 to the frame's ring
 // entry (agt_pyramid.hip agt_launch_pyr_upload2) -- and the frame is registered with its pyramid stages done; the LK | PnP launch
 // follows at the join as ever.  Returns 1 when the form does not apply (geometry, pyramid work of earlier frames still pending):
-// nothing has been enqueued for the frame then and the caller copies and calls agt_track_frame.
+// nothing has been enqueued for the frame then and the caller copies and calls agt_track_frame.  (The caller has checked agt_step_fits.)
 static int step_pipelined_uploaded(agt_ctx* c, const uint8_t* h_dev, uint8_t* d_gray, size_t gpitch, double* d_state_out)
 {
     if (c->eff_max_level != 2 || c->trk_B != 1) return 1;
-    int rc = pipelined_entry(c, 1);
+    int rc = pipelined_entry(c, 1, true);
     if (rc) return rc;
     const long t = c->trk_frame + 1;
     if (c->n_stage[0] != t - 1 || c->n_stage[1] != t - 1) return 1;
-    const int slot = (int)(t % c->live_ring);
+    const int slot = ring_slot(c, t);
     const int W = c->cfg.width, H = c->cfg.height;
     hipError_t e = agt_launch_pyr_upload2(c->stream, h_dev, W, H, (long)W, d_gray, (long)gpitch, c->lmem[slot][1], c->lpitch[1], c->lmem[slot][2], c->lpitch[2]);
     if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return 1; }
     if (e != hipSuccess) return hip_fail(c, e);
-    c->l0_ptr[slot] = d_gray; c->l0_pitch[slot] = (long)gpitch; c->l0_bstride[slot] = (long)gpitch * H;
-    c->built_B[slot] = 1;
-    c->so_ring[slot] = d_state_out;
+    register_frame(c, slot, d_gray, gpitch, gpitch * (size_t)H, 1, d_state_out);
     c->trk_frame = t;
     c->n_stage[0] = c->n_stage[1] = t;
     return AGT_OK;
@@ -672,18 +781,104 @@ int agt_estimate_pose(agt_ctx* c, const float* d_img, const uint8_t* d_mask, int
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
-// pyrDown.. -> LK -> PnP (+ dense stage) as launches on the context's stream: pose complete in stream order.
+// ---- The serial step: pyrDown.. -> LK -> PnP (+ dense stage) as launches on the context's stream, pose complete in stream order.
 // next_frame != null (clip submission with the dense stage): the caller will hand that frame in next, with the same pitch and
 // stream stride -- its two-level pyramid pass rides in one of this frame's launches (the chained LK | PnP launch, the four-wave PnP
 // launch, or the second dense launch) instead of being the first launch of its own chain, and this frame's last dense step is left
 // to that frame's LK launch (c->dense_pending).
+
+// The launch form of one serial frame, decided (serial_form) before anything of it is issued.
+struct SerialForm {
+    bool lk_role_launch;         // LK as the LK role of the step, a one-frame group, instead of the stand-alone LK launch
+    bool ride;                   // the next frame's two-level pyramid pass rides in one of this frame's launches: ...
+    bool chain_pnp;              // ... LK and PnP of the frame in ONE launch, which then carries the ride as well
+    bool ride_pnp;               // ... the ride in the PnP launch (otherwise, and unchained: in the dense stage's second launch)
+    bool defer;                  // the dense stage's last step is left to the NEXT frame's LK launch
+};
+
+// dense: the frame runs the dense stage; spans: stage spans are being recorded (agt_profile_begin)
+static SerialForm serial_form(const agt_ctx* c, int pslot, int slot, int nslot, size_t pitch, size_t batch_stride, int B,
+                              bool dense, bool spans, const uint8_t* next_frame)
+{
+    SerialForm f;
+    const bool dense_iters = dense && c->dn_iters > 0;
+    // four waves per corner: the LK role of the step as a one-frame group (the frame-chained body; see agt_step.hip lk_role)
+    const bool wide = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
+    f.lk_role_launch = wide && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
+    // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
+    // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
+    // (Measured on configs[4], us per frame: no ride 89.0; in the PnP launch 84.0-84.5; in the dense launch 84.0-85.3; in the LK
+    // launch 84.5-84.8 as tiles behind the LK role launch's own workgroups, 86.5 as the pyramid role of the fused step kernel.)
+    f.ride = next_frame && c->eff_max_level == 2 && B <= AGT_PYR2_MAX_B && nslot != slot && nslot < c->ring &&
+             ((uintptr_t)next_frame & 3) == 0 && (agt_pnp_can_ride(c->trk_n) || dense_iters);
+    // Dense clips with the cooperative solver (64 < n <= 256): LK and PnP of the frame in ONE launch, the solver waiting for the
+    // frame's arrival count (agt_step.hip lk_pnp_coop_kernel); the next frame's pyramid pass then rides in that launch as well
+    // (while trackers + solvers are co-resident at the one workgroup per CU the solver's registers leave: more streams keep the LK
+    // launch of its own, whose 78 registers put several workgroups on a CU)
+    // (the LK role's grid is rounded up to a multiple of 8; the device's CU count, not a literal: ADVICE r4)
+    f.chain_pnp = f.lk_role_launch && dense_iters && !spans && agt_pnp_can_ride(c->trk_n) &&
+                  (long)agt_xcd_grid((long)c->trk_n * B, 3) + B <= c->chip.cus;
+    f.ride_pnp = f.ride && agt_pnp_can_ride(c->trk_n) && !f.chain_pnp;
+    // Clip submission: the stage's last step (final update + re-seed, a one-workgroup launch of 5.5 us) is left to the NEXT
+    // frame's LK launch, whose workgroups do it as their prologue (agt_step.hip lk_reseed_kernel) -- when that launch will be the
+    // four-waves-per-corner LK role launch (same geometry as this frame's) and no stage spans are being recorded
+    f.defer = next_frame && !spans && dense_iters && wide;
+    return f;
+}
+
+// LK of frame t as the one-frame LK role launch; chained, the pose solve `p` in the same launch.  Unlike launch_group, whose plans
+// advance the context's counters while they fill the tables, the arrival target (lk_target) and dense_pending change here only once
+// the launch is known to be out: this form has an error path (agt_track_frames_dense), and a failed launch must leave the counters'
+// bookkeeping and the deferred dense step as they were.
+static int serial_lk_role(agt_ctx* c, const SerialForm& f, const AgtPnpParams& p, long t, int B, const AgtPyrArgs* npyr)
+{
+    const int slot = ring_slot(c, t);
+    AgtStepParams S; AgtStepTables T;
+    memset(&S, 0, sizeof(S)); memset(&T, 0, sizeof(T));
+    fill_tracker_lk(c, &S.lk, ring_slot(c, t - 1), slot);
+    fill_lk_table(c, T.lk, t - 1, 1);
+    S.lk_nf = 1; S.n_lk = 1; S.lk_B = B;
+    if (f.chain_pnp) {
+        S.pnp = p; S.pnp_nf = 1; S.n_pnp = B;
+        T.lk.done[0] = c->lk_done + (size_t)slot * c->cfg.max_streams;
+        T.pnp.img[0] = c->corners[slot]; T.pnp.mask[0] = c->status[slot]; T.pnp.so[0] = p.state_out;
+        T.pnp.wait[0] = T.lk.done[0]; T.pnp.target[0] = c->lk_target[slot] + (unsigned)c->trk_n;
+        // knobs: AGT_CHAIN_WITHHOLD_DENSE=k makes the k-th chained LK | PnP launch of the dense tracker expect one arrival more than
+        // its LK role delivers (tests/test_dense.py drives the solver's give-up path with it)
+        { const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD_DENSE", 0); static long seen = 0; if (wh > 0 && ++seen == wh) T.pnp.target[0] += 1; }
+    }
+    hipError_t e;
+    if (c->dense_pending || f.chain_pnp) {
+        e = agt_launch_lk_reseed(c->stream, S, T, c->cfg.win, c->dense_pending ? &c->dense_final : nullptr, (f.ride && f.chain_pnp) ? npyr : nullptr);
+        if (e == hipSuccess) {                  // on failure dense_pending stays set: the caller's error path flushes it (agt_launch_dense_final)
+            c->dense_pending = 0;
+            if (f.chain_pnp) c->lk_target[slot] += (unsigned)c->trk_n;
+        }
+    } else e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_LK);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// dense photometric + geometric refinement of the frame's accepted pose, then (reseed) the corner set from it
+static int serial_dense(agt_ctx* c, const SerialForm& f, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int slot, int B,
+                        double* d_dense_out, hipEvent_t* pev, const AgtPyrArgs* npyr)
+{
+    hipError_t e = agt_launch_dense(c->stream, d_frames, (long)pitch, (long)batch_stride, c->cfg.width, c->cfg.height, c->dn_xyz, c->dn_t, c->dn_M,
+                                    c->obj, c->corners[slot], c->status[slot], c->trk_n, c->cam, c->pose, c->dense_partials, nullptr,
+                                    c->dense_done, B, c->dn_iters, c->dn_weight, 1e-3, d_dense_out, c->dn_reseed ? c->corners[slot] : nullptr,
+                                    c->dn_reseed ? c->status[slot] : nullptr, pev ? pev + 4 : nullptr, 2 * AGT_PROF_DENSE_MAX,
+                                    (f.ride && !f.ride_pnp && !f.chain_pnp) ? npyr : nullptr, f.defer ? &c->dense_final : nullptr);
+    if (e == hipSuccess && f.defer) c->dense_pending = 1;
+    if (pev) c->prof_dense[c->prof_n - 1] = c->dn_iters < AGT_PROF_DENSE_MAX ? c->dn_iters : AGT_PROF_DENSE_MAX;
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
 static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B,
                        double* d_state_out, double* d_dense_out, hipEvent_t* pev, const uint8_t* next_frame = nullptr)
 {
     int rc = join_pipeline(c);            // a mode switch drains the pipeline first
     if (rc) return rc;
     const long t = c->trk_frame + 1;
-    const int slot = (int)(t % c->live_ring), pslot = (int)((t - 1) % c->live_ring);
+    const int slot = ring_slot(c, t), pslot = ring_slot(c, t - 1), nslot = ring_slot(c, t + 1);
     hipStream_t M = c->stream;
     if (pev) (void)hipEventRecord(pev[0], M);
     const bool prebuilt = c->prebuilt_t == t && c->l0_ptr[slot] == d_frames && c->l0_pitch[slot] == (long)pitch &&
@@ -692,30 +887,14 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
     rc = prebuilt ? AGT_OK : pyramid_build_on(c, M, slot, d_frames, pitch, batch_stride, B);
     if (rc) return rc;
     if (pev) (void)hipEventRecord(pev[1], M);
-    // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
-    // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
-    // (Measured on configs[4], us per frame: no ride 89.0; in the PnP launch 84.0-84.5; in the dense launch 84.0-85.3; in the LK
-    // launch 84.5-84.8 as tiles behind the LK role launch's own workgroups, 86.5 as the pyramid role of the fused step kernel.)
+    const SerialForm f = serial_form(c, pslot, slot, nslot, pitch, batch_stride, B, d_dense_out != nullptr, pev != nullptr, next_frame);
     AgtPyrArgs npyr[2];
-    const int nslot = (int)((t + 1) % c->live_ring);
-    const bool lk_role_launch = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B) && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
-    const bool ride = next_frame && c->eff_max_level == 2 && B <= AGT_PYR2_MAX_B && nslot != slot && nslot < c->ring &&
-                      ((uintptr_t)next_frame & 3) == 0 && (agt_pnp_can_ride(c->trk_n) || (d_dense_out && c->dn_iters > 0));
-    // Dense clips with the cooperative solver (64 < n <= 256): LK and PnP of the frame in ONE launch, the solver waiting for the
-    // frame's arrival count (agt_step.hip lk_pnp_coop_kernel); the next frame's pyramid pass then rides in that launch as well
-    // (while trackers + solvers are co-resident at the one workgroup per CU the solver's registers leave: more streams keep the LK
-    // launch of its own, whose 78 registers put several workgroups on a CU)
-    // (the LK role's grid is rounded up to a multiple of 8; the device's CU count, not a literal: ADVICE r4)
-    const bool chain_pnp = lk_role_launch && d_dense_out && c->dn_iters > 0 && !pev && agt_pnp_can_ride(c->trk_n) &&
-                           (long)agt_xcd_grid((long)c->trk_n * B, 3) + B <= c->chip.cus;
-    const bool ride_pnp = ride && agt_pnp_can_ride(c->trk_n) && !chain_pnp;
-    if (ride) {
-        // (what pyramid_build_on registers for a frame, for frame t + 1 in its ring entry)
-        c->l0_ptr[nslot] = next_frame; c->l0_pitch[nslot] = (long)pitch; c->l0_bstride[nslot] = (long)batch_stride;
+    if (f.ride) {
+        // frame t + 1 in its ring entry, as pyramid_build_on would leave it (the serial step reads no state_out from the ring)
+        register_frame(c, nslot, next_frame, pitch, batch_stride, B, nullptr);
         const long db1 = (long)c->lh[1] * c->lpitch[1], db2 = (long)c->lh[2] * c->lpitch[2];
         agt_pyr2_args(next_frame, c->lw[0], c->lh[0], (long)pitch, (long)batch_stride, c->lmem[nslot][1], c->lpitch[1], db1,
                       c->lmem[nslot][2], c->lpitch[2], db2, B, &npyr[0], &npyr[1]);
-        c->built_B[nslot] = B;
         c->prebuilt_t = t + 1;
     }
     AgtPnpParams p;
@@ -726,69 +905,23 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
         if (rc) return rc;
         p.dense_pose = c->pose; p.dense_done = c->dense_done; p.dense_rec = d_dense_out;
     }
-    if (lk_role_launch) {
-        // four waves per corner: the LK role of the step as a one-frame group (the frame-chained body; see agt_step.hip lk_role)
-        AgtStepParams S; AgtStepTables T;
-        memset(&S, 0, sizeof(S)); memset(&T, 0, sizeof(T));
-        fill_lk(c, &S.lk, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
-                AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
-        S.lk_nf = 1; S.n_lk = 1; S.lk_B = B;
-        for (int k = 0; k < 2; k++) {
-            const int q = k ? slot : pslot;
-            for (int l = 0; l <= c->eff_max_level; l++) T.lk.img[k][l] = l == 0 ? c->l0_ptr[q] : c->lmem[q][l];
+    if (f.lk_role_launch) rc = serial_lk_role(c, f, p, t, B, npyr);
+    else {
+        if (c->dense_pending) {          // (cannot happen: the deferral is decided with this frame's launch form known)
+            c->dense_pending = 0;
+            hipError_t e = agt_launch_dense_final(M, c->dense_final, B);
+            if (e != hipSuccess) return hip_fail(c, e);
         }
-        T.lk.next[0] = c->corners[slot]; T.lk.status[0] = c->status[slot];
-        hipError_t e;
-        if (chain_pnp) {
-            S.pnp = p; S.pnp_nf = 1; S.n_pnp = B;
-            // (the slot's arrival target advances only once the launch is known to be out: ADVICE r4 -- a failed launch must leave
-            // the counters' bookkeeping and the deferred dense step as they were)
-            T.lk.done[0] = c->lk_done + (size_t)slot * c->cfg.max_streams;
-            T.pnp.img[0] = c->corners[slot]; T.pnp.mask[0] = c->status[slot]; T.pnp.so[0] = d_state_out;
-            T.pnp.wait[0] = T.lk.done[0]; T.pnp.target[0] = c->lk_target[slot] + (unsigned)c->trk_n;
-            // knobs: AGT_CHAIN_WITHHOLD_DENSE=k makes the k-th chained LK | PnP launch of the dense tracker expect one arrival more than
-            // its LK role delivers (tests/test_dense.py drives the solver's give-up path with it)
-            { const long wh = AGT_KNOB("AGT_CHAIN_WITHHOLD_DENSE", 0); static long seen = 0; if (wh > 0 && ++seen == wh) T.pnp.target[0] += 1; }
-        }
-        if (c->dense_pending || chain_pnp) {
-            e = agt_launch_lk_reseed(M, S, T, c->cfg.win, c->dense_pending ? &c->dense_final : nullptr, (ride && chain_pnp) ? npyr : nullptr);
-            if (e == hipSuccess) {                  // on failure dense_pending stays set: the caller's error path flushes it (agt_launch_dense_final)
-                c->dense_pending = 0;
-                if (chain_pnp) c->lk_target[slot] += (unsigned)c->trk_n;
-            }
-        } else e = agt_launch_step(M, S, T, c->cfg.win, AGT_STEP_LK);
-        if (e != hipSuccess) return hip_fail(c, e);
-    } else {
-    if (c->dense_pending) {          // (cannot happen: the deferral is decided with this frame's launch form known)
-        c->dense_pending = 0;
-        hipError_t e = agt_launch_dense_final(M, c->dense_final, B);
-        if (e != hipSuccess) return hip_fail(c, e);
+        rc = track_lk_on(c, M, pslot, slot, B);
     }
-    rc = lk_track_on(c, M, pslot, slot, c->corners[pslot], c->status[pslot], c->corners[slot], c->status[slot], nullptr,
-                     c->trk_n, B, AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
     if (rc) return rc;
-    }
     if (pev) (void)hipEventRecord(pev[2], M);
-    hipError_t e = chain_pnp ? hipSuccess : agt_launch_pnp(M, p, B, ride_pnp ? npyr : nullptr);
+    hipError_t e = f.chain_pnp ? hipSuccess : agt_launch_pnp(M, p, B, f.ride_pnp ? npyr : nullptr);
     if (e != hipSuccess) return hip_fail(c, e);
     if (pev) { (void)hipEventRecord(pev[3], M); c->prof_n++; }
-    if (d_dense_out) {
-        // Clip submission: the stage's last step (final update + re-seed, a one-workgroup launch of 5.5 us) is left to the NEXT
-        // frame's LK launch, whose workgroups do it as their prologue (agt_step.hip lk_reseed_kernel) -- when that launch will be the
-        // four-waves-per-corner LK role launch (same geometry as this frame's) and no stage spans are being recorded
-        const bool defer = next_frame && !pev && c->dn_iters > 0 && c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
-        // dense photometric + geometric refinement of the frame's accepted pose, then (reseed) the corner set from it
-        e = agt_launch_dense(M, d_frames, (long)pitch, (long)batch_stride, c->cfg.width, c->cfg.height, c->dn_xyz, c->dn_t, c->dn_M,
-                             c->obj, c->corners[slot], c->status[slot], c->trk_n, c->cam, c->pose, c->dense_partials, nullptr,
-                             c->dense_done, B, c->dn_iters, c->dn_weight, 1e-3, d_dense_out, c->dn_reseed ? c->corners[slot] : nullptr,
-                             c->dn_reseed ? c->status[slot] : nullptr, pev ? pev + 4 : nullptr, 2 * AGT_PROF_DENSE_MAX, (ride && !ride_pnp && !chain_pnp) ? npyr : nullptr,
-                             defer ? &c->dense_final : nullptr);
-        if (e == hipSuccess && defer) c->dense_pending = 1;
-        if (pev) c->prof_dense[c->prof_n - 1] = c->dn_iters < AGT_PROF_DENSE_MAX ? c->dn_iters : AGT_PROF_DENSE_MAX;
-        if (e != hipSuccess) return hip_fail(c, e);
-    }
-    c->trk_frame = t; c->n_lk = c->n_pnp = t;
-    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = t;
+    if (d_dense_out) rc = serial_dense(c, f, d_frames, pitch, batch_stride, slot, B, d_dense_out, pev, npyr);
+    if (rc) return rc;
+    frame_complete(c, t);
     return AGT_OK;
 }
 
@@ -802,8 +935,8 @@ int agt_track_frame(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t ba
     if (!c || !d_frames) return AGT_ERR_ARG;
     if (c->trk_ready != 2) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
-    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
-    hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+    if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
+    hipEvent_t* pev = profile_events(c);
     // the fused launch pays off while the stages are latency-bound (few streams); the biggest batches fill
     // the chip per stage and run faster as separate launches with their own register budgets
     if (c->pipeline && !c->reproject && (agt_step_fits(c->trk_n, B) || !pev)) {
@@ -838,12 +971,12 @@ int agt_track_frame_detected(agt_ctx* c, const uint8_t* d_frames, size_t pitch, 
     if (!c || !d_frames || !d_corners) return AGT_ERR_ARG;
     if (!c->trk_ready) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
-    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
     int rc = join_pipeline(c);
     if (rc) return rc;
     c->prebuilt_t = -1;
     const long t = c->trk_frame + 1;
-    const int slot = (int)(t % c->live_ring);
+    const int slot = ring_slot(c, t);
     rc = pyramid_build_on(c, c->stream, slot, d_frames, pitch, batch_stride, B);
     if (rc) return rc;
     AgtPnpParams p;
@@ -851,8 +984,7 @@ int agt_track_frame_detected(agt_ctx* c, const uint8_t* d_frames, size_t pitch, 
     p.seed_pts = c->corners[slot]; p.seed_status = c->status[slot];
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     if (e != hipSuccess) return hip_fail(c, e);
-    c->trk_frame = t; c->n_lk = c->n_pnp = t;
-    for (int s = 0; s < AGT_MAX_LEVELS; s++) c->n_stage[s] = t;
+    frame_complete(c, t);
     c->trk_ready = 2;
     return AGT_OK;
 }
@@ -895,7 +1027,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
     // Polled record: the frame's record goes straight to host-mapped memory of the context and the solver stores a sequence word behind
     // it (system scope); this thread polls the word -- no 128-byte copy (a blit KERNEL of ~4.5 us behind the step's launch,
     // rocprofv3), no completion signal, no stream wait.  (With profiling spans armed the call waits for the stream as before.)
-    const bool polled = !(c->prof_ev && c->prof_n < c->prof_cap);
+    const bool polled = !profiling_armed(c);
     double* const d_rec = (polled || !d_state) ? c->hrec_dev : d_state;       // where the pose solver writes the frame's record
     bool registered = false;
     // (the device address of the caller's buffer when it is pinned host memory, asked for on EVERY call: a cached answer would outlive the buffer)
@@ -911,12 +1043,10 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
         // level 0 to d_gray on the way (step_pipelined_uploaded) -- one launch instead of a copy-engine transfer (19 us + ~8 us of
         // submission and hand-over) and a pyramid launch (6 us).  Pageable memory, frame sizes the rolling pass does not take, the
         // stage-by-stage mode and pending pyramid work of earlier frames keep the copy.
-        if (c->pipeline && !c->reproject && agt_step_fits(c->trk_n, 1) && !(c->prof_ev && c->prof_n < c->prof_cap)) {
-            if (h_dev) {
-                int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
-                if (rcu < 0) return rcu;
-                registered = rcu == AGT_OK;
-            }
+        if (h_dev && polled && c->pipeline && !c->reproject && agt_step_fits(c->trk_n, 1)) {
+            int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
+            if (rcu < 0) return rcu;
+            registered = rcu == AGT_OK;
         }
         if (!registered) {
             if (gpitch == (size_t)W) e = hipMemcpyAsync(d_gray, h_frame, (size_t)W * H, hipMemcpyHostToDevice, c->stream);
@@ -955,25 +1085,16 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
         AGT_TQ(4);
         rc = poll_seq(c, c->hseq_host, want);
         if (rc) return rc;
-        memcpy(h_state, c->hrec_host, AGT_STATE_STRIDE * sizeof(double));
-#ifdef AGT_DEBUG_KNOBS
-        if (timing) { const double t5 = now(); for (int i = 0; i < 4; i++) acc.t[i] += tq[i + 1] - tq[i]; acc.t[4] += t5 - tq[4]; acc.t[5] += t5 - tq[0]; acc.n++; }
-#endif
-        return *(volatile int*)c->fault_host ? AGT_ERR_CHAIN : AGT_OK;
-    }
-    // (the waited form: profiling spans armed.  HSA_ENABLE_SDMA=0 -- blit-kernel copies -- made
-    // the copy-first form of round 3 slower still: 107 us.)
-    if (d_state) {
-        e = hipMemcpyAsync(h_state, d_state, AGT_STATE_STRIDE * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    } else {
+        // (the waited form: profiling spans armed.  HSA_ENABLE_SDMA=0 -- blit-kernel copies -- made
+        // the copy-first form of round 3 slower still: 107 us.)
+        e = d_state ? hipMemcpyAsync(h_state, d_state, AGT_STATE_STRIDE * sizeof(double), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
         AGT_TQ(4);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hip_fail(c, e);
-    } else {                                   // (no device record asked for: the record is in the context's host-mapped memory once the stream is done)
-        AGT_TQ(4);
-        e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return hip_fail(c, e);
-        memcpy(h_state, c->hrec_host, AGT_STATE_STRIDE * sizeof(double));
     }
+    // (unless a device record was read back: the record is in the context's host-mapped memory once the sequence word / the stream says so)
+    if (polled || !d_state) memcpy(h_state, c->hrec_host, AGT_STATE_STRIDE * sizeof(double));
 #ifdef AGT_DEBUG_KNOBS
     if (timing) { const double t5 = now(); for (int i = 0; i < 4; i++) acc.t[i] += tq[i + 1] - tq[i]; acc.t[4] += t5 - tq[4]; acc.t[5] += t5 - tq[0]; acc.n++; }
 #endif
@@ -1015,8 +1136,8 @@ int agt_tracker_state_read(agt_ctx* c, void* host_dst, int B)
 int agt_tracker_buffers(const agt_ctx* c, const float** d_corners, const uint8_t** d_status)
 {
     if (!c || !c->trk_ready) return AGT_ERR_STATE;
-    if (d_corners) *d_corners = c->corners[c->trk_frame % c->live_ring];
-    if (d_status) *d_status = c->status[c->trk_frame % c->live_ring];
+    if (d_corners) *d_corners = c->corners[ring_slot(c, c->trk_frame)];
+    if (d_status) *d_status = c->status[ring_slot(c, c->trk_frame)];
     return AGT_OK;
 }
 
@@ -1038,8 +1159,8 @@ int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
     if (!c || !d_frames || !d_dense_out) return AGT_ERR_ARG;
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
-    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
-    hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+    if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
+    hipEvent_t* pev = profile_events(c);
     return step_serial(c, d_frames, pitch, batch_stride, B, d_state_out, d_dense_out, pev);
 }
 
@@ -1052,9 +1173,9 @@ int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, si
     if (!c || !d_frames || !d_dense_out || count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
-    if ((pitch & 3) || ((uintptr_t)d_frames & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width) return AGT_ERR_ARG;
+    if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
     for (int k = 0; k < count; k++) {
-        hipEvent_t* pev = (c->prof_ev && c->prof_n < c->prof_cap) ? c->prof_ev + (size_t)c->prof_n * AGT_PROF_EVENTS : nullptr;
+        hipEvent_t* pev = profile_events(c);
         int rc = step_serial(c, d_frames + (size_t)k * frame_stride, pitch, batch_stride, B,
                              d_state_out ? d_state_out + (size_t)k * B * AGT_STATE_STRIDE : nullptr,
                              d_dense_out + (size_t)k * B * AGT_DENSE_STRIDE, pev, k + 1 < count ? d_frames + (size_t)(k + 1) * frame_stride : nullptr);

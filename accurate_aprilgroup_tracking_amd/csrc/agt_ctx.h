@@ -8,13 +8,32 @@
 
 #define AGT_SLOTS 4              // ring entries every context owns (slots 0 / 1 are also the public pyramid slots)
 #define AGT_RING_MAX 224         // (levels + 1) * AGT_MAX_GROUP frames in flight at the deepest pipeline
-#define AGT_EV_SLOTS 8           // events of the split pipeline, per kind: a launch waits for events at most three launches of their role old (l_ev_hist), slots are re-recorded modulo 8
+#define AGT_EV_SLOTS 8           // events of the split pipeline, per kind: a launch waits for events at most three launches of their role old (SplitEvents::lk_hist), slots are re-recorded modulo 8
 // The two-level pyramid pass saves a launch / pipeline stage and 16 % of the pyramid's HBM bytes, but its 41 KB workgroups
 // (3 per CU, eight barriers per tile) stream at 2.5 TB/s against 3.9 + 3.4 TB/s for two single-level passes (8 per CU): it is
 // used where the stage count matters (few streams), the two passes where throughput does (measured at 64 x 720p: 30.5 vs 25 us).
 #define AGT_PYR2_MAX_B 8
 #define AGT_TILT_SLOTS 8          // device table of tilted-sensor matrices: slot 0 the tracker's camera, 1.. the stateless calls'
 #define AGT_SPLIT_SLACK 2        // split mode: groups of extra ring entries (pyramid launches run that far ahead of LK)
+
+// Event state of the split pipeline (agt_api_tracker.hip issue_split).  A role's n-th launch records slot n % AGT_EV_SLOTS of its row, and
+// the histories name the slots of its most recent launches: the events later launches of the OTHER roles wait for (-1 = none: nothing
+// of that role is in flight).  Plain data: valid when zero-filled except for the histories, which reset_history() sets.
+struct SplitEvents {
+    enum Role { PYR, LK, POSE };
+    enum Row { PYR_DONE, LK_DONE, MISC, POSE_DONE, LK2_DONE, ROWS };        // LK2_DONE: the second half of the streams (ms_stream[0])
+    enum Misc { JOIN_LK, JOIN_POSE, HANDOVER, JOIN_LK2 };                   // slots of row MISC: the joins of the three library streams, the caller's stream handing over to LK
+    hipEvent_t ev[ROWS][AGT_EV_SLOTS];
+    long n[3];                               // launches issued in split mode per Role
+    int last_pyr;                            // event slot of the most recent pyramid launch
+    int lk_hist[3];                          // event slots of the three most recent LK launches, newest first
+    int pose_hist[2];                        // event slots of the two most recent PnP launches, newest first
+    int next_slot(Role r) const { return (int)(n[r] % AGT_EV_SLOTS); }
+    void reset_history() { last_pyr = -1; lk_hist[0] = lk_hist[1] = lk_hist[2] = -1; pose_hist[0] = pose_hist[1] = -1; }
+    void pushed_pyr(int slot) { last_pyr = slot; n[PYR]++; }
+    void pushed_lk(int slot) { lk_hist[2] = lk_hist[1]; lk_hist[1] = lk_hist[0]; lk_hist[0] = slot; n[LK]++; }
+    void pushed_pose(int slot) { pose_hist[1] = pose_hist[0]; pose_hist[0] = slot; n[POSE]++; }
+};
 
 struct agt_ctx {
     agt_config cfg;
@@ -43,16 +62,12 @@ struct agt_ctx {
     int live_ring;                           // ring modulus in use (<= ring): (L + 2) * group, at least AGT_SLOTS
     // big batches: the three stages of a step run on three library-owned streams (stage kernels of different frames
     // overlap: 57 us against 93 us back to back at 64 streams); events carry the exact dependencies
-    hipStream_t ms_stream[3];                // pyramid, LK, PnP
-    hipEvent_t ms_ev[5][AGT_EV_SLOTS];       // per launch of the role (split_n modulo AGT_EV_SLOTS): pyramid done, LK done, [2]: join / hand-over events, PnP done, LK done (second half of the streams)
+    hipStream_t ms_stream[3];                // [1] LK, [0] LK of the second half of the streams, [2] PnP (the pyramid role runs on the caller's stream)
     int ms_pool_slot;                        // which set of the process's library streams the context holds (-1: none)
     int ms_ready, ms_active;                 // streams / events exist; frames are in flight on them
     // split mode (more corners in flight than the fused launch takes): the pipeline's groups go out as three launches,
     // pyramid on the caller's stream, LK and PnP on library streams (ms_stream[1], [2])
-    long split_n[3];                         // launches issued in split mode per role: pyramid, LK, PnP
-    int last_p_ev;                           // event slot of the most recent pyramid launch (-1 = none)
-    int l_ev_hist[3];                        // event slots of the three most recent LK launches (-1 = none)
-    int y_ev_hist[2];                        // event slots of the two most recent PnP launches (-1 = none)
+    SplitEvents split;
     long trk_frame;                          // frames supplied since reset (0 = only the reset frame)
     long prebuilt_t = -1;                    // serial step, clip submission: frame whose pyramid the previous frame's dense launch built (-1 = none)
     // clip submission of the dense stage: the previous frame's last step (final update + re-seed) waits for this frame's LK launch
