@@ -122,6 +122,21 @@ int agt_lk_track(agt_ctx* c, int prev_slot, int next_slot,
                        crit_type, crit_max_count, crit_eps, flags, min_eig_threshold);
 }
 
+// agt_lk_track with the forward-backward check: the forward launch as agt_lk_track issues it, then the same kernels back from next_slot
+// to prev_slot in verdict mode (agt_api_tracker.hip lk_verdict_on), on the same stream
+int agt_lk_track_fb(agt_ctx* c, int prev_slot, int next_slot, const float* d_prev_pts, float* d_next_pts,
+                    uint8_t* d_status, float* d_err, float* d_fb_dist, int n, int B,
+                    int crit_type, int crit_max_count, double crit_eps, int flags, double min_eig_threshold, double fb_max_px)
+{
+    if (!c || prev_slot < 0 || prev_slot > 1 || next_slot < 0 || next_slot > 1) return AGT_ERR_ARG;
+    if (!(fb_max_px > 0.0) || !(fb_max_px <= 3.0e38)) return AGT_ERR_ARG;             // (NaN fails both; beyond float32: infinite)
+    int rc = lk_track_on(c, c->stream, prev_slot, next_slot, d_prev_pts, nullptr, d_next_pts, d_status, d_err, n, B,
+                         crit_type, crit_max_count, crit_eps, flags, min_eig_threshold);
+    if (rc) return rc;
+    return lk_verdict_on(c, c->stream, prev_slot, next_slot, d_prev_pts, d_next_pts, d_status, d_err, d_fb_dist, n, B,
+                         crit_type, crit_max_count, crit_eps, flags, min_eig_threshold, fb_max_px);
+}
+
 int agt_solve_pnp(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
                   const uint8_t* d_mask, int n, int B,
                   const double* K, const double* dist, int ndist,

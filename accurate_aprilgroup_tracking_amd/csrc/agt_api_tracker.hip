@@ -151,6 +151,8 @@ static int lk_launch_on(agt_ctx* c, hipStream_t stream, AgtLkParams& p, int prev
         p.prev_pts += (size_t)b0 * n * 2; p.next_pts += (size_t)b0 * n * 2; p.status += (size_t)b0 * n;
         if (p.prev_status) p.prev_status += (size_t)b0 * n;
         if (p.err) p.err += (size_t)b0 * n;
+        if (p.fb.orig) p.fb.orig += (size_t)b0 * n * 2;
+        if (p.fb.dist) p.fb.dist += (size_t)b0 * n;
     }
     hipError_t e = agt_launch_lk(stream, p, c->cfg.win, B, c->cfg.win == 21 ? waves : 0);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
@@ -171,12 +173,39 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
     return lk_launch_on(c, stream, p, prev_slot, next_slot, B, b0, waves);
 }
 
+// The backward launch of the forward-backward check, behind the forward launch prev_slot -> next_slot on the same stream: the same
+// kernels from next_slot back to prev_slot, started at the forward result d_next_pts (no initial flow), for the corners the forward pass
+// kept (d_status is its prev_status), in verdict mode (agt_kernels.h AgtLkVerdict): it writes no point and no err -- d_err only says
+// whether the pass measures one, as the forward pass did, since measuring can drop a corner whose final window left the image -- clears
+// the status byte of a corner that does not come home within fb_max_px of d_prev_pts, and files the distances in d_fb_dist (or null).
+int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
+                  const float* d_prev_pts, const float* d_next_pts, uint8_t* d_status, const float* d_err, float* d_fb_dist,
+                  int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                  int flags, double min_eig_threshold, double fb_max_px)
+{
+    if (!c || !d_prev_pts || !d_next_pts || !d_status || n < 0 || B <= 0) return AGT_ERR_ARG;
+    if (n == 0) return AGT_OK;
+    AgtLkParams p;
+    fill_lk(c, &p, next_slot, prev_slot, d_next_pts, d_status, const_cast<float*>(d_next_pts), d_status, const_cast<float*>(d_err), n,
+            crit_type, crit_max_count, crit_eps, flags & 0xffff & ~AGT_LK_USE_INITIAL_FLOW, min_eig_threshold);
+    p.fb.orig = d_prev_pts; p.fb.dist = d_fb_dist; p.fb.max_px = (float)fb_max_px;
+    return lk_launch_on(c, stream, p, next_slot, prev_slot, B, 0, 0);
+}
+
 // the tracker's LK launch of streams b0 .. b0 + B - 1 between two of its ring entries (B >= 1 and trk_n >= 4 by agt_tracker_reset)
 static int track_lk_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B, int b0 = 0, int waves = 0)
 {
     AgtLkParams p;
     fill_tracker_lk(c, &p, prev_slot, slot);
     return lk_launch_on(c, stream, p, prev_slot, slot, B, b0, waves);
+}
+
+// agt_tracker_fb_check: the verdict launch behind the tracker's LK launch prev_slot -> slot.  A dropped corner is a corner LK lost in
+// this frame: status 0 from here on (sticky), the forward position kept in its entry and carried.
+static int track_fb_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B)
+{
+    return lk_verdict_on(c, stream, prev_slot, slot, c->corners[prev_slot], c->corners[slot], c->status[slot], nullptr, nullptr, c->trk_n, B,
+                         AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, c->fb_max_px);
 }
 
 int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float* d_obj, int n, int B,
@@ -255,6 +284,17 @@ int agt_tracker_tag_gate(agt_ctx* c, int corners_per_tag)
     int rc = join_pipeline(c);
     if (rc) return rc;
     c->tag_gate = corners_per_tag;
+    return AGT_OK;
+}
+
+// Forward-backward check of the tracker's LK (semantics: include/agt_hip.h).  While it is on, frames take the stage-by-stage form
+// whatever the pipeline depth, as under the reproject option: the backward pass is a launch of its own behind the stand-alone LK launch.
+int agt_tracker_fb_check(agt_ctx* c, double fb_max_px)
+{
+    if (!c || !(fb_max_px >= 0.0) || !(fb_max_px <= 3.0e38)) return AGT_ERR_ARG;       // (NaN fails both; beyond float32: infinite)
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->fb_max_px = fb_max_px;
     return AGT_OK;
 }
 
@@ -804,7 +844,10 @@ static SerialForm serial_form(const agt_ctx* c, int pslot, int slot, int nslot, 
     const bool dense_iters = dense && c->dn_iters > 0;
     // four waves per corner: the LK role of the step as a one-frame group (the frame-chained body; see agt_step.hip lk_role)
     const bool wide = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
-    f.lk_role_launch = wide && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
+    // (forward-backward check on: the stand-alone LK launch, which the verdict launch follows -- not the LK role, not the chained or
+    // the deferring forms that build on it)
+    const bool fb = c->fb_max_px > 0.0;
+    f.lk_role_launch = wide && !fb && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
     // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
     // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
     // (Measured on configs[4], us per frame: no ride 89.0; in the PnP launch 84.0-84.5; in the dense launch 84.0-85.3; in the LK
@@ -822,7 +865,7 @@ static SerialForm serial_form(const agt_ctx* c, int pslot, int slot, int nslot, 
     // Clip submission: the stage's last step (final update + re-seed, a one-workgroup launch of 5.5 us) is left to the NEXT
     // frame's LK launch, whose workgroups do it as their prologue (agt_step.hip lk_reseed_kernel) -- when that launch will be the
     // four-waves-per-corner LK role launch (same geometry as this frame's) and no stage spans are being recorded
-    f.defer = next_frame && !spans && dense_iters && wide;
+    f.defer = next_frame && !spans && dense_iters && wide && !fb;
     return f;
 }
 
@@ -913,6 +956,7 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
             if (e != hipSuccess) return hip_fail(c, e);
         }
         rc = track_lk_on(c, M, pslot, slot, B);
+        if (rc == AGT_OK && c->fb_max_px > 0.0) rc = track_fb_on(c, M, pslot, slot, B);
     }
     if (rc) return rc;
     if (pev) (void)hipEventRecord(pev[2], M);
@@ -939,7 +983,7 @@ int agt_track_frame(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t ba
     hipEvent_t* pev = profile_events(c);
     // the fused launch pays off while the stages are latency-bound (few streams); the biggest batches fill
     // the chip per stage and run faster as separate launches with their own register budgets
-    if (c->pipeline && !c->reproject && (agt_step_fits(c->trk_n, B) || !pev)) {
+    if (c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && (agt_step_fits(c->trk_n, B) || !pev)) {
         // fused launch: the three spans collapse into one (span 2 = the whole step_kernel launch)
         if (pev) { (void)hipEventRecord(pev[0], c->stream); (void)hipEventRecord(pev[1], c->stream); (void)hipEventRecord(pev[2], c->stream); }
         int rc = step_pipelined(c, d_frames, pitch, batch_stride, B, d_state_out);
@@ -1043,7 +1087,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
         // level 0 to d_gray on the way (step_pipelined_uploaded) -- one launch instead of a copy-engine transfer (19 us + ~8 us of
         // submission and hand-over) and a pyramid launch (6 us).  Pageable memory, frame sizes the rolling pass does not take, the
         // stage-by-stage mode and pending pyramid work of earlier frames keep the copy.
-        if (h_dev && polled && c->pipeline && !c->reproject && agt_step_fits(c->trk_n, 1)) {
+        if (h_dev && polled && c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && agt_step_fits(c->trk_n, 1)) {
             int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
             if (rcu < 0) return rcu;
             registered = rcu == AGT_OK;
@@ -1157,6 +1201,7 @@ int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
                           double* d_state_out, double* d_dense_out)
 {
     if (!c || !d_frames || !d_dense_out) return AGT_ERR_ARG;
+    if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
@@ -1171,6 +1216,7 @@ int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, si
                            double* d_state_out, double* d_dense_out)
 {
     if (!c || !d_frames || !d_dense_out || count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
+    if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;

@@ -89,6 +89,7 @@ struct agt_ctx {
     int trk_n, trk_B, enhance_ape, trk_ready;
     int reproject, min_points, tag_gate;
     double gate_px;
+    double fb_max_px;                        // agt_tracker_fb_check: forward-backward threshold of the tracker's LK, px (0 = off; on: stage-by-stage frames)
     int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
     // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
     // record, +192 the word); seq(frame t) = hseq_off + t, monotonic across resets and rewinds
@@ -123,6 +124,10 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                 const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
                 int n, int B, int crit_type, int crit_max_count, double crit_eps,
                 int flags, double min_eig_threshold, int b0 = 0, int waves = 0);
+int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
+                  const float* d_prev_pts, const float* d_next_pts, uint8_t* d_status, const float* d_err, float* d_fb_dist,
+                  int n, int B, int crit_type, int crit_max_count, double crit_eps,
+                  int flags, double min_eig_threshold, double fb_max_px);
 int lk_lds_min(int per_cu);
 
 // Wait for a sequence word in host-mapped memory that a kernel stores behind its results (system scope) to reach `want`; after 2 s

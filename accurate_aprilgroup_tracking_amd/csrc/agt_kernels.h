@@ -45,7 +45,17 @@ struct AgtPyrArgs {
 
 #define AGT_MAX_GROUP 32         // frames one fused launch may advance each pipeline stage by (the per-frame tables are kernel arguments: 7.4 KB with the parameters)
 
-#define AGT_LK_FLAG_COTENANT 0x20000     // internal launch flag: the context declared co-tenancy (agt_lk_occupancy_cu): tracker waves at issue priority 1
+// Forward-backward check (agt_lk_track_fb, agt_tracker_fb_check): the BACKWARD launch of the stand-alone LK kernels -- slots swapped,
+// prev_pts = the forward result q, prev_status = status = the forward status -- runs in verdict mode: it publishes no point and no err;
+// a corner whose round trip does not come home within max_px of orig has its status byte cleared (agt_lk_body.h lk_publish).
+struct AgtLkVerdict {
+    const float* orig;        // [B][n][2] the points the forward pass started from; null = an ordinary launch
+    float* dist;              // [B][n] round-trip distance (-1 where either pass lost the corner), or null
+    float max_px;             // a corner is kept while max(|dx|, |dy|) < max_px
+    int pad_;
+};
+
+#define AGT_LK_FLAG_COTENANT 0x20000    // internal launch flag: the context declared co-tenancy (agt_lk_occupancy_cu): tracker waves at issue priority 1
 struct AgtLkParams {
     AgtLevel prev[AGT_MAX_LEVELS];
     AgtLevel next[AGT_MAX_LEVELS];
@@ -62,8 +72,10 @@ struct AgtLkParams {
     float* err;               // [B][n] or null
     int xshift;               // XCD-aware corner order (agt_xcd_order); set by the launchers
     int lds_min;              // host side only: least dynamic LDS a one-wave workgroup asks for = a residency cap (agt_lk_occupancy_cu); 0 = none
-    unsigned long long rsv_[3];   // unused: keeps the size, and so the kernel-argument offsets of the structures that embed it
+    AgtLkVerdict fb;          // forward-backward verdict launch (fb.orig != null); all zero otherwise.  Three words, as ever: the size
+                              // keeps the kernel-argument offsets of the structures that embed this one
 };
+static_assert(sizeof(AgtLkVerdict) == 24, "AgtLkVerdict fills the three reserved words of AgtLkParams");
 
 struct AgtCameraHost {
     double fx, fy, cx, cy;

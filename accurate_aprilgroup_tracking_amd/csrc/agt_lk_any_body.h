@@ -86,6 +86,7 @@ __device__ __forceinline__ void lk_body_any(const AgtLkParams* P, int pt, int b,
     LkFrameIo<1> io;
     io.grouped = false; io.prev_pts = P->prev_pts; io.next_pts = P->next_pts; io.status = P->status; io.err = P->err;
     io.have_pos = false; io.px = io.py = 0.f; io.pst = 1;
+    io.fb = &P->fb;
 
     const float halfx = (ww - 1) * 0.5f, halfy = (wh - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);

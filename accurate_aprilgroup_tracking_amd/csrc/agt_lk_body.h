@@ -293,7 +293,7 @@ struct LkFrameIo {
     bool have_pos; float px, py; int pst;       // pst: the corner's status after the previous frame (with have_pos)
     unsigned* done = nullptr;                   // chained launch (agt_step.hip): arrival counters of this frame, [B]; see lk_publish
     bool bad = false;                           // frame group: the frame's table entries cannot be addresses (agt_step.hip lk_role) -- nothing of the frame is touched
-    uint8_t* rsv_ = nullptr;                    // unused: without it lk_any_kernel is register-allocated differently (kept, as AgtLkParams::rsv_)
+    const AgtLkVerdict* fb = nullptr;           // stand-alone launches only: AgtLkParams::fb of the launch -- in use (lk_publish) where its orig is set
 };
 
 // The frame's result for one corner (called by one lane).  In a chained launch the PnP role of the SAME launch picks the
@@ -330,6 +330,23 @@ __device__ __forceinline__ void lk_publish(const LkFrameIo<NLEV>& io, long pidx,
         lk_publish_stores(io, pidx, x, y, st);
         if (io.err) io.err[pidx] = errv;
         lk_arrive(io.done, b);
+        return;
+    }
+    if (io.fb && io.fb->orig) {
+        // Verdict mode: this is the backward launch of the forward-backward check.  (x, y) is where the corner came home to, st the
+        // backward status; a corner the forward pass lost arrives here with st = 0 through the prev_status exit.  Nothing of the forward
+        // result is rewritten: the status byte is cleared where the round trip fails -- io.status is also the launch's prev_status, but
+        // a corner's byte is read and written by that corner's workgroup alone -- and the distance is filed.  float32 throughout; a NaN
+        // propagates into d and fails the comparison.
+        float d = -1.f;
+        bool keep = false;
+        if (st) {
+            const float dx = fabsf(io.fb->orig[pidx * 2] - x), dy = fabsf(io.fb->orig[pidx * 2 + 1] - y);
+            d = (dx > dy || dx != dx) ? dx : dy;
+            keep = d < io.fb->max_px;
+        }
+        if (!keep) io.status[pidx] = 0;
+        if (io.fb->dist) io.fb->dist[pidx] = d;
         return;
     }
     io.next_pts[pidx * 2] = x; io.next_pts[pidx * 2 + 1] = y;

@@ -233,6 +233,25 @@ class Context:
                                     int(flags), float(min_eig_threshold)), "agt_lk_track")
         return next_pts, status, err
 
+    def lk_track_fb(self, prev_slot, next_slot, prev_pts, next_pts=None, criteria=(3, 30, 0.01), flags=0,
+                    min_eig_threshold=1e-4, fb_threshold=1.0, want_err=True, want_dist=True):
+        """lk_track with the forward-backward check (agt_lk_track_fb): a corner keeps status 1 only if tracking it back from
+        next to prev lands within fb_threshold px (max norm) of where it started.  next_pts and err are the forward pass's.
+        Returns (next_pts [B,n,2] f32, status [B,n] u8, err [B,n] f32|None, fb_dist [B,n] f32|None; -1 where a pass lost the corner)."""
+        assert prev_pts.dtype == torch.float32 and prev_pts.is_cuda and prev_pts.is_contiguous()
+        B, n, _ = prev_pts.shape
+        if next_pts is None:
+            next_pts = torch.zeros_like(prev_pts)
+        else:
+            assert next_pts.dtype == torch.float32 and next_pts.is_contiguous() and next_pts.shape == prev_pts.shape
+        status = torch.empty((B, n), dtype=torch.uint8, device=prev_pts.device)
+        err = torch.empty((B, n), dtype=torch.float32, device=prev_pts.device) if want_err else None
+        dist = torch.empty((B, n), dtype=torch.float32, device=prev_pts.device) if want_dist else None
+        H.check(self.L.agt_lk_track_fb(self.h, prev_slot, next_slot, _ptr(prev_pts), _ptr(next_pts), _ptr(status),
+                                       _ptr(err), _ptr(dist), n, B, int(criteria[0]), int(criteria[1]), float(criteria[2]),
+                                       int(flags), float(min_eig_threshold), float(fb_threshold)), "agt_lk_track_fb")
+        return next_pts, status, err, dist
+
     # ---- PnP
     def solve_pnp(self, obj, img, K, dist, pose=None, use_guess=False, mask=None):
         """obj: cuda [n,3] (shared) or [B,n,3]; img: cuda [B,n,2]; same float dtype.
@@ -363,6 +382,23 @@ def cvtColor(src, code):
 def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, winSize=(21, 21), maxLevel=3,
                          criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0, minEigThreshold=1e-4):
     """cv2.calcOpticalFlowPyrLK for 8-bit single-channel images -> (nextPts (N,1,2) f32, status (N,1) u8, err (N,1) f32)."""
+    return _lk_pair(prevImg, nextImg, prevPts, nextPts, winSize, maxLevel, criteria, flags, minEigThreshold, None)
+
+
+def trackForwardBackward(prevImg, nextImg, prevPts, winSize=(21, 21), maxLevel=3,
+                         criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0, minEigThreshold=1e-4,
+                         fbThreshold=1.0, nextPts=None):
+    """The forward-backward check of OpenCV's lk_track.py sample in one call: calcOpticalFlowPyrLK(prev -> next), the result
+    tracked back next -> prev, and status cleared where the round trip ends fbThreshold px (max norm) or more from prevPts.
+    -> (nextPts (N,1,2) f32, status (N,1) u8, err (N,1) f32, fbDist (N,1) f32; -1 where either pass lost the corner).
+    nextPts and err are exactly calcOpticalFlowPyrLK's; nextPts (argument) is read with OPTFLOW_USE_INITIAL_FLOW."""
+    if not (fbThreshold > 0 and np.isfinite(fbThreshold)):
+        raise error("trackForwardBackward: fbThreshold must be finite and positive")
+    return _lk_pair(prevImg, nextImg, prevPts, nextPts, winSize, maxLevel, criteria, flags, minEigThreshold, float(fbThreshold))
+
+
+def _lk_pair(prevImg, nextImg, prevPts, nextPts, winSize, maxLevel, criteria, flags, minEigThreshold, fb_px):
+    """calcOpticalFlowPyrLK (fb_px None) / trackForwardBackward (fb_px = the threshold) on one host frame pair"""
     _require_gpu()
     a = np.asarray(prevImg); b = np.asarray(nextImg)
     if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
@@ -377,7 +413,8 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, winSize=(21, 2
     n = pts.shape[0]
     h, w = a.shape
     if n == 0:
-        return np.zeros((0, 1, 2), np.float32), np.zeros((0, 1), np.uint8), np.zeros((0, 1), np.float32)
+        empty = (np.zeros((0, 1, 2), np.float32), np.zeros((0, 1), np.uint8), np.zeros((0, 1), np.float32))
+        return empty if fb_px is None else empty + (np.zeros((0, 1), np.float32),)
     try:
         ctx = _context(w, h, maxLevel, win, n)
     except H.AgtError as e:
@@ -393,6 +430,10 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, winSize=(21, 2
         nx = None
         if nextPts is not None and (flags & OPTFLOW_USE_INITIAL_FLOW):
             nx = torch.from_numpy(np.ascontiguousarray(np.asarray(nextPts, np.float32).reshape(1, n, 2))).to(dev)
+        if fb_px is not None:
+            nx, st, er, fd = ctx.lk_track_fb(0, 1, pp, nx, criteria=criteria, flags=flags, min_eig_threshold=minEigThreshold, fb_threshold=fb_px)
+            return (nx.cpu().numpy().reshape(n, 1, 2), st.cpu().numpy().reshape(n, 1), er.cpu().numpy().reshape(n, 1),
+                    fd.cpu().numpy().reshape(n, 1))
         nx, st, er = ctx.lk_track(0, 1, pp, nx, criteria=criteria, flags=flags, min_eig_threshold=minEigThreshold)
         return (nx.cpu().numpy().reshape(n, 1, 2), st.cpu().numpy().reshape(n, 1), er.cpu().numpy().reshape(n, 1))
 

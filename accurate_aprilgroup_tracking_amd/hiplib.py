@@ -39,7 +39,7 @@ SYMBOLS = [
     "agt_preprocess_bgr", "agt_dense_refine", "agt_tracker_dense", "agt_track_frame_dense", "agt_track_frames_dense", "agt_upload", "agt_download",
     "agt_tracker_tag_gate", "agt_track_frame_detected", "agt_track_host_frame", "agt_tracker_rewind",
     "agt_device_info", "agt_xcd_tile_order", "agt_lk_occupancy", "agt_lk_occupancy_cu", "agt_lk_lds_request",
-    "agt_solve_pnp_host", "agt_project_points_host",
+    "agt_solve_pnp_host", "agt_project_points_host", "agt_lk_track_fb", "agt_tracker_fb_check",
 ]
 
 
@@ -90,6 +90,8 @@ def lib():
                                     C.POINTER(sz), C.POINTER(sz)]
     L.agt_pyramid_max_level.argtypes = [vp]
     L.agt_lk_track.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, f64, i32, f64]
+    L.agt_lk_track_fb.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, i32, f64, f64]
+    L.agt_tracker_fb_check.argtypes = [vp, f64]
     L.agt_solve_pnp.argtypes = [vp, vp, sz, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
     L.agt_project_points.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.agt_tracker_reset.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32]

@@ -42,13 +42,19 @@ class PoseDetector(TransformHelper):
     ERROR_GATE_PX = 2       # detect_pose.py:539
     DECISION_MARGIN = 50    # detect_pose.py:389
 
-    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv"):
+    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None):
         """`detector(gray) -> iterable of objects with .tag_id, .corners (4,2), .decision_margin`
-        stands in for apriltag.Detector(...).detect (detect_pose.py:368-371)."""
+        stands in for apriltag.Detector(...).detect (detect_pose.py:368-371).
+        lk_fb_px: forward-backward check of the LK step (None / 0 = off): a tracked corner whose track back into the previous
+        frame ends that many pixels (max norm) or more from where it started is dropped, and with it its tag.  backend
+        "stream" hands it to its StreamTracker (fb_check); backend "cv" tracks back with a second calcOpticalFlowPyrLK."""
         TransformHelper.__init__(self, logger, mtx, dist, cv=cv)
         if backend not in ("cv", "stream"):
             raise ValueError("backend must be 'cv' or 'stream'")
+        if lk_fb_px is not None and not (np.isfinite(lk_fb_px) and lk_fb_px >= 0):
+            raise ValueError("lk_fb_px must be None or a finite threshold >= 0")
         self.backend = backend
+        self.lk_fb_px = float(lk_fb_px) if lk_fb_px else None
         self._dev = None                # stream backend: _DeviceStream, created at the first frame (its size fixes the context)
         self.img = None
         self.draw_frame = None
@@ -109,7 +115,7 @@ class PoseDetector(TransformHelper):
         self.__dict__["_st_" + name] = value
 
     @classmethod
-    def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv"):
+    def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv", lk_fb_px=None):
         """Build from the reference's on-disk files: `CameraParams.npz` (calibrate_camera.py:107-123) and,
         optionally, an `april_group.json` somewhere else than DIRPATH/JSON_FILE (detect_pose.py:54-55).
         `detector` may be a recorded-detections .npz (formats.ReplayDetector) to replay a session."""
@@ -119,10 +125,10 @@ class PoseDetector(TransformHelper):
         if isinstance(detector, (str, os.PathLike)):
             detector = formats.ReplayDetector(detector)
         if april_group is None:
-            return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend)
+            return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px)
         folder, name = os.path.split(os.fspath(april_group))
         sub = type(cls.__name__, (cls,), {"DIRPATH": folder or ".", "JSON_FILE": name})
-        return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend)
+        return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px)
 
     # ------------------------------------------------------------------ model (detect_pose.py:105-227)
     def get_extrinsics(self):
@@ -262,6 +268,11 @@ class PoseDetector(TransformHelper):
         (21x21 window, 3 levels, COUNT+EPS (30, 0.01)) and return them per tag."""
         nxt, status, _ = self.cv.calcOpticalFlowPyrLK(self._prev_gray, gray, self._prev_corners, None,
                                                       winSize=(21, 21), maxLevel=2)
+        if self.lk_fb_px:
+            # forward-backward check (OpenCV's lk_track.py sample): back from where the corners arrived; float32 max norm
+            back, st_b, _ = self.cv.calcOpticalFlowPyrLK(gray, self._prev_gray, nxt, None, winSize=(21, 21), maxLevel=2)
+            d = np.abs(np.asarray(self._prev_corners, np.float32).reshape(-1, 2) - np.asarray(back, np.float32).reshape(-1, 2)).max(axis=1)
+            status = (status.reshape(-1) != 0) & (st_b.reshape(-1) != 0) & (d < np.float32(self.lk_fb_px))
         nxt = nxt.reshape(-1, 4, 2); ok = status.reshape(-1, 4).all(axis=1)
         img_list, obj_list, ids = [], [], []
         for t, tag_id in enumerate(self._prev_ids):
@@ -359,7 +370,7 @@ class _DeviceStream:
             new_k, self.roi, gw, gh = None, (0, 0, w, h), w, h
         self.trk = StreamTracker(gw, gh, det.all_objpts, det.mtx, det.dist, n_streams=1, max_level=2, win=21,
                                  enhance_ape=det.enhance_ape, reproject=False, min_points=4 * det.MIN_TAGS,
-                                 gate_px=float(det.ERROR_GATE_PX))
+                                 gate_px=float(det.ERROR_GATE_PX), fb_check=det.lk_fb_px or 0.0)
         self.trk.tag_gate(4)
         self.trk.pipeline(1)
         self.trk.reset()

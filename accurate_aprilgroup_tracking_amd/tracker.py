@@ -24,7 +24,7 @@ class TrackState(C.Structure):
 
 class StreamTracker:
     def __init__(self, width, height, obj_points, K, dist=None, n_streams=1, max_level=2, win=21,
-                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None):
+                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0):
         obj = np.ascontiguousarray(np.asarray(obj_points, np.float32).reshape(-1, 3))
         self.n = obj.shape[0]
         self.B = n_streams
@@ -38,6 +38,8 @@ class StreamTracker:
         assert H.lib().agt_tracker_state_size() == C.sizeof(TrackState)
         H.check(self.ctx.L.agt_tracker_options(self.ctx.h, int(reproject), int(min_points), float(gate_px)),
                 "agt_tracker_options")
+        if fb_check:
+            self.fb_check(fb_check)
         self._alive = []            # frames aliased by pyramid level 0 of the ring entries in flight
         self._keep_frames = max((max_level + 6) + 2, 12)
 
@@ -84,6 +86,13 @@ class StreamTracker:
         """4: the pose solve uses a corner only while all four corners of its tag are usable, min_points = 8 then is the
         reference's ">= 2 tags" (detect_pose.py:494-496).  0: every usable corner counts (the default of the C ABI)."""
         H.check(self.ctx.L.agt_tracker_tag_gate(self.ctx.h, int(corners_per_tag)), "agt_tracker_tag_gate")
+
+    def fb_check(self, max_px=1.0):
+        """Forward-backward check of the LK step: a corner whose track back from the new frame ends max_px (max norm) or more
+        from where it started is treated as lost in that frame (status 0, sticky; out of the solve, the tag gate and NTRACK).
+        0 switches it off (the default).  While it is on, step() runs stage by stage whatever the pipeline depth, with one
+        more LK launch per frame; step_dense() is refused.  May be changed mid-stream; joins the pipeline."""
+        H.check(self.ctx.L.agt_tracker_fb_check(self.ctx.h, float(max_px)), "agt_tracker_fb_check")
 
     def rewind(self):
         """Take the newest frame back as the tracking source: the next step() tracks from the frame before it (the reference

@@ -156,6 +156,17 @@ int agt_lk_track(agt_ctx* ctx, int prev_slot, int next_slot,
                  const float* d_prev_pts, float* d_next_pts, uint8_t* d_status, float* d_err,
                  int n, int B, int crit_type, int crit_max_count, double crit_eps,
                  int flags, double min_eig_threshold);
+/* agt_lk_track with the forward-backward check of OpenCV's lk_track.py sample (Kalal et al.): the corners are tracked prev -> next
+ * exactly as agt_lk_track does it (d_next_pts and d_err are that pass's, for every corner), the corners it kept (status 1) are
+ * tracked back next -> prev from where they arrived -- same window, levels, criteria and min_eig_threshold, the flags without
+ * AGT_LK_USE_INITIAL_FLOW -- and with d = max(|p.x - p'.x|, |p.y - p'.y|) in float32 between a corner p and its return p'
+ *     status = forward status && backward status && d < (float)fb_max_px            (a NaN fails the comparison).
+ * d_fb_dist: [B][n] f32 or NULL: d where both passes have status 1, -1 elsewhere.  Two launches of the LK kernels on the context's
+ * stream.  fb_max_px must be finite and > 0 (AGT_ERR_ARG).  Present from ABI 505 on: look the symbol up. */
+int agt_lk_track_fb(agt_ctx* ctx, int prev_slot, int next_slot, const float* d_prev_pts, float* d_next_pts,
+                    uint8_t* d_status, float* d_err, float* d_fb_dist, int n, int B,
+                    int crit_type, int crit_max_count, double crit_eps, int flags, double min_eig_threshold,
+                    double fb_max_px);
 
 /* ---- cv::solvePnP(SOLVEPNP_ITERATIVE), batched ---- */
 /* d_obj: n x 3 (obj_batch_stride = 0: shared by all B) or [B][n][3] (stride in elements).
@@ -228,6 +239,16 @@ int agt_lk_occupancy(agt_ctx* ctx, int waves_per_simd);
  * are usable, and min_points = 8 then means the reference's ">= 2 tags" (detect_pose.py:494-496; its detections are whole
  * tags, :400-437).  0 (default): every usable corner counts. */
 int agt_tracker_tag_gate(agt_ctx* ctx, int corners_per_tag);
+/* Forward-backward check of the tracker's LK step (agt_lk_track_fb's rule, threshold fb_max_px in pixels; 0 = off, the default):
+ * a corner that slid onto an occluder, a reflection or a neighbouring tag keeps LK status 1 but does not track back to where it
+ * started.  A corner the check drops is a corner LK lost in that frame: status 0 from then on (sticky), its entry keeps the forward
+ * position and is carried, it is masked out of the solve and counts against agt_tracker_tag_gate and AGT_ST_NTRACK; a detector-fed
+ * frame, agt_tracker_reset or an accepted pose under the reproject option revives it.  While the check is on, agt_track_frame,
+ * agt_track_frames and agt_track_host_frame run stage by stage whatever the pipeline depth (as under reproject): pyramid, LK, the
+ * backward LK launch, PnP -- about one more LK launch per frame; switching it off brings the pipelined forms back.
+ * agt_track_frame_dense / agt_track_frames_dense return AGT_ERR_UNSUPPORTED while it is on.  Joins the pipeline.  fb_max_px must be
+ * finite and >= 0 (AGT_ERR_ARG).  Present from ABI 505 on: look the symbol up. */
+int agt_tracker_fb_check(agt_ctx* ctx, double fb_max_px);
 /* Software pipelining across frames.  depth 0: separate launches per stage, the record of frame t is complete
  * in stream order after its call.  depth F in 1..32 (default 1; needs reproject == 0, otherwise the call falls back to
  * depth 0 behaviour): agt_track_frame registers the frame and, every F calls, issues ONE fused launch that advances every
