@@ -109,7 +109,7 @@ int ensure_ring(agt_ctx* c, int want)
     for (int s = c->ring; s < want; s++) {
         bool ok = true;
         for (int l = 1; l <= c->eff_max_level && ok; l++)
-            ok = hipMalloc((void**)&c->lmem[s][l], B * (size_t)c->lh[l] * (size_t)c->lpitch[l]) == hipSuccess;
+            ok = hipMalloc((void**)&c->lmem[s][l], B * (size_t)level_bstride(c, l)) == hipSuccess;
         ok = ok && hipMalloc((void**)&c->corners[s], B * N * 2 * sizeof(float)) == hipSuccess;
         ok = ok && hipMalloc((void**)&c->status[s], B * N) == hipSuccess;
         ok = ok && hipMemsetAsync(c->status[s], 1, B * N, c->stream) == hipSuccess;

@@ -16,7 +16,8 @@ int agt_pyr_down_u8(agt_ctx* c, const uint8_t* d_src, int sw, int sh, size_t spi
     if (!c || !d_src || !d_dst || sw <= 0 || sh <= 0 || B <= 0) return AGT_ERR_ARG;
     if ((spitch & 3) || (dpitch & 3) || ((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 3) || (sbatch & 3) || (dbatch & 3)) return AGT_ERR_ARG;
     if (spitch < (size_t)sw || dpitch < (size_t)((sw + 1) / 2)) return AGT_ERR_ARG;
-    hipError_t e = agt_launch_pyr_down(c->stream, d_src, sw, sh, (long)spitch, (long)sbatch, d_dst, (long)dpitch, (long)dbatch, B);
+    const AgtLevel src = { d_src, (long)spitch, (long)sbatch, sw, sh }, dst = { d_dst, (long)dpitch, (long)dbatch, (sw + 1) / 2, (sh + 1) / 2 };
+    hipError_t e = agt_launch_pyr_down(c->stream, src, dst, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
@@ -46,34 +47,28 @@ int agt_pyramid_build_pair(agt_ctx* c, const uint8_t* d_prev, const uint8_t* d_n
                !((pitch & 3) || ((uintptr_t)d_prev & 3) || ((uintptr_t)d_next & 3) || (batch_stride & 3) || pitch < (size_t)c->cfg.width);
     AgtStepParams S;
     AgtStepTables T;
+    const uint8_t* src[2] = { d_prev, d_next };
     if (one) {
         memset(&S, 0, sizeof(S));
         memset(&T, 0, sizeof(T));
         S.pnp.fault = c->fault_dev;
-        AgtPyrArgs& A = S.pyr[0];
-        A.sw = c->lw[0]; A.sh = c->lh[0]; A.dw = c->lw[1]; A.dh = c->lh[1];
-        A.spitch = (long)pitch; A.sbatch = (long)batch_stride;
-        A.dpitch = c->lpitch[1]; A.dbatch = (long)c->lh[1] * c->lpitch[1];
-        A.B = B;
         uintptr_t src_align = 0, dst_align = 0;
-        const uint8_t* src[2] = { d_prev, d_next };
         for (int k = 0; k < 2; k++) {
             T.pyr_src[0][k] = src[k]; T.pyr_dst[0][k] = c->lmem[k][1]; T.pyr_dst[1][k] = c->lmem[k][2];
             src_align |= (uintptr_t)src[k]; dst_align |= (uintptr_t)c->lmem[k][1] | (uintptr_t)c->lmem[k][2];
         }
-        A.src = T.pyr_src[0][0]; A.dst = T.pyr_dst[0][0];
-        AgtPyrArgs A0 = A, A1 = S.pyr[1];
-        A1.sw = c->lw[1]; A1.sh = c->lh[1]; A1.dw = c->lw[2]; A1.dh = c->lh[2];
-        A1.spitch = c->lpitch[1]; A1.sbatch = (long)c->lh[1] * c->lpitch[1];
-        A1.dpitch = c->lpitch[2]; A1.dbatch = (long)c->lh[2] * c->lpitch[2];
-        A1.B = B; A1.src = nullptr; A1.dst = nullptr;
-        agt_pyr2_plan(&A0, &A1, src_align, dst_align, 2);
-        one = A0.pad != 0 || B <= AGT_PYR2_MAX_B;             // (rolling form for big batches; the tiled two-level pass for small ones)
+        AgtLevel lv[AGT_MAX_LEVELS];
+        fill_levels(c, 0, lv);
+        lv[0].ptr = d_prev; lv[0].pitch = (long)pitch; lv[0].bstride = (long)batch_stride;
+        AgtPyrArgs A[2];
+        agt_pyr2_args(lv, B, A);
+        A[1].src = nullptr; A[1].dst = nullptr;              // (per frame: the tables)
+        agt_pyr2_plan(A, src_align, dst_align, 2);
+        one = agt_pyr_rolling(A[0]) || B <= AGT_PYR2_MAX_B;             // (rolling form for big batches; the tiled two-level pass for small ones)
         if (one) {
-            S.pyr[0] = A0; S.pyr[1] = A1;
-            S.pyr_fused = 1;
+            agt_step_set_two_level(S, A);
             S.pyr_nf[0] = 2;
-            S.n_pyr[0] = A0.gx * A0.gy * B * 2;
+            S.n_pyr[0] = agt_pyr_blocks(A[0]) * B * 2;
         }
     }
     if (!one) {
@@ -82,16 +77,10 @@ int agt_pyramid_build_pair(agt_ctx* c, const uint8_t* d_prev, const uint8_t* d_n
     }
     hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
     if (e != hipSuccess) return hip_fail(c, e);
-    const uint8_t* src[2] = { d_prev, d_next };
     for (int k = 0; k < 2; k++) {
         c->l0_ptr[k] = src[k]; c->l0_pitch[k] = (long)pitch; c->l0_bstride[k] = (long)batch_stride;
-        const uint8_t* sp_ = c->lmem[k][2]; long spitch = c->lpitch[2], sb = (long)c->lh[2] * c->lpitch[2];
-        for (int l = 3; l <= L; l++) {
-            const long db = (long)c->lh[l] * c->lpitch[l];
-            e = agt_launch_pyr_down(c->stream, sp_, c->lw[l - 1], c->lh[l - 1], spitch, sb, c->lmem[k][l], c->lpitch[l], db, B);
-            if (e != hipSuccess) return hip_fail(c, e);
-            sp_ = c->lmem[k][l]; spitch = c->lpitch[l]; sb = db;
-        }
+        rc = pyramid_levels_on(c, c->stream, k, 3, B);
+        if (rc) return rc;
         c->built_B[k] = B;
     }
     return AGT_OK;
@@ -108,7 +97,7 @@ int agt_pyramid_level(const agt_ctx* c, int slot, int level, const uint8_t** d_p
     if (w) *w = c->lw[level];
     if (h) *h = c->lh[level];
     if (pitch) *pitch = (size_t)(level == 0 ? c->l0_pitch[slot] : c->lpitch[level]);
-    if (batch_stride) *batch_stride = (size_t)(level == 0 ? c->l0_bstride[slot] : (long)c->lh[level] * c->lpitch[level]);
+    if (batch_stride) *batch_stride = (size_t)(level == 0 ? c->l0_bstride[slot] : level_bstride(c, level));
     return AGT_OK;
 }
 
@@ -291,8 +280,10 @@ int agt_dense_refine(agt_ctx* c, const uint8_t* d_img, size_t pitch, size_t batc
     if (rc) return rc;
     rc = dense_scratch(c, agt_dense_doubles(M, B), B);
     if (rc) return rc;
-    hipError_t e = agt_launch_dense(c->stream, d_img, (long)pitch, (long)batch_stride, w, h, d_model_xyz, d_model_t, M,
-                                    d_obj, d_img_pts, d_mask, N, cam, d_pose, c->dense_partials, d_stats, c->dense_done,
-                                    B, iters, photo_weight, 1e-3, nullptr, nullptr, nullptr);
+    agt_dense::DenseParams P = dense_params_on(c);
+    P.img = d_img; P.pitch = (long)pitch; P.ibatch = (long)batch_stride; P.w = w; P.h = h;
+    P.mxyz = d_model_xyz; P.mt = d_model_t; P.M = M; P.obj = d_obj; P.ipts = d_img_pts; P.mask = d_mask; P.N = N;
+    P.cam = cam; P.pose = d_pose; P.stats = d_stats; P.photo_weight = photo_weight;
+    hipError_t e = agt_launch_dense(c->stream, P, B, iters);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }

@@ -32,6 +32,13 @@ static inline hipEvent_t* profile_events(const agt_ctx* c) { return profiling_ar
 
 // scratch of the dense refinement: `need` doubles of block partials and one done word per stream; the two
 // capacities are tracked separately (a later call may bring more streams with fewer samples)
+agt_dense::DenseParams dense_params_on(const agt_ctx* c)
+{
+    agt_dense::DenseParams P = agt_dense::DenseParams();
+    P.partials = c->dense_partials; P.done = c->dense_done; P.mu = 1e-3;
+    return P;
+}
+
 int dense_scratch(agt_ctx* c, size_t need, int B)
 {
     if (need <= c->dense_cap && B <= c->dense_done_B) return AGT_OK;
@@ -57,42 +64,44 @@ int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_
     if (!c || !d_frames || slot < 0 || slot >= c->ring || B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
     c->l0_ptr[slot] = d_frames; c->l0_pitch[slot] = (long)pitch; c->l0_bstride[slot] = (long)batch_stride;
-    const uint8_t* src = d_frames; long sp = (long)pitch, sb = (long)batch_stride;
+    AgtLevel lv[AGT_MAX_LEVELS];
+    fill_levels(c, slot, lv);
     int l0 = 1;
-    bool two_level = c->eff_max_level >= 2 && B <= AGT_PYR2_MAX_B;
-    if (c->eff_max_level >= 2 && !two_level) {
-        // big batches: the two-level pass only in its register-rolling form (the tiled one loses to two single passes there)
-        AgtPyrArgs A0, A1;
-        agt_pyr2_args(src, c->lw[0], c->lh[0], sp, sb, c->lmem[slot][1], c->lpitch[1], (long)c->lh[1] * c->lpitch[1],
-                      c->lmem[slot][2], c->lpitch[2], (long)c->lh[2] * c->lpitch[2], B, &A0, &A1);
-        agt_pyr2_plan(&A0, &A1, (uintptr_t)src, (uintptr_t)c->lmem[slot][1] | (uintptr_t)c->lmem[slot][2], 1);
-        two_level = A0.pad != 0;
+    if (c->eff_max_level >= 2) {
+        // levels 1 and 2 in one pass: level 0 is read once, level 1 is never re-read from HBM.  Big batches: only in the pass's
+        // register-rolling form (the tiled one loses to two single passes there)
+        AgtPyrArgs A[2];
+        agt_pyr2_args(lv, B, A);
+        agt_pyr2_plan(A, (uintptr_t)lv[0].ptr, (uintptr_t)lv[1].ptr | (uintptr_t)lv[2].ptr, 1);
+        if (B <= AGT_PYR2_MAX_B || agt_pyr_rolling(A[0])) {
+            hipError_t e = agt_launch_pyr_down2(stream, A);
+            if (e != hipSuccess) return hip_fail(c, e);
+            l0 = 3;
+        }
     }
-    if (two_level) {
-        // levels 1 and 2 in one pass: level 0 is read once, level 1 is never re-read from HBM
-        const long db1 = (long)c->lh[1] * c->lpitch[1], db2 = (long)c->lh[2] * c->lpitch[2];
-        hipError_t e = agt_launch_pyr_down2(stream, src, c->lw[0], c->lh[0], sp, sb, c->lmem[slot][1], c->lpitch[1], db1,
-                                            c->lmem[slot][2], c->lpitch[2], db2, B);
-        if (e != hipSuccess) return hip_fail(c, e);
-        src = c->lmem[slot][2]; sp = c->lpitch[2]; sb = db2;
-        l0 = 3;
-    }
-    for (int l = l0; l <= c->eff_max_level; l++) {
-        const long db = (long)c->lh[l] * c->lpitch[l];
-        hipError_t e = agt_launch_pyr_down(stream, src, c->lw[l - 1], c->lh[l - 1], sp, sb, c->lmem[slot][l], c->lpitch[l], db, B);
-        if (e != hipSuccess) return hip_fail(c, e);
-        src = c->lmem[slot][l]; sp = c->lpitch[l]; sb = db;
-    }
+    int rc = pyramid_levels_on(c, stream, slot, l0, B);
+    if (rc) return rc;
     c->built_B[slot] = B;
     return AGT_OK;
 }
 
-static void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
+int pyramid_levels_on(agt_ctx* c, hipStream_t stream, int slot, int l0, int B)
+{
+    AgtLevel lv[AGT_MAX_LEVELS];
+    fill_levels(c, slot, lv);
+    for (int l = l0; l <= c->eff_max_level; l++) {
+        hipError_t e = agt_launch_pyr_down(stream, lv[l - 1], lv[l], B);
+        if (e != hipSuccess) return hip_fail(c, e);
+    }
+    return AGT_OK;
+}
+
+void fill_levels(const agt_ctx* c, int slot, AgtLevel* L)
 {
     for (int l = 0; l <= c->eff_max_level; l++) {
         L[l].w = c->lw[l]; L[l].h = c->lh[l]; L[l].ptr = level_ptr(c, slot, l);
         if (l == 0) { L[l].pitch = c->l0_pitch[slot]; L[l].bstride = c->l0_bstride[slot]; }
-        else { L[l].pitch = c->lpitch[l]; L[l].bstride = (long)c->lh[l] * c->lpitch[l]; }
+        else { L[l].pitch = c->lpitch[l]; L[l].bstride = level_bstride(c, l); }
     }
 }
 
@@ -407,30 +416,30 @@ struct GroupEntry {
 static void stage_geometry(const agt_ctx* c, int s, int B, AgtPyrArgs& A)
 {
     A.sw = c->lw[s]; A.sh = c->lh[s]; A.dw = c->lw[s + 1]; A.dh = c->lh[s + 1]; A.B = B;
-    if (s) { A.spitch = c->lpitch[s]; A.sbatch = (long)c->lh[s] * c->lpitch[s]; }
-    A.dpitch = c->lpitch[s + 1]; A.dbatch = (long)c->lh[s + 1] * c->lpitch[s + 1];
+    if (s) { A.spitch = c->lpitch[s]; A.sbatch = level_bstride(c, s); }
+    A.dpitch = c->lpitch[s + 1]; A.dbatch = level_bstride(c, s + 1);
 }
 
-// Stage 0 as the two-level pass (levels 1 and 2 from level 0): the level 1 -> 2 geometry and buffers ride in stage 1's slots; the pass's
-// grid in pyr[0]: 64 x 16 tiles of level 2 (tiled form) or workgroups per image with the strip height in pad (register-rolling form,
-// agt_pyramid4_body.h).  Stage 0's single-level plan of frames first .. first + cnt - 1 is in S.pyr[0] / T; returns whether the
-// two-level pass replaces it (`fused` on entry: it has to, the batch is small).
+// Stage 0 as the two-level pass (levels 1 and 2 from level 0; agt_step_set_two_level): the pass's grid is 64 x 16 tiles of level 2
+// (tiled form) or workgroups per image with the strip height in strip_rows (register-rolling form, agt_pyramid4_body.h).  Stage 0's
+// single-level plan of frames first .. first + cnt - 1 is in S.pyr[0] / T; returns whether the two-level pass replaces it (`fused`
+// on entry: it has to, the batch is small).
 static bool plan_two_level(agt_ctx* c, const GroupEntry& G, AgtStepParams& S, AgtStepTables& T, long first, int cnt,
                            uintptr_t src_align, uintptr_t dst_align, bool fused)
 {
     const int B = G.B;
-    AgtPyrArgs A0 = S.pyr[0], A1 = S.pyr[1];
-    stage_geometry(c, 1, B, A1);
+    AgtPyrArgs A[2] = { S.pyr[0], S.pyr[1] };
+    stage_geometry(c, 1, B, A[1]);
     uintptr_t d2_align = 0;
     for (int k = 0; k < cnt; k++) d2_align |= (uintptr_t)c->lmem[ring_slot(c, first + k)][2];
     // (fused step: agt_step_fits, <= 256 corners in flight -- its kernel carries the tiled two-level pass only: plan as ONE frame, which
     // keeps the launch below the rolling form's 16 images.  Round 5: except the pyramid-only launch at the head of a run, which is
     // pyr_group_kernel -- 20 frames of 1280x720, the driver's block: 15.1 us tiled, see DESIGN.md section 6 for the rolling figure)
-    agt_pyr2_plan(&A0, &A1, src_align, dst_align | d2_align, (G.fits && !G.pyr_only) ? 1 : cnt,
+    agt_pyr2_plan(A, src_align, dst_align | d2_align, (G.fits && !G.pyr_only) ? 1 : cnt,
                   (G.fits || B < AGT_SPLIT_PYR_OH_B0 || B > AGT_SPLIT_PYR_OH_B1) ? 16 : AGT_SPLIT_PYR_OH);
-    if (!fused && A0.pad != 0 && c->n_stage[1] == first - 1) fused = true;       // big batch, rolling form, no backlog (stage 1 is where stage 0 is)
+    if (!fused && agt_pyr_rolling(A[0]) && c->n_stage[1] == first - 1) fused = true;       // big batch, rolling form, no backlog (stage 1 is where stage 0 is)
     if (fused) {
-        S.pyr[0] = A0; S.pyr[1] = A1;
+        agt_step_set_two_level(S, A);
         for (int k = 0; k < cnt; k++) T.pyr_dst[1][k] = c->lmem[ring_slot(c, first + k)][2];
         c->n_stage[1] += cnt;            // (same frames: level 2 is complete when level 1 is)
     }
@@ -467,14 +476,13 @@ static bool plan_pyramid(agt_ctx* c, const GroupEntry& G, AgtStepParams& S, AgtS
             src_align |= (uintptr_t)T.pyr_src[s][k]; dst_align |= (uintptr_t)T.pyr_dst[s][k];
         }
         A.src = T.pyr_src[s][0]; A.dst = T.pyr_dst[s][0];
-        agt_pyr_plan(&A, src_align, dst_align, (int)cnt);          // tiled or register-rolling form (A.pad), workgroups per image in A.gx * A.gy
+        agt_pyr_plan(&A, src_align, dst_align, (int)cnt);          // tiled or register-rolling form (agt_pyr_rolling), workgroups per image: agt_pyr_blocks
         if (s == 0 && L >= 2) fused = plan_two_level(c, G, S, T, first, (int)cnt, src_align, dst_align, fused);
         S.pyr_nf[s] = (int)cnt;
-        S.n_pyr[s] = A.gx * A.gy * B * (int)cnt;
+        S.n_pyr[s] = agt_pyr_blocks(A) * B * (int)cnt;
         c->n_stage[s] += cnt;
         any = true;
     }
-    S.pyr_fused = fused ? 1 : 0;
     return any;
 }
 
@@ -905,10 +913,12 @@ static int serial_lk_role(agt_ctx* c, const SerialForm& f, const AgtPnpParams& p
 static int serial_dense(agt_ctx* c, const SerialForm& f, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int slot, int B,
                         double* d_dense_out, hipEvent_t* pev, const AgtPyrArgs* npyr)
 {
-    hipError_t e = agt_launch_dense(c->stream, d_frames, (long)pitch, (long)batch_stride, c->cfg.width, c->cfg.height, c->dn_xyz, c->dn_t, c->dn_M,
-                                    c->obj, c->corners[slot], c->status[slot], c->trk_n, c->cam, c->pose, c->dense_partials, nullptr,
-                                    c->dense_done, B, c->dn_iters, c->dn_weight, 1e-3, d_dense_out, c->dn_reseed ? c->corners[slot] : nullptr,
-                                    c->dn_reseed ? c->status[slot] : nullptr, pev ? pev + 4 : nullptr, 2 * AGT_PROF_DENSE_MAX,
+    agt_dense::DenseParams P = dense_params_on(c);
+    P.img = d_frames; P.pitch = (long)pitch; P.ibatch = (long)batch_stride; P.w = c->cfg.width; P.h = c->cfg.height;
+    P.mxyz = c->dn_xyz; P.mt = c->dn_t; P.M = c->dn_M; P.obj = c->obj; P.ipts = c->corners[slot]; P.mask = c->status[slot]; P.N = c->trk_n;
+    P.cam = c->cam; P.pose = c->pose; P.photo_weight = c->dn_weight; P.rec = d_dense_out;
+    if (c->dn_reseed) { P.seed_pts = c->corners[slot]; P.seed_status = c->status[slot]; }
+    hipError_t e = agt_launch_dense(c->stream, P, B, c->dn_iters, pev ? pev + 4 : nullptr, 2 * AGT_PROF_DENSE_MAX,
                                     (f.ride && !f.ride_pnp && !f.chain_pnp) ? npyr : nullptr, f.defer ? &c->dense_final : nullptr);
     if (e == hipSuccess && f.defer) c->dense_pending = 1;
     if (pev) c->prof_dense[c->prof_n - 1] = c->dn_iters < AGT_PROF_DENSE_MAX ? c->dn_iters : AGT_PROF_DENSE_MAX;
@@ -935,9 +945,9 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
     if (f.ride) {
         // frame t + 1 in its ring entry, as pyramid_build_on would leave it (the serial step reads no state_out from the ring)
         register_frame(c, nslot, next_frame, pitch, batch_stride, B, nullptr);
-        const long db1 = (long)c->lh[1] * c->lpitch[1], db2 = (long)c->lh[2] * c->lpitch[2];
-        agt_pyr2_args(next_frame, c->lw[0], c->lh[0], (long)pitch, (long)batch_stride, c->lmem[nslot][1], c->lpitch[1], db1,
-                      c->lmem[nslot][2], c->lpitch[2], db2, B, &npyr[0], &npyr[1]);
+        AgtLevel lv[AGT_MAX_LEVELS];
+        fill_levels(c, nslot, lv);
+        agt_pyr2_args(lv, B, npyr);
         c->prebuilt_t = t + 1;
     }
     AgtPnpParams p;
@@ -1042,8 +1052,11 @@ int agt_preprocess_bgr(agt_ctx* c, const uint8_t* d_bgr, size_t spitch, size_t s
     if (roi_x < 0 || roi_y < 0 || roi_w <= 0 || roi_h <= 0 || roi_x + roi_w > src_w || roi_y + roi_h > src_h) return AGT_ERR_ARG;
     if (spitch < (size_t)src_w * 3 || gpitch < (size_t)roi_w) return AGT_ERR_ARG;
     if (undistort && (!c->map1 || c->map_w != src_w || c->map_h != src_h)) return AGT_ERR_STATE;
-    hipError_t e = agt_launch_preprocess(c->stream, d_bgr, (long)spitch, (long)sbatch, src_w, src_h, c->map1, c->map2, src_w,
-                                         roi_x, roi_y, roi_w, roi_h, d_gray, (long)gpitch, (long)gbatch, undistort ? 1 : 0, 1, B);
+    AgtRemapArgs A = AgtRemapArgs();
+    A.src = d_bgr; A.spitch = (long)spitch; A.sbatch = (long)sbatch; A.sw = src_w; A.sh = src_h; A.map1 = c->map1; A.map2 = c->map2; A.mw = src_w;
+    A.rx = roi_x; A.ry = roi_y; A.rw = roi_w; A.rh = roi_h; A.dst = d_gray; A.dpitch = (long)gpitch; A.dbatch = (long)gbatch;
+    A.undistort = undistort ? 1 : 0; A.B = B;
+    hipError_t e = agt_launch_preprocess(c->stream, A, 1);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 

@@ -155,7 +155,9 @@ int agt_undistort_bgr(agt_ctx* c, const uint8_t* d_src, size_t spitch, size_t sb
     if (!c || !d_src || !d_dst || B <= 0) return AGT_ERR_ARG;
     if (!c->map1) return AGT_ERR_STATE;
     if (spitch < (size_t)c->map_w * 3 || dpitch < (size_t)c->map_w * 3) return AGT_ERR_ARG;
-    hipError_t e = agt_launch_preprocess(c->stream, d_src, (long)spitch, (long)sbatch, c->map_w, c->map_h, c->map1, c->map2, c->map_w,
-                                         0, 0, c->map_w, c->map_h, d_dst, (long)dpitch, (long)dbatch, 1, 0, B);
+    AgtRemapArgs A = AgtRemapArgs();
+    A.src = d_src; A.spitch = (long)spitch; A.sbatch = (long)sbatch; A.sw = c->map_w; A.sh = c->map_h; A.map1 = c->map1; A.map2 = c->map2; A.mw = c->map_w;
+    A.rw = c->map_w; A.rh = c->map_h; A.dst = d_dst; A.dpitch = (long)dpitch; A.dbatch = (long)dbatch; A.undistort = 1; A.B = B;
+    hipError_t e = agt_launch_preprocess(c->stream, A, 0);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }

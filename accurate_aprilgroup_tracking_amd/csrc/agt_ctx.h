@@ -109,6 +109,9 @@ struct agt_ctx {
     int* prof_dense;                         // per recorded frame: dense iterations whose launches carry events
 };
 
+// bytes between the streams of context-owned level l (>= 1)
+inline long level_bstride(const agt_ctx* c, int l) { return (long)c->lh[l] * c->lpitch[l]; }
+
 // agt_api.hip
 int hip_fail(agt_ctx* c, hipError_t e);
 int fill_camera(const double* K, const double* dist, int ndist, AgtCameraHost* cam, AgtTiltHost* tilt = nullptr);
@@ -120,6 +123,9 @@ int ms_pool_acquire(int device, hipStream_t out[3]);
 int dense_scratch(agt_ctx* c, size_t need, int B);
 int join_pipeline(agt_ctx* c);
 int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B);
+void fill_levels(const agt_ctx* c, int slot, AgtLevel* L);          // levels 0 .. eff_max_level of ring entry `slot` (level 0: as registered)
+int pyramid_levels_on(agt_ctx* c, hipStream_t stream, int slot, int l0, int B);      // builds levels l0 .. eff_max_level, each from the level below
+agt_dense::DenseParams dense_params_on(const agt_ctx* c);           // zeroed, with what every dense call takes from the context: scratch, damping
 int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                 const float* d_prev_pts, const uint8_t* d_prev_status, float* d_next_pts, uint8_t* d_status, float* d_err,
                 int n, int B, int crit_type, int crit_max_count, double crit_eps,

@@ -22,7 +22,6 @@
 // iters Gauss-Newton iterations = iters + 1 launches (round 2: 2 * iters + 1 re-seed launch); nothing synchronises.
 // No MFMA: the contraction is 6x6.
 #undef AGT_PNP_STAMPS
-#include <cstring>
 #include "agt_pnp_body.h"
 #include "agt_pyramid2_body.h"
 
@@ -227,41 +226,27 @@ __global__ __launch_bounds__(256) void dense_final_kernel(const DenseParams P)
 
 }  // namespace
 
-// rec == null: plain agt_dense_refine (done words cleared here, stats [B][8]).  rec != null: stage of the tracker -- the
-// done words and the start poses were written by the PnP epilogue of the same frame (done = pose not accepted), the
-// statistics go into the record; seed_pts / seed_status != null: the corner re-seed rides in the final launch.
-// partials: agt_dense_doubles(M, B) doubles.
-hipError_t agt_launch_dense(hipStream_t stream, const uint8_t* img, long pitch, long ibatch, int w, int h,
-                            const float* mxyz, const float* mt, int M,
-                            const float* obj, const float* ipts, const uint8_t* mask, int N,
-                            const AgtCameraHost& cam, double* pose, double* partials, double* stats, int* done,
-                            int B, int iters, double photo_weight, double mu, double* rec, float* seed_pts, uint8_t* seed_status,
-                            hipEvent_t* ev, int n_ev, const AgtPyrArgs* next_pyr, AgtDenseFinal* defer_final)
+// (contract: agt_kernels.h)
+hipError_t agt_launch_dense(hipStream_t stream, DenseParams P, int B, int iters, hipEvent_t* ev, int n_ev, const AgtPyrArgs* next_pyr, AgtDenseFinal* defer_final)
 {
-    static_assert(sizeof(DenseParams) <= sizeof(AgtDenseFinal::bytes), "AgtDenseFinal holds a DenseParams");
-    DenseParams P;
     P.n_pyr = 0;
     P.py0 = AgtPyrArgs(); P.py1 = AgtPyrArgs();
-    P.rec = rec; P.stats_stride = rec ? AGT_DENSE_STRIDE : 8;
-    if (rec) stats = rec + AGT_DN_PHOTO_RMS;
-    P.img = img; P.pitch = pitch; P.ibatch = ibatch; P.w = w; P.h = h;
-    P.mxyz = mxyz; P.mt = mt; P.M = M; P.obj = obj; P.ipts = ipts; P.mask = mask; P.N = N;
-    P.cam = cam; P.pose = pose; P.nblk = (M + 255) / 256; P.stats = stats; P.done = done;
-    P.partials = partials; P.pstride = (long)B * (P.nblk + 1) * DROW; P.ppose = partials + 2 * P.pstride;
-    P.photo_weight = photo_weight; P.mu = mu;
-    P.seed_pts = seed_pts; P.seed_status = seed_status;
-    hipError_t e = rec ? hipSuccess : hipMemsetAsync(done, 0, (size_t)B * sizeof(int), stream);
+    P.stats_stride = P.rec ? AGT_DENSE_STRIDE : 8;
+    if (P.rec) P.stats = P.rec + AGT_DN_PHOTO_RMS;
+    P.nblk = (P.M + 255) / 256;
+    P.pstride = (long)B * (P.nblk + 1) * DROW; P.ppose = P.partials + 2 * P.pstride;
+    hipError_t e = P.rec ? hipSuccess : hipMemsetAsync(P.done, 0, (size_t)B * sizeof(int), stream);
     for (int it = 0; it < iters && e == hipSuccess; it++) {
         P.iter = it;
         // (the geometric block's slot is always in the grid when a pyramid job rides along: block indices above nblk are tiles)
-        unsigned gx = (unsigned)(P.nblk + (N > 0 ? 1 : 0));
+        unsigned gx = (unsigned)(P.nblk + (P.N > 0 ? 1 : 0));
         size_t lds = sizeof(DenseShared);
         P.n_pyr = 0;
         // (in the SECOND launch when there is one: the first has no update prologue and is shorter than a pyramid tile's ~6 us --
         // riding there stretched it by 3.2 us; the later launches last ~7 us and hide the tiles completely)
         if (it == (iters > 1 ? 1 : 0) && next_pyr) {
             P.py0 = next_pyr[0]; P.py1 = next_pyr[1];
-            P.n_pyr = P.py0.gx * P.py0.gy;
+            P.n_pyr = agt_pyr_blocks(P.py0);
             gx = (unsigned)(P.nblk + 1 + P.n_pyr);
             lds = lds > (size_t)agt_pyr2::PYR2_LDS_BYTES ? lds : (size_t)agt_pyr2::PYR2_LDS_BYTES;
         }
@@ -270,26 +255,18 @@ hipError_t agt_launch_dense(hipStream_t stream, const uint8_t* img, long pitch, 
         if (ev && n_ev >= 2 && it == iters - 1) (void)hipEventRecord(ev[0], stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && defer_final) {
-        // clip submission: the last update and the re-seed ride in the next frame's LK launch (agt_step.hip lk_reseed_kernel)
-        P.iter = iters; P.n_pyr = 0;
-        memcpy(defer_final->bytes, &P, sizeof(P));
-        return e;
-    }
-    if (e == hipSuccess) {
-        P.iter = iters;
-        hipLaunchKernelGGL(dense_final_kernel, dim3(B), dim3(256), sizeof(DenseShared), stream, P);
-        if (ev && n_ev >= 2 && iters > 0) (void)hipEventRecord(ev[1], stream);
-        e = hipGetLastError();
-    }
-    return e;
+    if (e != hipSuccess) return e;
+    P.iter = iters; P.n_pyr = 0;
+    // clip submission: the last update and the re-seed ride in the next frame's LK launch (agt_step_dense.hip lk_reseed_kernel)
+    if (defer_final) { defer_final->P = P; return e; }
+    hipLaunchKernelGGL(dense_final_kernel, dim3(B), dim3(256), sizeof(DenseShared), stream, P);
+    if (ev && n_ev >= 2 && iters > 0) (void)hipEventRecord(ev[1], stream);
+    return hipGetLastError();
 }
 
 hipError_t agt_launch_dense_final(hipStream_t stream, const AgtDenseFinal& F, int B)
 {
-    DenseParams P;
-    memcpy(&P, F.bytes, sizeof(P));
-    hipLaunchKernelGGL(dense_final_kernel, dim3(B), dim3(256), sizeof(DenseShared), stream, P);
+    hipLaunchKernelGGL(dense_final_kernel, dim3(B), dim3(256), sizeof(DenseShared), stream, F.P);
     return hipGetLastError();
 }
 

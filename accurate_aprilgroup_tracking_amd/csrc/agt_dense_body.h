@@ -15,30 +15,6 @@ namespace agt_dense {
 constexpr int DN = 29;                 // 21 (upper JtJ) + 6 (Jt r) + r^2 + valid count
 constexpr int DROW = 32;               // doubles per block row in the partials buffer
 
-struct DenseParams {
-    const uint8_t* img; long pitch, ibatch; int w, h;
-    const float* mxyz; const float* mt; int M;
-    const float* obj; const float* ipts; const uint8_t* mask; int N;
-    AgtCameraHost cam;
-    double* pose;                      // [B][6]
-    double* partials;                  // [2][B][nblk + 1][DROW]: block rows, double-buffered by iteration parity
-    double* ppose;                     // [2][B][8]: linearisation point of iteration k + 1 (published by block 0 of launch k + 1)
-    long pstride;                      // doubles between the two row buffers
-    int nblk;
-    double* stats;                     // [B][stats_stride]: 5 values written per iteration
-    int stats_stride;
-    double* rec;                       // tracker stage: per-frame record [B][AGT_DENSE_STRIDE] (pose, refined flag, stats) or null
-    int* done;                         // [B]
-    double photo_weight, mu;
-    int iter;
-    float* seed_pts; uint8_t* seed_status;     // tracker stage with re-seed: the frame's corner set / LK status ([B][N][2], [B][N]) or null
-    // clip submission (agt_track_frames_dense): the two-level pyramid pass of the NEXT frame rides in the first accumulate launch
-    // as extra workgroups (blockIdx.x > nblk) -- it depends on nothing this frame computes, and alone it was a 6.5 us launch
-    // in the frame's serial chain
-    AgtPyrArgs py0, py1;
-    int n_pyr;                                 // tiles per stream (0 = none)
-};
-
 struct DenseShared {
     double wtot[4][DROW];
     double rows8[8][DROW];             // update prologue: partial sums of the previous iteration's rows

@@ -65,6 +65,13 @@ __device__ __forceinline__ float agt_uniform(float v)
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
+// AgtPnpParams::host_seq: the frame's record (written by this wave a moment ago, to host-mapped memory) is complete: tell the polling host thread
+__device__ __forceinline__ void agt_host_seq_store(unsigned long long* host_seq, unsigned long long value, bool writer_lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                  // system scope: the record's stores are performed first
+    if (writer_lane) __hip_atomic_store(host_seq, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---------------------------------------------------------------------------
 // FP64 geometry (OpenCV calibration.cpp semantics; see oracle/cv_pnp.c for the restatement)
 //

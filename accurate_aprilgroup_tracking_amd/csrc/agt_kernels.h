@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstddef>
+#include <type_traits>
 #include "../../include/agt_hip.h"
 
 struct AgtLevel {
@@ -37,11 +39,20 @@ struct AgtPyrArgs {
     const uint8_t* src; uint8_t* dst;
     long spitch, sbatch, dpitch, dbatch;
     int sw, sh, dw, dh;
-    int gx, gy, B;            // tile grid (x, y) and images
-    int pad;
+    int gx, gy, B;            // tiled form: tile grid (x, y); register-rolling form: gx = workgroups per image, gy = 1.  B: images
+    int strip_rows;           // output rows per strip of the register-rolling form (two-level pass: level-2 rows); 0 = tiled form
     int xshift;               // log2 of the XCD count the block order is laid out for (agt_xcd_order); set by the launchers
-    int rsv_;                 // two-level rolling pass: 1 = every strip top-down (diagnostic A/B; 0 = alternating directions)
+    int topdown;              // two-level rolling pass: 1 = every strip top-down (diagnostic A/B; 0 = alternating directions)
 };
+__host__ __device__ inline bool agt_pyr_rolling(const AgtPyrArgs& A) { return A.strip_rows != 0; }
+__host__ __device__ inline int agt_pyr_blocks(const AgtPyrArgs& A) { return A.gx * A.gy; }        // workgroups per image, either form
+// (the device reads these members from the kernel-argument segment by offset: agt_step.hip pyr_role)
+#define AGT_PYR_AT(m, o) static_assert(offsetof(AgtPyrArgs, m) == o, "AgtPyrArgs layout: " #m)
+AGT_PYR_AT(src, 0); AGT_PYR_AT(dst, 8); AGT_PYR_AT(spitch, 16); AGT_PYR_AT(sbatch, 24); AGT_PYR_AT(dpitch, 32); AGT_PYR_AT(dbatch, 40);
+AGT_PYR_AT(sw, 48); AGT_PYR_AT(sh, 52); AGT_PYR_AT(dw, 56); AGT_PYR_AT(dh, 60); AGT_PYR_AT(gx, 64); AGT_PYR_AT(gy, 68); AGT_PYR_AT(B, 72);
+AGT_PYR_AT(strip_rows, 76); AGT_PYR_AT(xshift, 80); AGT_PYR_AT(topdown, 84);
+#undef AGT_PYR_AT
+static_assert(sizeof(AgtPyrArgs) == 88, "AgtPyrArgs layout");
 
 #define AGT_MAX_GROUP 32         // frames one fused launch may advance each pipeline stage by (the per-frame tables are kernel arguments: 7.4 KB with the parameters)
 
@@ -55,7 +66,8 @@ struct AgtLkVerdict {
     int pad_;
 };
 
-#define AGT_LK_FLAG_COTENANT 0x20000    // internal launch flag: the context declared co-tenancy (agt_lk_occupancy_cu): tracker waves at issue priority 1
+#define AGT_LK_FLAG_GENERAL  0x10000    // internal launch flags: the general body for every corner (diagnostic: AGT_LK_RS=0) ...
+#define AGT_LK_FLAG_COTENANT 0x20000    // ... the context declared co-tenancy (agt_lk_occupancy_cu): tracker waves at issue priority 1
 struct AgtLkParams {
     AgtLevel prev[AGT_MAX_LEVELS];
     AgtLevel next[AGT_MAX_LEVELS];
@@ -63,7 +75,7 @@ struct AgtLkParams {
     int n;                    // points per stream
     int max_count;            // criteria, already clamped
     double eps2;              // epsilon^2
-    int flags;                // AGT_LK_* of the ABI in the low bits; internal: 0x10000 = general body for every corner (diagnostic), AGT_LK_FLAG_COTENANT
+    int flags;                // AGT_LK_* of the ABI in the low bits; internal: AGT_LK_FLAG_GENERAL, AGT_LK_FLAG_COTENANT
     double min_eig_threshold;
     const float* prev_pts;    // [B][n][2]
     const uint8_t* prev_status;   // [B][n] or null: tracker mode, a corner lost in an earlier frame stays lost (position carried)
@@ -128,13 +140,6 @@ struct AgtPnpParams {
     unsigned long long host_seq_base;
 };
 
-// the frame's record (written by this wave a moment ago, to host-mapped memory) is complete: tell the polling host thread
-__device__ __forceinline__ void agt_host_seq_store(unsigned long long* host_seq, unsigned long long value, bool writer_lane)
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                  // system scope: the record's stores are performed first
-    if (writer_lane) __hip_atomic_store(host_seq, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // device-resident per-stream tracker state: the attributes of PoseDetector
 // (detect_pose.py:74-83) that _estimate_pose mutates
 struct AgtTrackState {
@@ -159,8 +164,8 @@ struct AgtTrackState {
 // chains are serial across frames; the pyramid stages treat the frames as a batch)
 struct AgtStepParams {
     AgtPyrArgs pyr[AGT_MAX_LEVELS - 1];                        // geometry; src / dst per frame in AgtStepTables
-    int pyr_fused;                    // != 0: stage 0 builds levels 1 AND 2 in one pass (pyr[0].gx / gy = its tile grid, pyr[1] =
-    int pyr_pad;                      // the level 1 -> 2 geometry, pyr_dst[1] = the level-2 buffers); stage 1 then has no blocks
+    int pyr_fused;                    // != 0: stage 0 builds levels 1 AND 2 in one pass (agt_step_set_two_level); stage 1 then has no blocks
+    int pyr_pad;
     int pyr_nf[AGT_MAX_LEVELS - 1];
     int n_pyr[AGT_MAX_LEVELS - 1];    // blocks of each pyramid stage = tiles x streams x frames (0 = stage idle)
     AgtLkParams lk;                   // geometry of prev[] / next[], criteria; images per frame in AgtStepTables
@@ -173,6 +178,9 @@ struct AgtStepParams {
     int xshift;                       // XCD-aware block orders of the LK and pyramid roles (agt_xcd_order); set by the launchers
     int rsv_;
 };
+// Stage 0 as the two-level pass: A[0] = the level 0 -> 1 half, which also carries the pass's grid (agt_pyr2_plan), A[1] = the level 1 -> 2
+// half, which rides in stage 1's slots (pyr[1]; its level-2 buffers per frame in AgtStepTables::pyr_dst[1])
+inline void agt_step_set_two_level(AgtStepParams& S, const AgtPyrArgs* A) { S.pyr[0] = A[0]; S.pyr[1] = A[1]; S.pyr_fused = 1; }
 
 // per-frame pointer tables of the fused launch: its SECOND kernel argument.  They are indexed with run-time
 // frame numbers and therefore read from the kernel-argument segment directly (never through a by-value copy).
@@ -207,17 +215,61 @@ struct AgtProjParams {
     unsigned long long host_seq_base;
 };
 
+// The dense stage's parameter block (agt_dense.hip: specification, mapping; agt_dense_body.h: the update).  The caller fills frame, model,
+// corner set, camera, pose, scratch (partials, done) and weights; agt_launch_dense derives the rest.
+namespace agt_dense {
+struct DenseParams {
+    const uint8_t* img; long pitch, ibatch; int w, h;
+    const float* mxyz; const float* mt; int M;
+    const float* obj; const float* ipts; const uint8_t* mask; int N;
+    AgtCameraHost cam;
+    double* pose;                      // [B][6]
+    double* partials;                  // [2][B][nblk + 1][DROW]: block rows, double-buffered by iteration parity
+    double* ppose;                     // [2][B][8]: linearisation point of iteration k + 1 (published by block 0 of launch k + 1)
+    long pstride;                      // doubles between the two row buffers
+    int nblk;
+    double* stats;                     // [B][stats_stride]: 5 values written per iteration
+    int stats_stride;
+    double* rec;                       // tracker stage: per-frame record [B][AGT_DENSE_STRIDE] (pose, refined flag, stats) or null
+    int* done;                         // [B]
+    double photo_weight, mu;
+    int iter;
+    float* seed_pts; uint8_t* seed_status;     // tracker stage with re-seed: the frame's corner set / LK status ([B][N][2], [B][N]) or null
+    // clip submission (agt_track_frames_dense): the two-level pyramid pass of the NEXT frame rides in the first accumulate launch
+    // as extra workgroups (blockIdx.x > nblk) -- it depends on nothing this frame computes, and alone it was a 6.5 us launch
+    // in the frame's serial chain
+    AgtPyrArgs py0, py1;
+    int n_pyr;                                 // tiles per stream (0 = none)
+};
+}  // namespace agt_dense
+
+// The source-side view of agt_preproc.hip's RemapParams (the kernel's argument): what agt_launch_preprocess is given
+struct AgtRemapArgs {
+    const uint8_t* src; long spitch, sbatch; int sw, sh;
+    const short2* map1; const unsigned short* map2; int mw;      // maps cover mw x (any) pixels
+    int rx, ry, rw, rh;                                          // output window in map coordinates
+    uint8_t* dst; long dpitch, dbatch;
+    int undistort;                                               // 0: taps come straight from (x, y)
+    int B;                                                       // images (gray path: flattened work order)
+    int xshift;                                                  // log2 of the XCD count the gray path's band order is laid out for; set by the launcher
+};
+
+// The two compiled pyramid depths of the LK kernels: NLEV = 3 for max_level < 3, AGT_MAX_LEVELS beyond.  f(std::integral_constant<int, NLEV>)
+template <class F> inline auto agt_with_nlev(int max_level, F&& f)
+{
+    return max_level < 3 ? f(std::integral_constant<int, 3>()) : f(std::integral_constant<int, AGT_MAX_LEVELS>());
+}
+
 void agt_pyr_grid(int dw, int dh, int* gx, int* gy);
-void agt_pyr_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int frames);
+void agt_pyr_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int frames);     // tiled or register-rolling form of one pyrDown pass (agt_pyramid.hip)
 hipError_t agt_launch_pyr_upload2(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, uint8_t* copy, long cpitch,
                                   uint8_t* dst1, long dpitch1, uint8_t* dst2, long dpitch2);     // fused upload + two-level pyramid of one frame (agt_pyramid.hip)
-void agt_pyr2_plan(AgtPyrArgs* A0, AgtPyrArgs* A1, uintptr_t src_align, uintptr_t dst_align, int frames, int oh_cap = 16);     // the same for the two-level pass      // tiled or register-rolling form of one pyrDown pass (agt_pyramid.hip)
+// The two-level pass lv[0] -> lv[1] -> lv[2] as the pair of argument blocks A[0], A[1] its body takes: the geometry (tiled form) ...
+void agt_pyr2_args(const AgtLevel* lv, int B, AgtPyrArgs* A);
+void agt_pyr2_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int frames, int oh_cap = 16);     // ... its form (tiled or register-rolling) ...
+hipError_t agt_launch_pyr_down2(hipStream_t stream, const AgtPyrArgs* A);                                     // ... and the launch of what was planned
 void agt_pyr2_grid(int w2, int h2, int* gx, int* gy);           // tile grid of the two-level pass (64 x 16 tiles of L2)
-int agt_pyr2_lds_bytes(void);
-hipError_t agt_launch_pyr_down2(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, long sbatch,
-                                uint8_t* dst1, long dpitch1, long dbatch1, uint8_t* dst2, long dpitch2, long dbatch2, int B);
-hipError_t agt_launch_pyr_down(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, long sbatch,
-                               uint8_t* dst, long dpitch, long dbatch, int B);
+hipError_t agt_launch_pyr_down(hipStream_t stream, const AgtLevel& src, const AgtLevel& dst, int B);          // dst.w, dst.h are implied: (w + 1) / 2
 // waves: 0 = by batch size (agt_lk_wide), 1 / 4 = that many waves per corner (win 21 only)
 hipError_t agt_launch_lk(hipStream_t stream, const AgtLkParams& p, int win, int B, int waves = 0);
 // ride != null (two argument blocks of agt_pyr2_args): the two-level pyramid pass of another frame as extra workgroups of the
@@ -227,24 +279,18 @@ bool agt_pnp_can_ride(int n);
 hipError_t agt_launch_project(hipStream_t stream, const AgtProjParams& p, int B);
 hipError_t agt_launch_undistort_map(hipStream_t stream, const double* K, const AgtCameraHost& cam, const AgtTiltHost& tilt, const double* ir,
                                     int w, int h, short2* map1, unsigned short* map2);
-hipError_t agt_launch_preprocess(hipStream_t stream, const uint8_t* src, long spitch, long sbatch, int sw, int sh,
-                                 const short2* map1, const unsigned short* map2, int mw,
-                                 int rx, int ry, int rw, int rh, uint8_t* dst, long dpitch, long dbatch,
-                                 int undistort, int gray, int B);
+hipError_t agt_launch_preprocess(hipStream_t stream, const AgtRemapArgs& A, int gray);
 // The dense stage's last step (final Gauss-Newton update + corner re-seed) handed on to the LK launch of the NEXT frame instead of
-// being launched: the stage's parameter block as agt_dense.hip fills it (opaque here; agt_step.hip agt_launch_lk_reseed reads it)
-struct AgtDenseFinal { alignas(8) unsigned char bytes[776]; };
+// being launched: the stage's parameter block as agt_launch_dense left it (agt_step_dense.hip agt_launch_lk_reseed reads it)
+struct AgtDenseFinal { agt_dense::DenseParams P; };
 hipError_t agt_launch_lk_reseed(hipStream_t stream, const struct AgtStepParams& S, const struct AgtStepTables& T, int win, const AgtDenseFinal* F, const struct AgtPyrArgs* ride = nullptr);
 hipError_t agt_launch_dense_final(hipStream_t stream, const AgtDenseFinal& F, int B);      // the deferred step as its own launch after all
-hipError_t agt_launch_dense(hipStream_t stream, const uint8_t* img, long pitch, long ibatch, int w, int h,
-                            const float* mxyz, const float* mt, int M,
-                            const float* obj, const float* ipts, const uint8_t* mask, int N,
-                            const AgtCameraHost& cam, double* pose, double* partials, double* stats, int* done,
-                            int B, int iters, double photo_weight, double mu, double* rec, float* seed_pts, uint8_t* seed_status,
+// P.rec == null: plain agt_dense_refine (done words cleared here, P.stats [B][8]).  P.rec != null: stage of the tracker -- the done words
+// and the start poses were written by the PnP epilogue of the same frame (done = pose not accepted), the statistics go into the record;
+// P.seed_pts / seed_status != null: the corner re-seed rides in the final launch.  P.partials: agt_dense_doubles(M, B) doubles.
+// ev: profiling events; next_pyr: the riding two-level pass (agt_pyr2_args); defer_final: the last step is left there, not launched
+hipError_t agt_launch_dense(hipStream_t stream, agt_dense::DenseParams P, int B, int iters,
                             hipEvent_t* ev = nullptr, int n_ev = 0, const AgtPyrArgs* next_pyr = nullptr, AgtDenseFinal* defer_final = nullptr);
-// geometry of the two-level pyramid pass (agt_pyramid.hip) as the pair of argument blocks its body takes
-void agt_pyr2_args(const uint8_t* src, int sw, int sh, long spitch, long sbatch, uint8_t* dst1, long dpitch1, long dbatch1,
-                   uint8_t* dst2, long dpitch2, long dbatch2, int B, AgtPyrArgs* A0, AgtPyrArgs* A1);
 int agt_dense_blocks(int M);
 size_t agt_dense_doubles(int M, int B);
 bool agt_lk_window_supported(int win);

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
         // ~3 % of corners whose window touches the image border at SOME level took for ALL levels -- and the launch lasts as long as its
         // slowest wave.  The border is mostly reached at the coarsest level only: the general body now tracks just the coarse levels that
         // need it and hands the position to the row-segment body for the fine ones -- two bodies in sequence, each register-allocated alone.)
-        const int fine = (pst != 0 && !(P.flags & 0x10000)) ? agt_uniform(agt_lk::rs_interior_levels<NLEV>(ppx, ppy, P.max_level, P.prev[0].w, P.prev[0].h)) : 0;
+        const int fine = (pst != 0 && !(P.flags & AGT_LK_FLAG_GENERAL)) ? agt_uniform(agt_lk::rs_interior_levels<NLEV>(ppx, ppy, P.max_level, P.prev[0].w, P.prev[0].h)) : 0;
         // One split point is compiled: the coarsest level alone (by far the common case -- its window covers four times the ground of the
         // finest one's) of a full-depth pyramid; every other corner that needs the general body somewhere gets it everywhere, as before.
         // One call site per body: the general one runs all levels, result included, or the coarsest alone; the row-segment one the rest.
@@ -80,12 +80,13 @@ hipError_t launch_lk_t(hipStream_t stream, const AgtLkParams& p_in, int B)
     const long total = (long)p.n * B;
     if (total <= 0 || total > (1L << 30)) return hipErrorInvalidValue;
     const dim3 grid(agt_xcd_grid(total, p.xshift)), block(AGT_WAVE * NW);
-    constexpr int OCC = (WIN == 21 && NW == 1) ? 4 : 1;
-    // (pyramids of more than three levels: the six-level one-wave body keeps six levels' tile bookkeeping alive and spilled 34 VGPRs
-    // at the 128 registers of four waves per SIMD; it gets the 168 of three -- round 5, no scratch left in the library)
-    constexpr int OCC6 = (WIN == 21 && NW == 1) ? 3 : 1;
-    if (p.max_level < 3) hipLaunchKernelGGL((lk_kernel<WIN, NW, 3, OCC>), grid, block, lds, stream, p, (int)total);
-    else hipLaunchKernelGGL((lk_kernel<WIN, NW, AGT_MAX_LEVELS, OCC6>), grid, block, lds, stream, p, (int)total);
+    agt_with_nlev(p.max_level, [&](auto nlev) {
+        constexpr int NLEV = decltype(nlev)::value;
+        // (pyramids of more than three levels: the six-level one-wave body keeps six levels' tile bookkeeping alive and spilled 34 VGPRs
+        // at the 128 registers of four waves per SIMD; it gets the 168 of three -- round 5, no scratch left in the library)
+        constexpr int OCC = (WIN == 21 && NW == 1) ? (NLEV == 3 ? 4 : 3) : 1;
+        hipLaunchKernelGGL((lk_kernel<WIN, NW, NLEV, OCC>), grid, block, lds, stream, p, (int)total);
+    });
     return hipGetLastError();
 }
 
@@ -134,7 +135,7 @@ bool agt_lk_wide(int n, int B)
 hipError_t agt_launch_lk(hipStream_t stream, const AgtLkParams& p_in, int win, int B, int waves)
 {
     AgtLkParams p = p_in;
-    if (!AGT_KNOB("AGT_LK_RS", 1)) p.flags |= 0x10000;     // (knobs: AGT_LK_RS=0 keeps every corner on the general body; flag bit 16, internal)
+    if (!AGT_KNOB("AGT_LK_RS", 1)) p.flags |= AGT_LK_FLAG_GENERAL;     // (knobs: AGT_LK_RS=0 keeps every corner on the general body)
     switch (win) {
     // (2 and 8 waves per corner were measured too: 2 loses to 1 on big batches -- 60 vs 42 us at 64 streams --, 8 loses
     // to 4 on small ones -- 19.5 vs 17.8 us)

@@ -61,15 +61,7 @@ __global__ __launch_bounds__(256) void undistort_map_kernel(const MapParams P)
     P.map2[o] = (unsigned short)((iv & (INTER_TAB - 1)) * INTER_TAB + (iu & (INTER_TAB - 1)));
 }
 
-struct RemapParams {
-    const uint8_t* src; long spitch, sbatch; int sw, sh;
-    const short2* map1; const unsigned short* map2; int mw;      // maps cover mw x (any) pixels
-    int rx, ry, rw, rh;                                          // output window in map coordinates
-    uint8_t* dst; long dpitch, dbatch;
-    int undistort;                                               // 0: taps come straight from (x, y)
-    int B;                                                       // images (gray path: flattened work order)
-    int xshift;                                                  // log2 of the XCD count the gray path's band order is laid out for
-};
+struct RemapParams : AgtRemapArgs {};      // (the kernels' argument type, by this name in their symbols)
 
 struct __attribute__((packed)) Tap6 { uint32_t lo; uint16_t hi; };
 
@@ -256,19 +248,13 @@ hipError_t agt_launch_undistort_map(hipStream_t stream, const double* K, const A
     return hipGetLastError();
 }
 
-hipError_t agt_launch_preprocess(hipStream_t stream, const uint8_t* src, long spitch, long sbatch, int sw, int sh,
-                                 const short2* map1, const unsigned short* map2, int mw,
-                                 int rx, int ry, int rw, int rh, uint8_t* dst, long dpitch, long dbatch,
-                                 int undistort, int gray, int B)
+hipError_t agt_launch_preprocess(hipStream_t stream, const AgtRemapArgs& A, int gray)
 {
     RemapParams P;
-    P.src = src; P.spitch = spitch; P.sbatch = sbatch; P.sw = sw; P.sh = sh;
-    P.map1 = map1; P.map2 = map2; P.mw = mw; P.rx = rx; P.ry = ry; P.rw = rw; P.rh = rh;
-    P.dst = dst; P.dpitch = dpitch; P.dbatch = dbatch; P.undistort = undistort;
-    P.B = B;
+    static_cast<AgtRemapArgs&>(P) = A;
     P.xshift = agt_chip_current().xshift;
-    const int nseg = (rw + 255) / 256, bands = (rh + 7) / 8, X = 1 << P.xshift;
-    if (gray) hipLaunchKernelGGL(preprocess_kernel<true>, dim3(2 * X * nseg, B, (bands + X - 1) / X), dim3(256), 0, stream, P);
-    else hipLaunchKernelGGL(preprocess_kernel<false>, dim3((rw + 255) / 256, rh, B), dim3(256), 0, stream, P);
+    const int nseg = (A.rw + 255) / 256, bands = (A.rh + 7) / 8, X = 1 << P.xshift;
+    if (gray) hipLaunchKernelGGL(preprocess_kernel<true>, dim3(2 * X * nseg, A.B, (bands + X - 1) / X), dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(preprocess_kernel<false>, dim3((A.rw + 255) / 256, A.rh, A.B), dim3(256), 0, stream, P);
     return hipGetLastError();
 }

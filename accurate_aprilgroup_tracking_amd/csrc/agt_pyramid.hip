@@ -23,7 +23,7 @@ __global__ __launch_bounds__(agt_pyr::NT) void pyr_down_kernel(const AgtPyrArgs 
     agt_pyr::pyr_down_body(A, r - by * A.gx, by, A.src + (long)bz * A.sbatch, A.dst + (long)bz * A.dbatch, lds);
 }
 
-// register-rolling form (agt_pyramid3_body.h): A.gx = workgroups per image, A.pad = output rows per strip; same XCD-aware order
+// register-rolling form (agt_pyramid3_body.h): A.gx = workgroups per image, A.strip_rows = output rows per strip; same XCD-aware order
 __global__ __launch_bounds__(agt_pyr::NT) void pyr_roll_kernel(const AgtPyrArgs A)
 {
     const int t = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, A.xshift);
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(agt_pyr::NT) void pyr_upload2_kernel(const AgtPyrAr
 }
 
 // two levels per pass, register-rolling form with alternating strip directions (agt_pyramid4_body.h): A0.gx = workgroups per image,
-// A0.pad = level-2 rows per strip
+// A0.strip_rows = level-2 rows per strip
 __global__ __launch_bounds__(agt_pyr::NT) void pyr_roll2_kernel(const AgtPyrArgs A0, const AgtPyrArgs A1)
 {
     const int t = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, A0.xshift);
@@ -71,29 +71,26 @@ void agt_pyr2_grid(int w2, int h2, int* gx, int* gy)
     *gx = (w2 + agt_pyr2::TW2 - 1) / agt_pyr2::TW2;
     *gy = (h2 + agt_pyr2::TH2 - 1) / agt_pyr2::TH2;
 }
-int agt_pyr2_lds_bytes(void) { return agt_pyr2::PYR2_LDS_BYTES; }
 
-void agt_pyr2_args(const uint8_t* src, int sw, int sh, long spitch, long sbatch, uint8_t* dst1, long dpitch1, long dbatch1,
-                   uint8_t* dst2, long dpitch2, long dbatch2, int B, AgtPyrArgs* pA0, AgtPyrArgs* pA1)
+void agt_pyr2_args(const AgtLevel* lv, int B, AgtPyrArgs* A)
 {
-    AgtPyrArgs& A0 = *pA0; AgtPyrArgs& A1 = *pA1;
-    A0.src = src; A0.sw = sw; A0.sh = sh; A0.spitch = spitch; A0.sbatch = sbatch;
-    A0.dst = dst1; A0.dw = (sw + 1) / 2; A0.dh = (sh + 1) / 2; A0.dpitch = dpitch1; A0.dbatch = dbatch1;
-    A1.src = dst1; A1.sw = A0.dw; A1.sh = A0.dh; A1.spitch = dpitch1; A1.sbatch = dbatch1;
-    A1.dst = dst2; A1.dw = (A0.dw + 1) / 2; A1.dh = (A0.dh + 1) / 2; A1.dpitch = dpitch2; A1.dbatch = dbatch2;
-    agt_pyr2_grid(A1.dw, A1.dh, &A0.gx, &A0.gy);              // the tile grid of the pass rides in A0
-    A1.gx = A0.gx; A1.gy = A0.gy;
-    A0.B = A1.B = B; A0.pad = A1.pad = 0;
-    A0.xshift = A1.xshift = agt_chip_current().xshift; A0.rsv_ = A1.rsv_ = 0;
+    for (int k = 0; k < 2; k++) {
+        A[k].src = lv[k].ptr; A[k].sw = lv[k].w; A[k].sh = lv[k].h; A[k].spitch = lv[k].pitch; A[k].sbatch = lv[k].bstride;
+        A[k].dst = const_cast<uint8_t*>(lv[k + 1].ptr); A[k].dw = (lv[k].w + 1) / 2; A[k].dh = (lv[k].h + 1) / 2; A[k].dpitch = lv[k + 1].pitch; A[k].dbatch = lv[k + 1].bstride;
+        A[k].B = B; A[k].strip_rows = 0;
+        A[k].xshift = agt_chip_current().xshift; A[k].topdown = 0;
+    }
+    agt_pyr2_grid(A[1].dw, A[1].dh, &A[0].gx, &A[0].gy);              // the tile grid of the pass rides in A[0]
+    A[1].gx = A[0].gx; A[1].gy = A[0].gy;
 }
 
-// The register-rolling form of the two-level pass where it applies: A0.pad = level-2 rows per strip, A0.gx = workgroups per image,
-// A0.gy = 1 (A1 likewise); else the tiled form is left as agt_pyr2_args set it up (A0.pad = 0).  src_align / dst_align: OR of every
+// The register-rolling form of the two-level pass where it applies: strip_rows = level-2 rows per strip, gx = workgroups per image,
+// gy = 1 (in both blocks); else the tiled form as agt_pyr2_args sets it up (strip_rows = 0).  src_align / dst_align: OR of every
 // source / destination address of the launch (both destination levels); frames: images per stream in the launch.
-void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintptr_t dst_align, int frames, int oh_cap)
+void agt_pyr2_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int frames, int oh_cap)
 {
-    AgtPyrArgs& A0 = *pA0; AgtPyrArgs& A1 = *pA1;
-    A0.pad = A1.pad = 0;
+    AgtPyrArgs& A0 = A[0]; AgtPyrArgs& A1 = A[1];
+    A0.strip_rows = A1.strip_rows = 0;
     agt_pyr2_grid(A1.dw, A1.dh, &A0.gx, &A0.gy);
     A1.gx = A0.gx; A1.gy = A0.gy;
     const bool ok = ((src_align | (uintptr_t)A0.spitch | (uintptr_t)A0.sbatch | (uintptr_t)A0.sw) & 15) == 0 &&
@@ -111,7 +108,7 @@ void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintpt
     int want = images >= 16 ? 1 : 0;
     // knobs: AGT_PYR4=0 / 1 forces the choice, AGT_PYR4_OH=n the strip height, AGT_PYR4_REV=0 top-down strips only
     { const long on = AGT_KNOB("AGT_PYR4", -1); if (on >= 0) want = (int)on; }
-    A0.rsv_ = A1.rsv_ = AGT_KNOB("AGT_PYR4_REV", 1) ? 0 : 1;
+    A0.topdown = A1.topdown = AGT_KNOB("AGT_PYR4_REV", 1) ? 0 : 1;
     if (!ok || !want) return;
     // strip height (level-2 rows, even): ~2 waves on each SIMD where the launch has that many units (the pass shares the chip with
     // the LK kernels of other batches; measured on 64 x 720p inside the pipelined step: oh2 = 4: 53.5 us, 6: 50.3, 8: 48.8-49.1,
@@ -131,7 +128,7 @@ void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintpt
     if (oh_cap < Q) oh_cap = Q;
     oh = oh < Q ? Q : (oh > oh_cap ? oh_cap : oh);
     { const long f = AGT_KNOB("AGT_PYR4_OH", 0); if (f > 0) oh = (int)(f + Q - 1) / Q * Q; }
-    A0.pad = A1.pad = oh;
+    A0.strip_rows = A1.strip_rows = oh;
     A0.gx = A1.gx = agt_pyr4::roll2_blocks(A0.sw, A1.dh, oh);
     A0.gy = A1.gy = 1;
 }
@@ -141,8 +138,11 @@ void agt_pyr2_plan(AgtPyrArgs* pA0, AgtPyrArgs* pA1, uintptr_t src_align, uintpt
 hipError_t agt_launch_pyr_upload2(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, uint8_t* copy, long cpitch,
                                   uint8_t* dst1, long dpitch1, uint8_t* dst2, long dpitch2)
 {
-    AgtPyrArgs A0, A1;
-    agt_pyr2_args(src, sw, sh, spitch, 0, dst1, dpitch1, 0, dst2, dpitch2, 0, 1, &A0, &A1);
+    const int w1 = (sw + 1) / 2, h1 = (sh + 1) / 2;
+    const AgtLevel lv[3] = { { src, spitch, 0, sw, sh }, { dst1, dpitch1, 0, w1, h1 }, { dst2, dpitch2, 0, (w1 + 1) / 2, (h1 + 1) / 2 } };
+    AgtPyrArgs A[2];
+    agt_pyr2_args(lv, 1, A);
+    AgtPyrArgs& A0 = A[0]; AgtPyrArgs& A1 = A[1];
     const bool ok = (((uintptr_t)src | (uintptr_t)spitch | (uintptr_t)sw | (uintptr_t)copy | (uintptr_t)cpitch) & 15) == 0 &&
                     (((uintptr_t)dst1 | (uintptr_t)dpitch1) & 7) == 0 && (((uintptr_t)dst2 | (uintptr_t)dpitch2) & 3) == 0 &&
                     sw >= 32 && sh >= 32 && (long)sh * spitch < (1L << 31) && (long)sh * cpitch < (1L << 31) && (long)A0.dh * dpitch1 < (1L << 31);
@@ -150,23 +150,19 @@ hipError_t agt_launch_pyr_upload2(hipStream_t stream, const uint8_t* src, int sw
     // two level-2 rows per strip (17 level-0 rows a lane): the most units one frame gives, measured 22.9 us from pinned host memory
     // (4: 24.7, 8: 26.2); the rows a strip reads twice come out of the L2, not over PCIe again
     const int oh = agt_pyr4::L2_PER_TRIP;
-    A0.pad = A1.pad = oh;
+    A0.strip_rows = A1.strip_rows = oh;
     A0.gx = A1.gx = agt_pyr4::roll2_blocks(sw, A1.dh, oh);
     A0.gy = A1.gy = 1;
     hipLaunchKernelGGL(pyr_upload2_kernel, dim3(agt_xcd_grid(A0.gx, A0.xshift)), dim3(agt_pyr::NT), 0, stream, A0, A1, copy, (int)cpitch);
     return hipGetLastError();
 }
 
-// src (sw x sh) -> dst1 ((sw+1)/2 x (sh+1)/2) -> dst2, both written, one launch
-hipError_t agt_launch_pyr_down2(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, long sbatch,
-                                uint8_t* dst1, long dpitch1, long dbatch1, uint8_t* dst2, long dpitch2, long dbatch2, int B)
+// the two-level pass as agt_pyr2_args + agt_pyr2_plan left it in A[0], A[1]: both levels written, one launch
+hipError_t agt_launch_pyr_down2(hipStream_t stream, const AgtPyrArgs* A)
 {
-    AgtPyrArgs A0, A1;
-    agt_pyr2_args(src, sw, sh, spitch, sbatch, dst1, dpitch1, dbatch1, dst2, dpitch2, dbatch2, B, &A0, &A1);
-    agt_pyr2_plan(&A0, &A1, (uintptr_t)src, (uintptr_t)dst1 | (uintptr_t)dst2, 1);
-    const long tiles = (long)A0.gx * A0.gy * B;
-    if (A0.pad) hipLaunchKernelGGL(pyr_roll2_kernel, dim3(agt_xcd_grid(tiles, A0.xshift)), dim3(agt_pyr::NT), 0, stream, A0, A1);
-    else hipLaunchKernelGGL(pyr_down2_kernel, dim3(agt_xcd_grid(tiles, A0.xshift)), dim3(agt_pyr::NT), agt_pyr2::PYR2_LDS_BYTES, stream, A0, A1);
+    const dim3 grid(agt_xcd_grid((long)agt_pyr_blocks(A[0]) * A[0].B, A[0].xshift));
+    if (agt_pyr_rolling(A[0])) hipLaunchKernelGGL(pyr_roll2_kernel, grid, dim3(agt_pyr::NT), 0, stream, A[0], A[1]);
+    else hipLaunchKernelGGL(pyr_down2_kernel, grid, dim3(agt_pyr::NT), agt_pyr2::PYR2_LDS_BYTES, stream, A[0], A[1]);
     return hipGetLastError();
 }
 
@@ -177,13 +173,13 @@ void agt_pyr_grid(int dw, int dh, int* gx, int* gy)
 }
 
 // Geometry of one pyrDown pass for A.src / A.dst (pointers, pitches, sizes and B filled in): the register-rolling form where
-// it applies (A.pad = output rows per strip, A.gx = workgroups per image, A.gy = 1), else the tiled form (A.pad = 0, tile grid).
+// it applies (A.strip_rows = output rows per strip, A.gx = workgroups per image, A.gy = 1), else the tiled form (strip_rows = 0, tile grid).
 // `src_align` / `dst_align`: OR of every source / destination address the launch will see (frames of a group, batch strides).
 void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int frames)
 {
     AgtPyrArgs& A = *pA;
-    A.pad = 0;
-    A.xshift = agt_chip_current().xshift; A.rsv_ = 0;
+    A.strip_rows = 0;
+    A.xshift = agt_chip_current().xshift; A.topdown = 0;
     agt_pyr_grid(A.dw, A.dh, &A.gx, &A.gy);
     const bool ok = ((src_align | (uintptr_t)A.spitch | (uintptr_t)A.sbatch | (uintptr_t)A.sw) & 15) == 0 &&
                     ((dst_align | (uintptr_t)A.dpitch | (uintptr_t)A.dbatch) & 7) == 0 &&
@@ -202,21 +198,20 @@ void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int 
     int oh = (int)(A.dh / strips) & ~3;
     oh = oh < 4 ? 4 : (oh > 16 ? 16 : oh);
     { const long f = AGT_KNOB("AGT_PYR3_OH", 0); if (f > 0) oh = (int)f & ~3; }
-    A.pad = oh;
+    A.strip_rows = oh;
     A.gx = agt_pyr3::roll_blocks(A.sw, A.dh, oh);
     A.gy = 1;
 }
 
-hipError_t agt_launch_pyr_down(hipStream_t stream, const uint8_t* src, int sw, int sh, long spitch, long sbatch,
-                               uint8_t* dst, long dpitch, long dbatch, int B)
+hipError_t agt_launch_pyr_down(hipStream_t stream, const AgtLevel& src, const AgtLevel& dst, int B)
 {
     AgtPyrArgs A;
-    A.src = src; A.sw = sw; A.sh = sh; A.spitch = spitch; A.sbatch = sbatch;
-    A.dst = dst; A.dw = (sw + 1) / 2; A.dh = (sh + 1) / 2; A.dpitch = dpitch; A.dbatch = dbatch;
+    A.src = src.ptr; A.sw = src.w; A.sh = src.h; A.spitch = src.pitch; A.sbatch = src.bstride;
+    A.dst = const_cast<uint8_t*>(dst.ptr); A.dw = (src.w + 1) / 2; A.dh = (src.h + 1) / 2; A.dpitch = dst.pitch; A.dbatch = dst.bstride;
     A.B = B;
-    agt_pyr_plan(&A, (uintptr_t)src, (uintptr_t)dst, 1);
-    const long tiles = (long)A.gx * A.gy * B;
-    if (A.pad) hipLaunchKernelGGL(pyr_roll_kernel, dim3(agt_xcd_grid(tiles, A.xshift)), dim3(agt_pyr::NT), 0, stream, A);
-    else hipLaunchKernelGGL(pyr_down_kernel, dim3(agt_xcd_grid(tiles, A.xshift)), dim3(agt_pyr::NT), agt_pyr::PYR_LDS_BYTES, stream, A);
+    agt_pyr_plan(&A, (uintptr_t)A.src, (uintptr_t)A.dst, 1);
+    const dim3 grid(agt_xcd_grid((long)agt_pyr_blocks(A) * B, A.xshift));
+    if (agt_pyr_rolling(A)) hipLaunchKernelGGL(pyr_roll_kernel, grid, dim3(agt_pyr::NT), 0, stream, A);
+    else hipLaunchKernelGGL(pyr_down_kernel, grid, dim3(agt_pyr::NT), agt_pyr::PYR_LDS_BYTES, stream, A);
     return hipGetLastError();
 }

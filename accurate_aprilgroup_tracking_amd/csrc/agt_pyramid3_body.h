@@ -61,11 +61,11 @@ __device__ __forceinline__ uint4 roll_hrow(u32x4 d, uint32_t e, bool left_edge, 
     return hgroup8b<ODD>(make_uint4(d.x, d.y, d.z, d.w), pm, nx);
 }
 
-// One 256-thread workgroup = 16 units of the image at `img` (units blk * 16 ..).  A.pad = output rows per strip (multiple of UO).
+// One 256-thread workgroup = 16 units of the image at `img` (units blk * 16 ..).  A.strip_rows = output rows per strip (multiple of UO).
 template <bool EDGE, typename RS>
 __device__ __forceinline__ void pyr_roll_rows(const AgtPyrArgs& A, const RS rs, const RS rd, int y0, int oy0, int g, int q, int G, bool lane_on)
 {
-    const int sh = A.sh, dh = A.dh, oh = A.pad;
+    const int sh = A.sh, dh = A.dh, oh = A.strip_rows;
     const int pitch = (int)A.spitch, dpitch = (int)A.dpitch;
     const int NR = 2 * oh + 3;
     const bool left_edge = g == 0, right_edge = g == G - 1;
@@ -114,7 +114,7 @@ __device__ __forceinline__ void pyr_roll_rows(const AgtPyrArgs& A, const RS rs, 
 __device__ __forceinline__ void pyr_roll_body(const AgtPyrArgs& A, int blk, const uint8_t* __restrict__ img, uint8_t* __restrict__ out)
 {
     const int tid = threadIdx.x, q = tid & 15;
-    const int G = A.sw >> 4, ncol = (G + 15) >> 4, oh = A.pad;
+    const int G = A.sw >> 4, ncol = (G + 15) >> 4, oh = A.strip_rows;
     const int nstrip = (A.dh + oh - 1) / oh, units = nstrip * ncol;
     const int u = blk * UNITS_PER_BLOCK + (tid >> 4);
     const bool uvalid = u < units;

@@ -125,7 +125,7 @@ template <bool EDGE, bool COPY, bool REV, bool LR, typename RS>
 __device__ __forceinline__ void pyr_roll2_rows(const AgtPyrArgs& A0, const AgtPyrArgs& A1, const RS rs, const RS r1, const RS r2, const RS rc, int cpitch,
                                                int oy2, int g, int q, int G, bool lane_on, bool rev)
 {
-    const int sh = A0.sh, h1 = A0.dh, h2 = A1.dh, oh2 = A0.pad;
+    const int sh = A0.sh, h1 = A0.dh, h2 = A1.dh, oh2 = A0.strip_rows;
     const int pitch = (int)A0.spitch, pitch1 = (int)A0.dpitch, pitch2 = (int)A1.dpitch;
     const int NR = 4 * oh2 + 9;                                  // level-0 rows of the strip
     const int y1a = 2 * oy2 - 2;                                 // first level-1 row the strip computes (two halo rows above its own)
@@ -241,14 +241,14 @@ __device__ __forceinline__ void pyr_roll2_rows(const AgtPyrArgs& A0, const AgtPy
     }
 }
 
-// One 256-thread workgroup = 16 units of the image at `img`.  A0: level 0 -> 1 geometry (A0.pad = level-2 rows per strip, even),
+// One 256-thread workgroup = 16 units of the image at `img`.  A0: level 0 -> 1 geometry (A0.strip_rows = level-2 rows per strip, even),
 // A1: level 1 -> 2 geometry.
 template <bool COPY = false, bool REV = true>
 __device__ __forceinline__ void pyr_roll2_body(const AgtPyrArgs& A0, const AgtPyrArgs& A1, int blk, const uint8_t* __restrict__ img,
                                                uint8_t* __restrict__ out1, uint8_t* __restrict__ out2, uint8_t* copy = nullptr, int cpitch = 0)
 {
     const int tid = threadIdx.x, q = tid & 15;
-    const int G = A0.sw >> 4, ncol = (G + TILE_GROUPS - 1) / TILE_GROUPS, oh2 = A0.pad;
+    const int G = A0.sw >> 4, ncol = (G + TILE_GROUPS - 1) / TILE_GROUPS, oh2 = A0.strip_rows;
     const int nstrip = (A1.dh + oh2 - 1) / oh2, units = nstrip * ncol;
     // Unit order: column tile fastest -- the four units of a wave are (mostly) four ADJACENT COLUMN TILES of one strip, 896 contiguous
     // bytes of every row.  Round 5 measured the other order (a wave = four consecutive strips of one column tile: strips that share
@@ -269,7 +269,7 @@ __device__ __forceinline__ void pyr_roll2_body(const AgtPyrArgs& A0, const AgtPy
     const auto r2 = __builtin_amdgcn_make_buffer_rsrc(out2, 0, A1.dh * (int)A1.dpitch, 0x00020000);
     const auto rc = __builtin_amdgcn_make_buffer_rsrc(COPY ? copy : out2, 0, COPY ? A0.sh * cpitch : 0, 0x00020000);
     if (__builtin_amdgcn_ballot_w64(uvalid) == 0) return;
-    const bool rev = REV && (s & 1) && A0.rsv_ == 0;              // odd strips bottom-up
+    const bool rev = REV && (s & 1) && A0.topdown == 0;              // odd strips bottom-up
     const bool lr = __builtin_amdgcn_ballot_w64(lane_on && (g == 0 || g == G - 1)) != 0;
     if (__builtin_amdgcn_ballot_w64(edge) != 0) pyr_roll2_rows<true, COPY, REV, true>(A0, A1, rs, r1, r2, rc, cpitch, oy2, g, q, G, lane_on, rev);
     else if (lr) pyr_roll2_rows<false, COPY, REV, true>(A0, A1, rs, r1, r2, rc, cpitch, oy2, g, q, G, lane_on, rev);

@@ -184,10 +184,10 @@ __device__ __forceinline__ void pyr_role(KParams KS, KTables KT, int blk, int ba
         const int n = KS->n_pyr[s];
         if (blk < n) {
             AgtPyrArgs A;
-            A.src = nullptr; A.dst = nullptr; A.pad = 0; A.rsv_ = 0;
+            A.src = nullptr; A.dst = nullptr; A.strip_rows = 0; A.topdown = 0;
             A.spitch = KS->pyr[s].spitch; A.sbatch = KS->pyr[s].sbatch; A.dpitch = KS->pyr[s].dpitch; A.dbatch = KS->pyr[s].dbatch;
             A.sw = KS->pyr[s].sw; A.sh = KS->pyr[s].sh; A.dw = KS->pyr[s].dw; A.dh = KS->pyr[s].dh;
-            A.gx = KS->pyr[s].gx; A.gy = KS->pyr[s].gy; A.B = KS->pyr[s].B; A.pad = KS->pyr[s].pad;
+            A.gx = KS->pyr[s].gx; A.gy = KS->pyr[s].gy; A.B = KS->pyr[s].B; A.strip_rows = KS->pyr[s].strip_rows;
             // XCD-aware tile order (see agt_pyramid.hip): workgroup index % X is the XCD (X = 2^xshift XCDs); the stage's
             // workgroups on XCD j take a contiguous run of tiles, runs laid out in XCD order.
             // (the fused step kernel keeps the LITERAL 8-way deal of rounds 1-4 -- a correct order on every device, the tuned one on a whole
@@ -197,19 +197,19 @@ __device__ __forceinline__ void pyr_role(KParams KS, KTables KT, int blk, int ba
             const int j = (blk + base) & xm;
             int tile = (blk - ((j - base) & xm)) >> xs;
             for (int q = 0; q < j; q++) tile += (n - ((q - base) & xm) + xm) >> xs;
-            const int per_img = A.gx * A.gy;
+            const int per_img = agt_pyr_blocks(A);
             const int bz = tile / per_img, r = tile - bz * per_img;      // bz = frame * B + stream
             const int by = r / A.gx, bx = r - by * A.gx;
             const int fr = bz / A.B, st = bz - fr * A.B;
             if (s == 0 && KS->pyr_fused) {
-                // levels 1 and 2 in one pass (agt_pyramid2_body.h); the level 1 -> 2 geometry sits in pyr[1]
+                // levels 1 and 2 in one pass (agt_pyramid2_body.h); the level 1 -> 2 geometry sits in pyr[1] (agt_step_set_two_level)
                 AgtPyrArgs A1;
-                A1.src = nullptr; A1.dst = nullptr; A1.pad = 0;
+                A1.src = nullptr; A1.dst = nullptr; A1.strip_rows = 0;
                 A1.spitch = KS->pyr[1].spitch; A1.sbatch = KS->pyr[1].sbatch; A1.dpitch = KS->pyr[1].dpitch; A1.dbatch = KS->pyr[1].dbatch;
                 A1.sw = KS->pyr[1].sw; A1.sh = KS->pyr[1].sh; A1.dw = KS->pyr[1].dw; A1.dh = KS->pyr[1].dh;
                 A1.gx = A.gx; A1.gy = A.gy; A1.B = A.B;
-                if (ROLL2 && A.pad) {      // register-rolling form, alternating strip directions (agt_pyramid.hip agt_pyr2_plan): bx = workgroup of the image, no LDS
-                    A.rsv_ = KS->pyr[0].rsv_;
+                if (ROLL2 && agt_pyr_rolling(A)) {      // register-rolling form, alternating strip directions (agt_pyramid.hip agt_pyr2_plan): bx = workgroup of the image, no LDS
+                    A.topdown = KS->pyr[0].topdown;
                     agt_pyr4::pyr_roll2_body(A, A1, bx, KT->pyr_src[0][fr] + (long)st * A.sbatch, KT->pyr_dst[0][fr] + (long)st * A.dbatch,
                                              KT->pyr_dst[1][fr] + (long)st * A1.dbatch);
                     return;
@@ -218,7 +218,7 @@ __device__ __forceinline__ void pyr_role(KParams KS, KTables KT, int blk, int ba
                                          KT->pyr_dst[1][fr] + (long)st * A1.dbatch, lds);
                 return;
             }
-            if (A.pad) {        // register-rolling form (agt_pyramid3_body.h): bx = workgroup of the image, no LDS
+            if (agt_pyr_rolling(A)) {        // register-rolling form (agt_pyramid3_body.h): bx = workgroup of the image, no LDS
                 agt_pyr3::pyr_roll_body(A, bx, KT->pyr_src[s][fr] + (long)st * A.sbatch, KT->pyr_dst[s][fr] + (long)st * A.dbatch);
                 return;
             }
@@ -531,26 +531,25 @@ hipError_t agt_launch_step(hipStream_t stream, const AgtStepParams& S, const Agt
     if (!(roles & AGT_STEP_PNP)) { P.n_pnp = 0; P.pnp_nf = 0; }
     if (!(roles & AGT_STEP_LK)) { P.n_lk = 0; P.lk_nf = 0; }
     if (!(roles & AGT_STEP_PYR)) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) { P.n_pyr[s] = 0; P.pyr_nf[s] = 0; } }
-    if (!AGT_KNOB("AGT_LK_RS", 1)) P.lk.flags |= 0x10000;        // (knobs: AGT_LK_RS=0 keeps every corner on the general LK body)
+    if (!AGT_KNOB("AGT_LK_RS", 1)) P.lk.flags |= AGT_LK_FLAG_GENERAL;        // (knobs: AGT_LK_RS=0 keeps every corner on the general LK body)
     {   // knobs: AGT_STEP_SKIP drops roles from the launch to time the others
         const long skip = AGT_KNOB("AGT_STEP_SKIP", 0);
         if (skip & 1) P.n_pnp = 0; if (skip & 2) P.n_lk = 0; if (skip & 4) { for (int s = 0; s < AGT_MAX_LEVELS - 1; s++) P.n_pyr[s] = 0; }
     }
-    const bool small = P.lk.max_level < 3;
     size_t lds = 0;
     int blocks = 0;
-    // (the register-rolling forms of the pyramid passes, pyr[s].pad != 0, use no LDS: a launch of them alone must not be held to
+    // (the register-rolling forms of the pyramid passes, agt_pyr_rolling(pyr[s]), use no LDS: a launch of them alone must not be held to
     // the tiled kernels' occupancy)
     size_t pyr_lds = 0;
     for (int s = 0; s < AGT_MAX_LEVELS - 1; s++)
         if (P.n_pyr[s] > 0) {
             blocks += P.n_pyr[s];
-            const size_t need = P.pyr[s].pad ? 0 : ((P.pyr_fused && s == 0) ? (size_t)agt_pyr2::PYR2_LDS_BYTES : (size_t)agt_pyr::PYR_LDS_BYTES);
+            const size_t need = agt_pyr_rolling(P.pyr[s]) ? 0 : ((P.pyr_fused && s == 0) ? (size_t)agt_pyr2::PYR2_LDS_BYTES : (size_t)agt_pyr::PYR_LDS_BYTES);
             pyr_lds = pyr_lds > need ? pyr_lds : need;
         }
     lds = pyr_lds;
     // the LK role: one workgroup per corner
-    const size_t lk_lds = small ? lk_role_lds<21, 4, 3>(P.lk.max_level + 1) : lk_role_lds<21, 4, AGT_MAX_LEVELS>(P.lk.max_level + 1);
+    const size_t lk_lds = agt_with_nlev(P.lk.max_level, [&](auto nlev) { return lk_role_lds<21, 4, decltype(nlev)::value>(P.lk.max_level + 1); });
     if (P.n_lk > 0) {
         P.n_lk = (int)((long)P.lk.n * P.lk_B);
         blocks += P.n_lk;
@@ -564,8 +563,7 @@ hipError_t agt_launch_step(hipStream_t stream, const AgtStepParams& S, const Agt
     }
     if (roles == AGT_STEP_LK) {
         const unsigned grid8 = agt_xcd_grid(P.n_lk, P.xshift);          // (XCD-aware corner order: lk_role; blocks past the last corner exit)
-        if (small) hipLaunchKernelGGL((lk_group_kernel<21, 4, 3, 1>), dim3(grid8), dim3(AGT_WAVE * 4), lk_lds, stream, P, T);
-        else hipLaunchKernelGGL((lk_group_kernel<21, 4, AGT_MAX_LEVELS, 1>), dim3(grid8), dim3(AGT_WAVE * 4), lk_lds, stream, P, T);
+        agt_with_nlev(P.lk.max_level, [&](auto nlev) { hipLaunchKernelGGL((lk_group_kernel<21, 4, decltype(nlev)::value, 1>), dim3(grid8), dim3(AGT_WAVE * 4), lk_lds, stream, P, T); });
         return hipGetLastError();
     }
     if (!(roles & (AGT_STEP_LK | AGT_STEP_PNP))) return hipErrorInvalidValue;       // (LK | PnP without the pyramid role: diagnostics)
@@ -573,8 +571,9 @@ hipError_t agt_launch_step(hipStream_t stream, const AgtStepParams& S, const Agt
     // launch is only used while <= 256 corners are in flight (agt_step_fits).  Round 2 also shipped an OCC = 2 build for 257-2048
     // corners (registers capped at 256: ~500 VGPR spills, 1 KB of scratch in the PnP role); round 3's split mode with the LK role
     // as one group launch beats it at every stream count (profiles/r03_stream_sweep.txt), so it is gone.
-    if (small) hipLaunchKernelGGL((step_kernel<21, 4, 3, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T);
-    else return agt_launch_step_deep(stream, P, T, blocks, lds);
+    // (the kernel of deeper pyramids is compiled in the other translation unit: agt_launch_step_deep)
+    if (P.lk.max_level >= 3) return agt_launch_step_deep(stream, P, T, blocks, lds);
+    hipLaunchKernelGGL((step_kernel<21, 4, 3, true, 1>), dim3(blocks), dim3(STEP_THREADS), lds, stream, P, T);
     return hipGetLastError();
 }
 #endif      // !AGT_STEP_NOLICM_TU

@@ -1,7 +1,7 @@
 // agt_step_dense.hip -- the chained launches of the tracker's dense stage (BASELINE configs[4]): the LK launch that first finishes the
 // previous frame's photometric refinement and re-seeds its corner (lk_reseed_kernel), and the same with the frame's cooperative pose
 // solve and the next frame's pyramid tiles behind it in ONE launch (lk_pnp_coop_kernel).  Its own translation unit since round 5:
-// agt_step.hip is compiled without the machine-level loop-invariant code motion (Makefile), which these kernels want to keep.
+// agt_step_nolicm.hip is compiled without the machine-level loop-invariant code motion (Makefile), which these kernels want to keep.
 #undef AGT_LK_STAMPS          // (the diagnostic build's in-kernel stamps belong to agt_lk.hip / agt_pnp.hip / agt_step.hip)
 #undef AGT_PNP_STAMPS
 #undef AGT_STEP_STAMPS
@@ -128,26 +128,24 @@ hipError_t agt_launch_lk_reseed(hipStream_t stream, const AgtStepParams& S, cons
     P.xshift = agt_chip_current().xshift; P.rsv_ = 0; P.lk.xshift = P.xshift;
     const unsigned grid8 = agt_xcd_grid(corners, 3);              // (lk_reseed_role deals 8 ways on every device)
     P.n_lk = (int)grid8;
-    agt_dense::DenseParams D;
-    static_assert(sizeof(D) <= sizeof(F->bytes), "AgtDenseFinal holds a DenseParams");
-    memset(&D, 0, sizeof(D));
+    agt_dense::DenseParams D = agt_dense::DenseParams();
     if (F) {
-        memcpy(&D, F->bytes, sizeof(D));
+        D = F->P;
         if (D.N != P.lk.n || (D.seed_pts && D.seed_pts != P.lk.prev_pts)) return hipErrorInvalidValue;      // (a re-seeded corner set IS this launch's start)
     }
-    const bool small = P.lk.max_level < 3;
-    size_t per = small ? lk_role_lds<21, 4, 3>(P.lk.max_level + 1) : lk_role_lds<21, 4, AGT_MAX_LEVELS>(P.lk.max_level + 1);
-    if (!chain) {
-        if (small) hipLaunchKernelGGL((lk_reseed_kernel<3>), dim3(grid8), dim3(AGT_WAVE * 4), per, stream, P, T, D);
-        else hipLaunchKernelGGL((lk_reseed_kernel<AGT_MAX_LEVELS>), dim3(grid8), dim3(AGT_WAVE * 4), per, stream, P, T, D);
-        return hipGetLastError();
-    }
-    if (per < sizeof(agt_pnp::PnpShared)) per = sizeof(agt_pnp::PnpShared);
     const AgtPyrArgs none = AgtPyrArgs();
-    const int n_pyr = ride ? ride[0].gx * ride[0].gy : 0;
-    if (ride && per < (size_t)agt_pyr2::PYR2_LDS_BYTES) per = (size_t)agt_pyr2::PYR2_LDS_BYTES;
-    const unsigned grid = grid8 + (unsigned)P.n_pnp + (unsigned)(n_pyr * P.lk_B);
-    if (small) hipLaunchKernelGGL((lk_pnp_coop_kernel<3>), dim3(grid), dim3(AGT_WAVE * 4), per, stream, P, T, D, F ? 1 : 0, ride ? ride[0] : none, ride ? ride[1] : none, n_pyr > 0 ? n_pyr : 1);
-    else hipLaunchKernelGGL((lk_pnp_coop_kernel<AGT_MAX_LEVELS>), dim3(grid), dim3(AGT_WAVE * 4), per, stream, P, T, D, F ? 1 : 0, ride ? ride[0] : none, ride ? ride[1] : none, n_pyr > 0 ? n_pyr : 1);
-    return hipGetLastError();
+    const int n_pyr = ride ? agt_pyr_blocks(ride[0]) : 0;
+    return agt_with_nlev(P.lk.max_level, [&](auto nlev) {
+        constexpr int NLEV = decltype(nlev)::value;
+        size_t per = lk_role_lds<21, 4, NLEV>(P.lk.max_level + 1);
+        if (!chain) {
+            hipLaunchKernelGGL((lk_reseed_kernel<NLEV>), dim3(grid8), dim3(AGT_WAVE * 4), per, stream, P, T, D);
+            return hipGetLastError();
+        }
+        if (per < sizeof(agt_pnp::PnpShared)) per = sizeof(agt_pnp::PnpShared);
+        if (ride && per < (size_t)agt_pyr2::PYR2_LDS_BYTES) per = (size_t)agt_pyr2::PYR2_LDS_BYTES;
+        const unsigned grid = grid8 + (unsigned)P.n_pnp + (unsigned)(n_pyr * P.lk_B);
+        hipLaunchKernelGGL((lk_pnp_coop_kernel<NLEV>), dim3(grid), dim3(AGT_WAVE * 4), per, stream, P, T, D, F ? 1 : 0, ride ? ride[0] : none, ride ? ride[1] : none, n_pyr > 0 ? n_pyr : 1);
+        return hipGetLastError();
+    });
 }
