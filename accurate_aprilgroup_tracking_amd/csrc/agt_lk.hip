@@ -23,11 +23,7 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
     const int cidx = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, P.xshift);
     if (cidx >= total) return;
     const int bY = cidx / P.n, bX = cidx - bY * P.n;          // stream, corner
-    agt_lk::LkFrameIo<NLEV> io;
-    io.grouped = false; io.prev_pts = P.prev_pts; io.next_pts = P.next_pts; io.status = P.status; io.err = P.err;
-    io.have_pos = false; io.px = io.py = 0.f; io.pst = 1;
-    io.fb = &P.fb;           // (set: the backward launch of the forward-backward check, lk_publish gives the verdict.  Unconditionally the
-                             // address: a pointer that depends on the arguments' content forces a copy of them into scratch)
+    const agt_lk::LkFrameIo<NLEV> io = agt_lk::lk_launch_io<NLEV>(&P);
     float ox, oy; int ost;
 #ifdef AGT_LK_STAMPS
     struct CornerLog {

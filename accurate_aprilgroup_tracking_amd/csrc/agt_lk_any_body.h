@@ -72,6 +72,7 @@ __device__ __forceinline__ void any_block_sum(const int (&v)[NV], long long (&ou
 }
 
 // Track corner `pt` of stream `b`; all 256 threads of the workgroup.  lds: any_geom(ww, wh).bytes, 16-byte aligned.
+// Written out here, mirroring agt_lk_body.h lk_patch_pixel: the call moved lk_any_kernel and cost one window of profiles/lk_refactor_anybench.txt
 __device__ __forceinline__ void lk_body_any(const AgtLkParams* P, int pt, int b, uint8_t* lds, int ww, int wh)
 {
     const AnyGeom G = any_geom(ww, wh);
@@ -83,10 +84,7 @@ __device__ __forceinline__ void lk_body_any(const AgtLkParams* P, int pt, int b,
     int phase = 0;
     const int tid = (int)threadIdx.x, lane = tid & (AGT_WAVE - 1), wave = tid / AGT_WAVE;
     const long pidx = (long)b * P->n + pt;
-    LkFrameIo<1> io;
-    io.grouped = false; io.prev_pts = P->prev_pts; io.next_pts = P->next_pts; io.status = P->status; io.err = P->err;
-    io.have_pos = false; io.px = io.py = 0.f; io.pst = 1;
-    io.fb = &P->fb;
+    const LkFrameIo<1> io = lk_launch_io<1>(P);
 
     const float halfx = (ww - 1) * 0.5f, halfy = (wh - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
@@ -179,9 +177,9 @@ __device__ __forceinline__ void lk_body_any(const AgtLkParams* P, int pt, int b,
         const float A22 = (float)(double)at[2] * FLT_SCALE;
 
         float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * ww * wh);
+        const float minEig = lk_min_eig(A11, A12, A22, ww * wh);
         if (P->flags & AGT_LK_GET_MIN_EIGENVALS) errv = minEig;
-        if (agt_uniform((int)((double)minEig < P->min_eig_threshold || D < FLT_EPSILON))) {
+        if (agt_uniform((int)lk_flat(minEig, D, P->min_eig_threshold))) {
             if (level == 0) st = 0;
             continue;
         }

@@ -164,15 +164,46 @@ __device__ __forceinline__ int bil4(int v00, int v01, int v10, int v11, int iw00
     return __mul24(v00, iw00) + __mul24(v01, iw01) + __mul24(v10, iw10) + __mul24(v11, iw11);
 }
 
+// Two int32 sums in one DPP chain: v_permlane32_swap leaves { v0 of lanes 0-31 | v1 of lanes 0-31 } and { v0 of lanes 32-63 | v1 of
+// lanes 32-63 } side by side, so one add gives pair sums of v0 in the lower half-wave and of v1 in the upper one.  Then the DPP row
+// steps FIRST .. LAST - 1 of four: after step k every lane holds the sum over its 2, 4, 8, 16 lanes (callers bound the operands).
+__device__ __forceinline__ int pair_fold(int v0, int v1)
+{
+    const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v0, (unsigned)v1, false, false);
+    return (int)sw[0] + (int)sw[1];
+}
+template <int FIRST, int LAST>
+__device__ __forceinline__ int row_steps(int v)
+{
+    if (FIRST <= 0 && 0 < LAST) v += agt_dpp_i32<0xB1>(v);         // quad_perm [1,0,3,2]
+    if (FIRST <= 1 && 1 < LAST) v += agt_dpp_i32<0x4E>(v);         // quad_perm [2,3,0,1]
+    if (FIRST <= 2 && 2 < LAST) v += agt_dpp_i32<0x141>(v);        // row_half_mirror: 8-lane sums
+    if (FIRST <= 3 && 3 < LAST) v += agt_dpp_i32<0x140>(v);        // row_mirror: 16-lane sums
+    return v;
+}
+// ... and the two totals of a folded register after all four steps: rows 0 / 1 hold value 0, rows 2 / 3 value 1
+__device__ __forceinline__ void pair_totals(int x, int& t0, int& t1)
+{
+    t0 = __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16);
+    t1 = __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48);
+}
+// ... or, across waves: the first lane of each 16-lane row adds its row's sum, split lo / hi, into the workgroup's accumulator
+// { lo0, hi0, lo1, hi1 } at acc with LDS atomics (integer: order-free, exact)
+__device__ __forceinline__ void pair_accumulate(int* acc, int lane, int xl, int xh)
+{
+    if ((lane & 15) == 0) {
+        __attribute__((address_space(3))) int* q = (__attribute__((address_space(3))) int*)(acc + ((lane >> 5) << 1));
+        __hip_atomic_fetch_add(q, xl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(q + 1, xh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
 // Exact 64-lane sum of one int per lane; identical (wave-uniform) in every lane.
 // STEPS DPP steps in int32 (proved not to overflow), the rest in 64-bit scalars.
 template <int STEPS>
 __device__ __forceinline__ long long wave_sum_exact(int v)
 {
-    v += agt_dpp_i32<0xB1>(v);                         // quad_perm [1,0,3,2]
-    v += agt_dpp_i32<0x4E>(v);                         // quad_perm [2,3,0,1]
-    if (STEPS >= 3) v += agt_dpp_i32<0x141>(v);        // row_half_mirror: 8-lane sums
-    if (STEPS >= 4) v += agt_dpp_i32<0x140>(v);        // row_mirror: 16-lane sums
+    v = row_steps<0, STEPS>(v);
     constexpr int G = 1 << STEPS;
     long long t = 0;
 #pragma unroll
@@ -186,10 +217,9 @@ __device__ __forceinline__ void block_sum_exact(const int (&v)[NV], long long (&
                                                 int wave, int lane)
 {
     if constexpr (NW == 4) {
-        // Four waves per corner (round 3): every value is split v = 65536 * hi + lo, two values share one DPP chain per half
-        // (v_permlane32_swap: value 0 in the lower half-wave, value 1 in the upper one), and the FIRST LANE OF EACH 16-LANE
-        // ROW adds its row sum straight into the workgroup's accumulators with LDS atomics (integer: order-free, exact):
-        // no read-lanes, no per-wave slots, one or two 16-byte reads after the barrier.  |v| < 2^28 per thread keeps every
+        // Four waves per corner (round 3): every value is split v = 65536 * hi + lo, two values share one DPP chain per half and
+        // the row sums go straight into the workgroup's accumulators (pair_accumulate): no read-lanes, no per-wave slots, one
+        // or two 16-byte reads after the barrier.  |v| < 2^28 per thread keeps every
         // int32 partial in range (lo: 256 x 65535 < 2^24, hi: 256 x 2^12).  Three accumulator sets rotate; the set of sum
         // i + 2 is cleared by thread 0 right after the barrier of sum i, when its last readers (sum i - 1) are past it.
         // Accumulator layout: pair p of values -> ints [4 p + 2 * (value & 1) + { 0: lo, 1: hi }].
@@ -197,6 +227,8 @@ __device__ __forceinline__ void block_sum_exact(const int (&v)[NV], long long (&
 #pragma unroll
         for (int p = 0; p < (NV + 1) / 2; p++) {
             const int a = v[2 * p], b = 2 * p + 1 < NV ? v[2 * p + 1] : 0;
+            // (pair_fold + row_steps<0, 4> of both halves, written out: as two calls the halves' steps are no longer interleaved in the
+            // source and the four-wave kernels are scheduled differently)
             const auto swl = __builtin_amdgcn_permlane32_swap((unsigned)(a & 0xffff), (unsigned)(b & 0xffff), false, false);
             const auto swh = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 16), (unsigned)(b >> 16), false, false);
             int xl = (int)swl[0] + (int)swl[1], xh = (int)swh[0] + (int)swh[1];
@@ -204,11 +236,7 @@ __device__ __forceinline__ void block_sum_exact(const int (&v)[NV], long long (&
             xl += agt_dpp_i32<0x4E>(xl); xh += agt_dpp_i32<0x4E>(xh);
             xl += agt_dpp_i32<0x141>(xl); xh += agt_dpp_i32<0x141>(xh);
             xl += agt_dpp_i32<0x140>(xl); xh += agt_dpp_i32<0x140>(xh);
-            if ((lane & 15) == 0) {
-                __attribute__((address_space(3))) int* q = (__attribute__((address_space(3))) int*)(acc + 4 * p + ((lane >> 5) << 1));
-                __hip_atomic_fetch_add(q, xl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(q + 1, xh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+            pair_accumulate(acc + 4 * p, lane, xl, xh);
         }
         block_sync<NW>();
         const int4 r0 = *reinterpret_cast<const int4*>(acc);
@@ -224,15 +252,8 @@ __device__ __forceinline__ void block_sum_exact(const int (&v)[NV], long long (&
         return;
     }
     if constexpr ((NV == 2 || NV == 3) && PAIR_OK) {
-        // two sums in one chain: v_permlane32_swap leaves { v0 of lanes 0-31 | v1 of lanes 0-31 } and { v0 of lanes
-        // 32-63 | v1 of lanes 32-63 } side by side, so one add gives pair sums of v0 in the lower half-wave and of v1
-        // in the upper one; four DPP row steps (still < 2^31, checked by the caller's PAIR_OK) and four readlanes follow
-        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v[0], (unsigned)v[1], false, false);
-        int x = (int)sw[0] + (int)sw[1];
-        x += agt_dpp_i32<0xB1>(x);
-        x += agt_dpp_i32<0x4E>(x);
-        x += agt_dpp_i32<0x141>(x);
-        x += agt_dpp_i32<0x140>(x);
+        // two sums in one chain; the four row steps stay below 2^31 (the caller's PAIR_OK); four readlanes follow
+        const int x = row_steps<0, 4>(pair_fold(v[0], v[1]));
         out[0] = (long long)__builtin_amdgcn_readlane(x, 0) + (long long)__builtin_amdgcn_readlane(x, 16);
         out[1] = (long long)__builtin_amdgcn_readlane(x, 32) + (long long)__builtin_amdgcn_readlane(x, 48);
         if constexpr (NV == 3) out[2] = wave_sum_exact<STEPS>(v[2]);
@@ -258,21 +279,24 @@ __device__ __forceinline__ void block_sum_exact(const int (&v)[NV], long long (&
     }
 }
 
+// the one-wave row-segment body's LDS grid of un-rounded interpolations (agt_lk_rs_body.h): 23 rows (window rows + 2) of 24 int32 (23 + pad)
+constexpr int RS_BROWS = 23, RS_BP = 24, RS_B_BYTES = RS_BROWS * RS_BP * 4;
+static_assert(RS_B_BYTES == 23 * 24 * 4, "the row-segment grid's LDS footprint is part of every one-wave launch's size");
+
 // LDS bytes one corner needs: [levels] x { I tile | J tile }, derivative tile, reduction slots
 template <int WIN, int NW>
 __host__ __device__ constexpr size_t lk_lds_bytes(int levels)
 {
     using C = LkCfg<WIN, NW>;
     size_t behind = (size_t)((C::DW * C::DW + 3) & ~3) * sizeof(int) + (size_t)2 * NW * 4 * sizeof(long long);
-    // (one wave per corner, 21 x 21: the row-segment body keeps a 23 x 24 int32 grid there instead -- agt_lk_rs_body.h RS_B_BYTES)
-    if (WIN == 21 && NW == 1 && behind < (size_t)23 * 24 * 4) behind = (size_t)23 * 24 * 4;
+    // (one wave per corner, 21 x 21: the row-segment body keeps its grid of interpolations there instead)
+    if (WIN == 21 && NW == 1 && behind < (size_t)RS_B_BYTES) behind = (size_t)RS_B_BYTES;
     return (size_t)levels * C::LEVEL_LDS + behind;
 }
 
-
 // 1 / 2^l as a float: the exponent field written directly.  (As the division 1.f / (float)(1 << l) with a run-time l it is the full IEEE
 // sequence -- v_div_scale x 2, v_rcp, four fused multiply-adds, v_div_fmas, v_div_fixup -- on the critical path of every level of every
-// corner, and of every trip of rs_interior: round 6.)  Exact for 0 <= l <= 126.
+// corner, and of every trip of rs_interior_levels: round 6.)  Exact for 0 <= l <= 126.
 __device__ __forceinline__ float lk_level_scale(int l) { return __int_as_float((127 - l) << 23); }
 
 // A coordinate the tracker will not form an address from: non-finite or |x| >= 2^20.  OpenCV floors such a value to an integer far
@@ -280,6 +304,56 @@ __device__ __forceinline__ float lk_level_scale(int l) { return __int_as_float((
 // image" at every level: status 0, err 0, the position carried -- which is what the bodies below do with it up front (a GPU
 // float -> int conversion turns a NaN into 0, i.e. INTO the image).  Finite positions below 2^20 go through the usual bounds tests.
 __device__ __forceinline__ bool lk_pt_ok(float x, float y) { return fabsf(x) < 1048576.f && fabsf(y) < 1048576.f; }
+
+// ---- The steps of LKTrackerInvoker::operator() (lkpyramid.cpp; oracle/cv_lk.c lk_point) that more than one body takes, one copy each:
+// every one is a bit-parity obligation.  A helper holds no STAMP / CSTAMP / CCOUNT / CREPS (they use the caller's names), keeps OpenCV's
+// operand and evaluation order (-ffp-contract=off: the expressions as written are the contract), and takes as a callable what its
+// caller reads lazily from the kernel-argument segment.  A body uses a helper only where the call leaves its kernels' instructions
+// as they were (tools/isa_diff.py against the build before); each says in the comment above it which steps it keeps written out for
+// that reason -- mend those copies WITH the helper.  Steps that moved every body as a helper stay written out in all of them: the
+// image-band and search-tile tests (inside a helper the || chain is no longer a chain of branches), the start of a level, the lost /
+// wild corner at entry, the scalar Scharr (general, any-window body), set_box (the float search box: row-segment, frame-chained body).
+
+// What one iteration decided, as ONE code (one vector -> scalar crossing): 0 go on, 1 converged, 2 oscillating, 3 go on but the next
+// window position is outside the box.  OpenCV: `if (delta.ddot(delta) <= criteria.epsilon) break;` -- FP64 -- then
+// `if (j > 0 && std::abs(delta.x + prevDelta.x) < 0.01 && std::abs(delta.y + prevDelta.y) < 0.01)`.  The float sum is within 2e-7 of the
+// FP64 one, so FP64 is evaluated only inside a 1e-6 band around the threshold (eps2_lo, eps2_hi; wave-uniform, rare; eps2() is read only
+// there);  fabs((double)f) < 0.01  <=>  fabsf(f) <= 0.01f  (0.01f is the largest float below 0.01).
+template <typename Eps2>
+__device__ __forceinline__ int lk_iter_code(float dx, float dy, float pdx, float pdy, int j, float nextx, float nexty,
+                                            float bx0, float bx1, float by0, float by1, float eps2_lo, float eps2_hi, Eps2&& eps2)
+{
+    const float d2 = dx * dx + dy * dy;
+    const bool osc = j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f;
+    const bool out_of_box = !(nextx >= bx0 && nextx < bx1 && nexty >= by0 && nexty < by1);
+    int code = out_of_box ? 3 : 0;
+    code = osc ? 2 : code;
+    code = d2 < eps2_lo ? 1 : code;
+    code = (!(d2 < eps2_lo) && !(d2 > eps2_hi)) ? 4 : code;
+    code = agt_uniform(code);
+    if (code == 4) {
+        const bool conv = (double)dx * dx + (double)dy * dy <= eps2();
+        code = agt_uniform(conv ? 1 : (osc ? 2 : (out_of_box ? 3 : 0)));
+    }
+    return code;
+}
+
+// The 2 x 2 system of a level (D = A11*A22 - A12*A12 stays at the call sites): `minEig = (A22 + A11 - std::sqrt((A11-A22)*(A11-A22) +
+// 4.f*A12*A12)) / (2*winSize.width*winSize.height)`; the level is skipped `if (minEig < minEigThreshold || D < FLT_EPSILON)` (FP64)
+__device__ __forceinline__ float lk_min_eig(float A11, float A12, float A22, int area) { return (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * area); }
+__device__ __forceinline__ bool lk_flat(float minEig, float D, double min_eig_threshold) { return (double)minEig < min_eig_threshold || D < FLT_EPSILON; }
+
+// One window pixel of the I patch: `ival = CV_DESCALE(src[x]*iw00 + src[x+cn]*iw01 + src[x+stepI]*iw10 + src[x+stepI+cn]*iw11, W_BITS1-5)`
+// and the same of both derivatives with W_BITS1.  p: the pixel in the I tile (pitch ip); d: its derivative position in the packed
+// derivative tile (dx | dy << 16, pitch dw ints)
+__device__ __forceinline__ void lk_patch_pixel(const uint8_t* p, int ip, const int* d, int dw, int iw00, int iw01, int iw10, int iw11,
+                                               int& iv, int& ix, int& iy)
+{
+    iv = descale(bil4(p[0], p[1], p[ip], p[ip + 1], iw00, iw01, iw10, iw11), W_BITS - 5);
+    const int d00 = d[0], d01 = d[1], d10 = d[dw], d11 = d[dw + 1];
+    ix = descale(bil4((short)d00, (short)d01, (short)d10, (short)d11, iw00, iw01, iw10, iw11), W_BITS);
+    iy = descale(bil4(d00 >> 16, d01 >> 16, d10 >> 16, d11 >> 16, iw00, iw01, iw10, iw11), W_BITS);
+}
 
 // Where one frame of the tracker reads and writes.  grouped = image bases come from imgI / imgJ (the frame
 // group of the fused step) instead of P.prev / P.next; have_pos = the previous position comes in registers
@@ -365,6 +439,33 @@ __device__ __forceinline__ AgtLevel get_level(const LV& L)
     return r;
 }
 
+// LkFrameIo of a stand-alone launch.  fb (set: the backward launch of the forward-backward check, lk_publish gives the verdict) is
+// unconditionally the address: a pointer that depends on the arguments' content forces a copy of them into scratch
+template <int NLEV>
+__device__ __forceinline__ LkFrameIo<NLEV> lk_launch_io(const AgtLkParams* P)
+{
+    LkFrameIo<NLEV> io;
+    io.grouped = false; io.prev_pts = P->prev_pts; io.next_pts = P->next_pts; io.status = P->status; io.err = P->err;
+    io.have_pos = false; io.px = io.py = 0.f; io.pst = 1;
+    io.fb = &P->fb;
+    return io;
+}
+
+// Level l as the prologues see it: the corner (ipx, ipy) of the I window of previous position (ppx, ppy), the origin (jx0, jy0) of the search
+// tile around the expected start (gsx, gsy) of the search, both images' geometry.  img(p): a frame group's image pointer as the body wants it
+template <int WIN, int MARGIN, int NLEV, typename PP, typename Img>
+__device__ __forceinline__ void lk_level_geometry(PP P, const LkFrameIo<NLEV>& io, int l, float ppx, float ppy, float gsx, float gsy,
+                                                  int& ipx, int& ipy, int& jx0, int& jy0, AgtLevel& LI, AgtLevel& LJ, Img&& img)
+{
+    const float halfw = (WIN - 1) * 0.5f;
+    const float scale = lk_level_scale(l);
+    ipx = (int)floorf(ppx * scale - halfw); ipy = (int)floorf(ppy * scale - halfw);
+    jx0 = (int)floorf(gsx * scale - halfw) - MARGIN; jy0 = (int)floorf(gsy * scale - halfw) - MARGIN;
+    LI = get_level(P->prev[l]);
+    LJ = get_level(P->next[l]);
+    if (io.grouped) { LI.ptr = img(io.imgI[l]); LJ.ptr = img(io.imgJ[l]); }
+}
+
 // PP: pointer to the parameters -- `const AgtLkParams*` (stand-alone launch) or a pointer into the kernel-argument
 // segment (fused step, where the level tables are indexed with run-time levels inside a frame loop).
 // STOP > 0 (round 6, agt_lk.hip lk_kernel): only the pyramid levels max_level .. level_stop are tracked here and nothing is
@@ -372,6 +473,7 @@ __device__ __forceinline__ AgtLevel get_level(const LV& L)
 // through the finer levels; ost < 0 then says that the corner was finished (published) here after all (lost, wild).
 // (STOP is a template parameter: as a run-time bound of the level loop it cost the one-wave kernel its register allocation -- spills at
 // 128 registers -- and with it known, the prologue requests only the tiles of the levels tracked here.)
+// Written out here, mirroring the helper named: the NW > 1 prologue's geometry (lk_level_geometry: as a call it moves the step kernels).
 template <int WIN, int NW, int NLEV, typename PP, int STOP = 0>
 __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const LkFrameIo<NLEV>& io, float& ox, float& oy, int& ost)
 {
@@ -442,12 +544,9 @@ __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const
 #pragma unroll
         for (int l = 0; l < NLEV; l++) {
             if (l >= STOP && l <= P->max_level) {
-                const float scale = lk_level_scale(l);
-                const int ipx = (int)floorf(ppx * scale - halfw), ipy = (int)floorf(ppy * scale - halfw);
-                const int jx0 = (int)floorf(gsx * scale - halfw) - C::MARGIN, jy0 = (int)floorf(gsy * scale - halfw) - C::MARGIN;
-                AgtLevel LI = get_level(P->prev[l]);
-                AgtLevel LJ = get_level(P->next[l]);
-                if (io.grouped) { LI.ptr = io.imgI[l]; LJ.ptr = io.imgJ[l]; }
+                int ipx, ipy, jx0, jy0;
+                AgtLevel LI, LJ;
+                lk_level_geometry<WIN, C::MARGIN>(P, io, l, ppx, ppy, gsx, gsy, ipx, ipy, jx0, jy0, LI, LJ, [](const uint8_t* p) { return p; });
                 uint32_t ti[C::ILD], tj[C::JLD];
 #pragma unroll
                 for (int k = 0; k < C::ILD; k++) ti[k] = 0;
@@ -559,12 +658,8 @@ __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const
         int asum[3] = { 0, 0, 0 };
 #pragma unroll
         for (int k = 0; k < C::NPX; k++) {
-            const uint8_t* p = sI + oI[k] + offI;
-            const int iv = descale(bil4(p[0], p[1], p[C::IP], p[C::IP + 1], iw00, iw01, iw10, iw11), W_BITS - 5);
-            const int* d = sD + oD[k];
-            const int d00 = d[0], d01 = d[1], d10 = d[C::DW], d11 = d[C::DW + 1];
-            const int ix = descale(bil4((short)d00, (short)d01, (short)d10, (short)d11, iw00, iw01, iw10, iw11), W_BITS);
-            const int iy = descale(bil4(d00 >> 16, d01 >> 16, d10 >> 16, d11 >> 16, iw00, iw01, iw10, iw11), W_BITS);
+            int iv, ix, iy;
+            lk_patch_pixel(sI + oI[k] + offI, C::IP, sD + oD[k], C::DW, iw00, iw01, iw10, iw11, iv, ix, iy);
             Iv[k] = pv[k] ? iv : 0; Ix[k] = pv[k] ? ix : 0; Iy[k] = pv[k] ? iy : 0;
             asum[0] += __mul24(Ix[k], Ix[k]); asum[1] += __mul24(Ix[k], Iy[k]); asum[2] += __mul24(Iy[k], Iy[k]);
         }
@@ -575,9 +670,9 @@ __device__ __forceinline__ void lk_body(PP P, int pt, int b, uint8_t* lds, const
         const float A22 = (float)(double)at[2] * FLT_SCALE;
 
         float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
+        const float minEig = lk_min_eig(A11, A12, A22, WIN * WIN);
         if (P->flags & AGT_LK_GET_MIN_EIGENVALS) errv = minEig;
-        if (agt_uniform((int)((double)minEig < P->min_eig_threshold || D < FLT_EPSILON))) {
+        if (agt_uniform((int)lk_flat(minEig, D, P->min_eig_threshold))) {
             if (STOP == 0 && level == 0) st = 0;
             continue;
         }

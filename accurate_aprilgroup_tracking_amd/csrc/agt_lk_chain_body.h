@@ -75,28 +75,8 @@ __host__ __device__ constexpr size_t lk_chain_lds_bytes() { return (size_t)Chain
 // put the prefetched tiles of the next frame back on the critical path of the first iteration after their request
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// 64-lane int32 sum (no overflow checks: callers bound the operands), wave-uniform result
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-    v += agt_dpp_i32<0xB1>(v);
-    v += agt_dpp_i32<0x4E>(v);
-    v += agt_dpp_i32<0x141>(v);
-    v += agt_dpp_i32<0x140>(v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-
-// two 64-lane int32 sums in one DPP chain (v_permlane32_swap: value 0 ends up in the lower half-wave, value 1 in the upper one)
-__device__ __forceinline__ void wave_sum2_i32(int v0, int v1, int& t0, int& t1)
-{
-    const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v0, (unsigned)v1, false, false);
-    int x = (int)sw[0] + (int)sw[1];
-    x += agt_dpp_i32<0xB1>(x);
-    x += agt_dpp_i32<0x4E>(x);
-    x += agt_dpp_i32<0x141>(x);
-    x += agt_dpp_i32<0x140>(x);
-    t0 = __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16);
-    t1 = __builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48);
-}
+// two 64-lane int32 sums in one DPP chain (no overflow checks: callers bound the operands)
+__device__ __forceinline__ void wave_sum2_i32(int v0, int v1, int& t0, int& t1) { pair_totals(row_steps<0, 4>(pair_fold(v0, v1)), t0, t1); }
 
 // The two mismatch sums of one iteration over the four waves, as the floats the 2 x 2 solve needs.  Exact: the partial sums are
 // split x = 65536 * hi + lo before they could leave int32, the hi and lo parts are accumulated separately (|sum hi| < 2^18,
@@ -109,26 +89,16 @@ __device__ __forceinline__ void iter_sum2(const int (&v)[2], float& f0, float& f
     // values travel whole that far (value 0 in the lower half-wave, value 1 in the upper one) and are split into 16-bit halves
     // only for the last DPP step and the cross-wave accumulation (lo < 2^20, |hi| < 2^18 over the workgroup) -- 11 instructions
     // instead of the 18 of two full half-chains
-    const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v[0], (unsigned)v[1], false, false);
-    int x = (int)sw[0] + (int)sw[1];
-    x += agt_dpp_i32<0xB1>(x);
-    x += agt_dpp_i32<0x4E>(x);
-    x += agt_dpp_i32<0x141>(x);
+    const int x = row_steps<0, 3>(pair_fold(v[0], v[1]));
     int xl = x & 0xffff, xh = x >> 16;
-    xl += agt_dpp_i32<0x140>(xl); xh += agt_dpp_i32<0x140>(xh);
-    // After the four DPP steps every lane of a 16-lane row holds its row's sum; rows 0 / 1 belong to value 0, rows 2 / 3 to value 1
-    // (the swap).  The first lane of each row adds its row sum straight into the workgroup's accumulator with an LDS atomic
-    // (integer: order-free, still exact): { lo0, hi0, lo1, hi1 }, three rotating slots -- the slot of iteration i + 2 is cleared
-    // by thread 0 right after the barrier of iteration i, when its last readers (iteration i - 1) are past it.  No read-lanes,
-    // no scalar adds, and after the barrier every wave reads ONE 16-byte word instead of four.
+    xl = row_steps<3, 4>(xl); xh = row_steps<3, 4>(xh);
+    // The row sums go straight into the workgroup's accumulator (pair_accumulate), three rotating slots -- the slot of iteration i + 2
+    // is cleared by thread 0 right after the barrier of iteration i, when its last readers (iteration i - 1) are past it.  No
+    // read-lanes, no scalar adds, and after the barrier every wave reads ONE 16-byte word instead of four.
     // (round 2: read-lanes + ds_write_b128 per wave + four ds_read_b128 and twelve adds after the barrier; finishing the sums
     // with row_bcast DPP steps and a store from lanes 31 / 63 had measured 11 % slower than that)
     int* s = slots + phase * 4;
-    if ((lane & 15) == 0) {
-        __attribute__((address_space(3))) int* a = (__attribute__((address_space(3))) int*)(s + ((lane >> 5) << 1));
-        __hip_atomic_fetch_add(a, xl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(a + 1, xh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
+    pair_accumulate(s, lane, xl, xh);
     lds_barrier();
     const int4 t = *reinterpret_cast<const int4*>(s);
     const int nz = phase == 0 ? 2 : phase - 1;                     // (phase + 2) % 3
@@ -163,6 +133,8 @@ __device__ __forceinline__ void tile_request(const uint8_t* img, int w, int h, l
 }
 
 // frame(k) -> LkFrameIo<NLEV> of frame k of the group (image pointers, outputs, arrival counter)
+// Written out here, mirroring the helper of agt_lk_body.h named: minEig (lk_min_eig: as a call it moves the step kernels) -- and
+// set_box, which is the row-segment body's word for word.
 template <int NLEV, typename PP, typename FrameFn>
 __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, int nf, FrameFn&& frame)
 {
@@ -388,12 +360,8 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             int a0 = 0, a1 = 0, a2 = 0;
 #pragma unroll
             for (int q = 0; q < C::NPX; q++) {
-                const uint8_t* p = s0 + oW[q];
-                const int iv = descale(bil4(p[0], p[1], p[JP], p[JP + 1], iw00, iw01, iw10, iw11), W_BITS - 5);
-                const int* d = sD + oD[q];
-                const int d00 = d[0], d01 = d[1], d10 = d[DW], d11 = d[DW + 1];
-                const int ix = descale(bil4((short)d00, (short)d01, (short)d10, (short)d11, iw00, iw01, iw10, iw11), W_BITS);
-                const int iy = descale(bil4(d00 >> 16, d01 >> 16, d10 >> 16, d11 >> 16, iw00, iw01, iw10, iw11), W_BITS);
+                int iv, ix, iy;
+                lk_patch_pixel(s0 + oW[q], JP, sD + oD[q], DW, iw00, iw01, iw10, iw11, iv, ix, iy);
                 Iv[l][q] = pv[q] ? iv : 0; Ix[l][q] = pv[q] ? ix : 0; Iy[l][q] = pv[q] ? iy : 0;
                 a0 += __mul24(Ix[l][q], Ix[l][q]); a1 += __mul24(Ix[l][q], Iy[l][q]); a2 += __mul24(Iy[l][q], Iy[l][q]);
             }
@@ -421,7 +389,7 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             for (int i = 0; i < 3; i++) A[i] = fmaf((float)hi[i], 65536.f, (float)lo[i]) * FLT_SCALE;
             const float D = A[0] * A[2] - A[1] * A[1];
             const float minEig = (A[2] + A[0] - sqrtf((A[0] - A[2]) * (A[0] - A[2]) + 4.f * A[1] * A[1])) / (float)(2 * WIN * WIN);
-            const bool ok = ((lvA >> l) & 1) && !((double)minEig < min_eig_threshold || D < FLT_EPSILON);
+            const bool ok = ((lvA >> l) & 1) && !lk_flat(minEig, D, min_eig_threshold);
             if (lane == 0) {
                 float* o = lvl + l * 8;
                 o[0] = A[0]; o[1] = A[1]; o[2] = A[2]; o[3] = ok ? 1.f / D : 0.f; o[4] = ok ? 1.f : 0.f;
@@ -563,20 +531,7 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
 #ifdef AGT_STEP_STAMPS
                 if (pidx == 0 && threadIdx.x == 0 && k < 4 && level < 3) agt_chain_stamps[k * 16 + 14] += 1ull << (level * 8);
 #endif
-                // (double)dx * dx + (double)dy * dy <= eps2: FP64 only inside a 1e-6 band around the threshold (code 4, rare);
-                // fabs((double)f) < 0.01  <=>  fabsf(f) <= 0.01f  (0.01f is the largest float below 0.01)
-                const float d2 = dx * dx + dy * dy;
-                const bool osc = j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f;
-                const bool out_of_box = !(nextx >= bx0 && nextx < bx1 && nexty >= by0 && nexty < by1);
-                int code = out_of_box ? 3 : 0;
-                code = osc ? 2 : code;
-                code = d2 < eps2_lo ? 1 : code;
-                code = (!(d2 < eps2_lo) && !(d2 > eps2_hi)) ? 4 : code;
-                code = agt_uniform(code);
-                if (code == 4) {
-                    const bool conv = (double)dx * dx + (double)dy * dy <= eps2;
-                    code = agt_uniform(conv ? 1 : (osc ? 2 : (out_of_box ? 3 : 0)));
-                }
+                const int code = lk_iter_code(dx, dy, pdx, pdy, j, nextx, nexty, bx0, bx1, by0, by1, eps2_lo, eps2_hi, [&] { return eps2; });
                 if (code == 1) break;
                 if (code == 2) { outx -= dx * 0.5f; outy -= dy * 0.5f; break; }
                 slow = code == 3;

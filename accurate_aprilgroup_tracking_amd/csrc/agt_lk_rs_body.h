@@ -2,37 +2,32 @@
 // the throughput kernel of big batches (BASELINE configs[2]: 64 x 1280x720, 3072 corners per step).
 // Same semantics and the same bits as agt_lk_body.h (oracle: oracle/cv_lk.c, CVO_ACC_EXACT); different mapping.
 //
-// Round 1's one-wave kernel gave lane l the window pixels l, l + 64, ... (7 per lane): 28 single-byte LDS reads
-// and ~20 VALU per pixel per iteration, a Scharr tile written to and re-read from LDS per level -- 4,184 VALU and
-// 633 LDS instructions per corner, VALU-issue bound at three to four waves per SIMD.  Here:
-//   * lane l = (row r, segment s) = (l / 3, l % 3) owns the 7 CONSECUTIVE window pixels [7s, 7s + 7) of window row r
-//     (63 lanes; lane 63 idles).  Its two source rows come as three aligned dwords each (6 LDS dword reads per
-//     iteration instead of 28 byte reads), aligned with v_alignbyte_b32;
-//   * the fixed-point bilinear tap  v00*iw00 + v01*iw01 + v10*iw10 + v11*iw11  is two v_dot4_u32_u8: the four bytes
-//     are packed into one register with v_perm_b32 and the 15-bit weights are split into high and low bytes
-//     (sum = 256 * dot4(P, WH) + dot4(P, WL), exact); the rounding constant rides in the accumulator input
-//     [round 6: two v_dot2_i32_i16 with int16 weights instead -- rs_weights_i16 / rs_tap2 below];
-//   * the I side of a level lives in registers only.  By linearity  sum_ij w_ij * Scharr(I)(x+j, y+i)  =
-//     Scharr(B)(x, y)  with  B = sum_ij w_ij * I(.+j, .+i)  taken WITHOUT rounding (B < 2^22, Scharr(B) < 2^27):
-//     each lane interpolates its 3 x 9 patch of B (27 dot4 pairs) and applies the Scharr taps to it -- no derivative
-//     tile in LDS, no barrier.  Valid while every derivative position of the window lies inside the image (the
-//     derivative image has a ZERO border); corners whose window touches the image border at some level take the
-//     general kernel body (agt_lk_body.h) instead, chosen per corner at entry;
-//   * the exact sums: per-lane partials (< 2^28) are split into 16-bit halves, each half is reduced over the wave in
-//     int32 without overflow (two sums share one DPP chain through v_permlane32_swap), and  hi * 65536 + lo  is formed
-//     in FP64 (exact) and rounded to float once -- the same value as (float)(double)(int64 sum).
+// Mapping:
+//   * lane l = (row r, segment s) = (l / 3, l % 3) owns the 7 CONSECUTIVE window pixels [7s, 7s + 7) of window row r (63 lanes; lane 63
+//     idles); with four waves per corner 2 pixels per lane, 231 lanes (RsCfg).  Its two source rows come as aligned dwords (6 LDS dword
+//     reads per iteration with one wave), aligned with v_alignbyte_b32;
+//   * the fixed-point bilinear tap  v00*iw00 + v01*iw01 + v10*iw10 + v11*iw11 + c  is TWO v_dot2_i32_i16, one per image row: the row's two
+//     neighbouring bytes zero-extended into the halves of a register (one v_perm_b32: rs_row_pairs), the row's two weights as int16
+//     halves of a scalar register (rs_weights_i16; a signed half also holds iw11 = -1), the first dot product's result as the second
+//     one's accumulator, the rounding constant and the patch value in the first one's (rs_tap2);
+//   * the I side of a level lives in registers only.  By linearity  sum_ij w_ij * Scharr(I)(x+j, y+i)  =  Scharr(B)(x, y)  with
+//     B = sum_ij w_ij * I(.+j, .+i)  taken WITHOUT rounding (B < 2^22, Scharr(B) < 2^27): the Scharr taps are applied to the lane's
+//     3 x 9 patch of B -- no derivative tile in LDS.  With one wave every B value is interpolated once, by 46 lanes, and handed round
+//     through an int32 grid in LDS (RS_B_BYTES, agt_lk_body.h).  Valid while every derivative position of the window lies inside the
+//     image (the derivative image has a ZERO border): levels where the window touches the image border take the general body
+//     (agt_lk_body.h), chosen per corner at entry (rs_interior_levels, agt_lk.hip lk_kernel);
+//   * the exact sums: two per-lane partials (< 2^28) share one DPP chain through v_permlane32_swap, travel whole while they fit int32
+//     and are split into 16-bit halves for the last row steps;  hi * 65536 + lo  is rounded to float once (one fma) -- the same
+//     value as (float)(double)(int64 sum).
+// History: round 1 gave lane l the window pixels l, l + 64, ... (28 single-byte LDS reads and ~20 VALU per pixel per iteration, a Scharr
+// tile in LDS per level: 4,184 VALU and 633 LDS instructions per corner).  Rounds 2-5 ran the tap as two v_dot4_u32_u8 with the 15-bit
+// weights split into byte planes on the scalar unit (~25 instructions per iteration, a shift-add to join the planes, a correction path
+// for iw11 = -1); round 6 replaced that by the int16 form above.  Figures: profiles/r0*_lk_iteration_isa.md, DESIGN.md section 4.
 #pragma once
 #include "agt_lk_body.h"
 
 namespace agt_lk {
 
-// Round 6 (the iteration's instruction diet): the fixed-point bilinear tap
-//     v00 * iw00 + v01 * iw01 + v10 * iw10 + v11 * iw11 + c
-// is TWO v_dot2_i32_i16 -- one per image row: the row's two neighbouring bytes zero-extended into the halves of a register (one
-// v_perm_b32), the two weights of the row as int16 halves of a scalar register, the first dot product's result as the second
-// one's accumulator.  Rounds 2-5 ran two v_dot4_u32_u8 per tap (the 15-bit weights split into byte planes) plus a shift-add to
-// join the planes, packed the weights into byte planes on the scalar unit (~25 instructions per iteration) and needed a
-// correction path for iw11 = -1 (a byte plane cannot hold it): the signed 16-bit form has none of the three.
 // byte selectors of v_perm_b32(S0 = bytes 4..7, S1 = bytes 0..3): { b[j], 0, b[j+1], 0 } for j = 0..3 (0x0c selects the constant 0)
 constexpr uint32_t RS_PAIR0 = 0x0c010c00u, RS_PAIR1 = 0x0c020c01u, RS_PAIR2 = 0x0c030c02u, RS_PAIR3 = 0x0c040c03u;
 
@@ -106,13 +101,6 @@ __device__ __forceinline__ int rs_mad24(int a, int b, int c)
     return r;
 }
 
-// three aligned dwords of an LDS row from byte address `a` on; `sh` = a & 3 is applied by the caller
-__device__ __forceinline__ void rs_row3(const uint8_t* s, int a, uint32_t& d0, uint32_t& d1, uint32_t& d2)
-{
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(s + (a & ~3));
-    d0 = p[0]; d1 = p[1]; d2 = p[2];
-}
-
 // Exact wave sums of two int32 per lane (|v| < 2^28), identical in every lane, ROUNDED ONCE to float.
 // v_permlane32_swap folds { v0 | v1 } into one register (lanes 0-31: pair sums of v0, lanes 32-63: of v1); the pair sums (< 2^29)
 // and two DPP steps (x 4: < 2^31) still fit int32, so the values travel WHOLE that far and are split into 16-bit halves only for
@@ -121,15 +109,10 @@ __device__ __forceinline__ void rs_row3(const uint8_t* s, int a, uint32_t& d0, u
 // once: the value of (float)(double)(int64 sum).
 __device__ __forceinline__ void rs_wave_sum2(int v0, int v1, float& s0, float& s1)
 {
-    const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v0, (unsigned)v1, false, false);
-    int x = (int)sw[0] + (int)sw[1];
-    x += agt_dpp_i32<0xB1>(x);
-    x += agt_dpp_i32<0x4E>(x);
-    int xl = x & 0xffff, xh = x >> 16;
-    xl += agt_dpp_i32<0x141>(xl); xh += agt_dpp_i32<0x141>(xh);
-    xl += agt_dpp_i32<0x140>(xl); xh += agt_dpp_i32<0x140>(xh);
-    const int lo0 = __builtin_amdgcn_readlane(xl, 0) + __builtin_amdgcn_readlane(xl, 16), lo1 = __builtin_amdgcn_readlane(xl, 32) + __builtin_amdgcn_readlane(xl, 48);
-    const int hi0 = __builtin_amdgcn_readlane(xh, 0) + __builtin_amdgcn_readlane(xh, 16), hi1 = __builtin_amdgcn_readlane(xh, 32) + __builtin_amdgcn_readlane(xh, 48);
+    const int x = row_steps<0, 2>(pair_fold(v0, v1));
+    const int xl = row_steps<2, 4>(x & 0xffff), xh = row_steps<2, 4>(x >> 16);
+    int lo0, lo1, hi0, hi1;
+    pair_totals(xl, lo0, lo1); pair_totals(xh, hi0, hi1);
     s0 = __builtin_fmaf((float)hi0, 65536.f, (float)lo0);
     s1 = __builtin_fmaf((float)hi1, 65536.f, (float)lo1);
 }
@@ -141,41 +124,10 @@ __device__ __forceinline__ const uint8_t* rs_uniform_ptr(const uint8_t* p)
     return (const uint8_t*)(((unsigned long long)hi << 32) | lo);
 }
 
-// the one-wave shape's grid of un-rounded interpolations in LDS: 23 rows (window rows + 2) of 24 int32 (23 columns + pad)
-constexpr int RS_BROWS = 23, RS_BP = 24, RS_B_BYTES = RS_BROWS * RS_BP * 4;
-
-// LDS bytes of one corner: the level tiles only (no derivative tile, no reduction slots)
-__host__ __device__ constexpr size_t lk_rs_lds_bytes(int levels) { return (size_t)levels * LkCfg<21, 1>::LEVEL_LDS; }
-
-// true when every derivative position the 21x21 window of `pt` touches lies inside the image at every level
-// (NLEV > 0: the trips are unrolled and predicated -- straight-line scalar code at the head of every corner's critical path)
-template <int NLEV = 0>
-__device__ __forceinline__ bool rs_interior(float ppx, float ppy, int max_level, int w0, int h0)
-{
-    bool ok = lk_pt_ok(ppx, ppy);              // (a NaN converts to 0, "inside": agt_lk_body.h lk_pt_ok)
-    int w = w0, h = h0;
-    if constexpr (NLEV > 0) {
-#pragma unroll
-        for (int l = 0; l < NLEV; l++) {
-            const float scale = lk_level_scale(l);
-            const int ipx = (int)floorf(ppx * scale - 10.f), ipy = (int)floorf(ppy * scale - 10.f);
-            ok = ok && (l > max_level || (ipx >= 0 && ipx + 21 < w && ipy >= 0 && ipy + 21 < h));
-            w = (w + 1) / 2; h = (h + 1) / 2;
-        }
-        return ok;
-    }
-    for (int l = 0; l <= max_level; l++) {
-        const float scale = lk_level_scale(l);
-        const int ipx = (int)floorf(ppx * scale - 10.f), ipy = (int)floorf(ppy * scale - 10.f);
-        ok = ok && ipx >= 0 && ipx + 21 < w && ipy >= 0 && ipy + 21 < h;
-        w = (w + 1) / 2; h = (h + 1) / 2;
-    }
-    return ok;
-}
-
 // the number of FINE levels 0 .. k - 1 at which every derivative position of the window lies inside the image (0: none, max_level + 1:
-// all = rs_interior).  A window that leaves the image at some level leaves it at every coarser one (it covers twice the ground there),
-// so the levels split into a coarse run for the general body and a fine run for the row-segment body (agt_lk.hip lk_kernel).
+// all; a wild position -- agt_lk_body.h lk_pt_ok -- has none: a NaN would convert to 0, "inside").  A window that leaves the image at
+// some level leaves it at every coarser one (it covers twice the ground there), so the levels split into a coarse run for the general
+// body and a fine run for the row-segment body (agt_lk.hip lk_kernel).
 template <int NLEV>
 __device__ __forceinline__ int rs_interior_levels(float ppx, float ppy, int max_level, int w0, int h0)
 {
@@ -208,7 +160,9 @@ struct RsCfg {
 };
 
 // Track one corner through one frame with NW waves (all 64 * NW threads call).  Preconditions checked by the caller:
-// rs_interior(...) holds and the corner's previous status is 1.  lds: lk_lds_bytes<21, NW>, 16-B aligned.
+// rs_interior_levels(...) covers every level tracked here and the corner's previous status is 1.  lds: lk_lds_bytes<21, NW>, 16-B aligned.
+// Written out here, mirroring the helper of agt_lk_body.h named: the iteration's decision code (lk_iter_code: as a call it moves one
+// instruction of the diagnostic build's four-wave lk_kernel) -- and set_box, which is the frame-chained body's word for word.
 // level_top >= 0 (round 6): the corner's coarse levels max_level .. level_top + 1 were tracked by the general body (their windows touch the
 // image border); this call carries the position it reached -- cx, cy, at the scale of level level_top + 1 -- through levels level_top .. 0.
 template <int NW, int NLEV, typename PP>
@@ -283,13 +237,10 @@ __device__ __forceinline__ void lk_body_rs(PP P, int pt, int b, uint8_t* lds, co
         for (int l = 0; l < NLEV; l++) {
             fastI[l] = fastJ[l] = false;
             if (l <= top) {
-                const float scale = lk_level_scale(l);
-                const int ipx = (int)floorf(ppx * scale - halfw), ipy = (int)floorf(ppy * scale - halfw);
-                const int jx0 = (int)floorf(gsx * scale - halfw) - C::MARGIN, jy0 = (int)floorf(gsy * scale - halfw) - C::MARGIN;
-                AgtLevel LI = get_level(P->prev[l]);
-                AgtLevel LJ = get_level(P->next[l]);
                 // (frames 2.. of a group read their image pointers from an LDS table: uniform, but only provably so after this)
-                if (io.grouped) { LI.ptr = rs_uniform_ptr(io.imgI[l]); LJ.ptr = rs_uniform_ptr(io.imgJ[l]); }
+                int ipx, ipy, jx0, jy0;
+                AgtLevel LI, LJ;
+                lk_level_geometry<WIN, C::MARGIN>(P, io, l, ppx, ppy, gsx, gsy, ipx, ipy, jx0, jy0, LI, LJ, [](const uint8_t* p) { return rs_uniform_ptr(p); });
                 {
                     const int ax0 = agt_uniform((ipx - 1) & ~3), ty0 = agt_uniform(ipy - 1);
                     fastI[l] = ax0 >= 0 && ax0 + 4 * C::INDW <= LI.w && ty0 >= 0 && ty0 + C::IW <= LI.h;
@@ -498,9 +449,9 @@ __device__ __forceinline__ void lk_body_rs(PP P, int pt, int b, uint8_t* lds, co
         A11 *= FLT_SCALE; A12 *= FLT_SCALE; A22 *= FLT_SCALE;
 
         float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
+        const float minEig = lk_min_eig(A11, A12, A22, WIN * WIN);
         if (P->flags & AGT_LK_GET_MIN_EIGENVALS) errv = minEig;
-        if (agt_uniform((int)((double)minEig < P->min_eig_threshold || D < FLT_EPSILON))) {
+        if (agt_uniform((int)lk_flat(minEig, D, P->min_eig_threshold))) {
             if (level == 0) st = 0;
             continue;
         }
@@ -526,8 +477,8 @@ __device__ __forceinline__ void lk_body_rs(PP P, int pt, int b, uint8_t* lds, co
             tile_store<C::JT, C::JNDW, T>(sJ, tid, t);
             block_sync<NW>();
         };
-        // IvR[k] = 256 - (Iv[k] << 9): floor((raw + 256 - 512 Iv) / 512) = floor((raw + 256) / 512) - Iv, so the subtraction of
-        // the patch value rides in the accumulator input of the low dot4 (mod 2^32) and the arithmetic shift yields the difference
+        // IvR[k] = 256 - (Iv[k] << 9): floor((raw + 256 - 512 Iv) / 512) = floor((raw + 256) / 512) - Iv, so the subtraction of the patch
+        // value rides in the accumulator input of the tap's first dot product (rs_tap2) and the arithmetic shift yields the difference
         int IvR[PX];
 #pragma unroll
         for (int k = 0; k < PX; k++) IvR[k] = (1 << (W_BITS - 5 - 1)) - (Iv[k] << (W_BITS - 5));
