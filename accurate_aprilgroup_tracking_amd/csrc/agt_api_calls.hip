@@ -162,6 +162,22 @@ int agt_project_points(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, i
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
+// the visibility rule of agt_tracker_visibility for B poses: project_kernel in its visibility mode (agt_pnp.hip), one thread per tag
+int agt_tag_visibility(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
+                       const double* d_pose, int corners_per_tag, double max_view_deg, int facing,
+                       uint8_t* d_visible, double* d_cos)
+{
+    if (!c || !d_obj || !d_pose || !d_visible || n <= 0 || B <= 0) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (!visibility_args_ok(corners_per_tag, max_view_deg, facing) || !(max_view_deg > 0.0) || n % corners_per_tag) return AGT_ERR_ARG;
+    AgtProjParams p;
+    memset(&p, 0, sizeof(p));
+    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n; p.pose = d_pose;
+    p.vis_out = d_visible; p.vis_cos = d_cos; p.vis_cos_max = visibility_cos_max(max_view_deg); p.vis_cpt = corners_per_tag; p.vis_facing = facing;
+    hipError_t e = agt_launch_project(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
 // ---- the reference's per-frame calls as ONE synchronous call each, host arrays in and out (detect_pose.py:509-526 solvePnP,
 // :441-465 projectPoints).  No copies are enqueued: the arguments go into a host-mapped staging area of the
 // context, the kernel reads them and writes its results there over PCIe and stores a sequence word behind them (system scope), the

@@ -5,6 +5,7 @@
 #include <new>
 #include <string.h>
 #include <stdio.h>
+#include <math.h>
 
 // ---- the idioms of the unit: ring entry of tracker frame `frame`; level l of the pyramid in ring entry `slot` (level 0 is the caller's frame)
 static inline int ring_slot(const agt_ctx* c, long frame) { return (int)(frame % c->live_ring); }
@@ -223,6 +224,7 @@ int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float*
     if (!c || !d_obj || slot < 0 || slot > 1) return AGT_ERR_ARG;
     if (n < 4 || n > c->cfg.max_points) return AGT_ERR_NPOINTS;
     if (c->tag_gate && n % c->tag_gate) return AGT_ERR_NPOINTS;      // whole tags: corners 4t .. 4t + 3
+    if (c->vis_deg > 0.0 && n % c->vis_cpt) return AGT_ERR_ARG;      // (agt_tracker_visibility: whole tags as well)
     if (B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
     if (d_corners && c->built_B[slot] < B) return AGT_ERR_STATE;
     int rc = join_pipeline(c);            // frames of an earlier run still in flight (fused pipeline or library streams)
@@ -307,6 +309,25 @@ int agt_tracker_fb_check(agt_ctx* c, double fb_max_px)
     return AGT_OK;
 }
 
+bool visibility_args_ok(int corners_per_tag, double max_view_deg, int facing)
+{
+    return max_view_deg >= 0.0 && max_view_deg <= 90.0 && (facing == 1 || facing == -1) && corners_per_tag >= 4;       // (NaN fails both comparisons)
+}
+// (cos(pi / 2) is 6e-17 in double: at 90 degrees the rule is the plain back-face test, n . c < 0)
+double visibility_cos_max(double max_view_deg) { return max_view_deg == 90.0 ? 0.0 : cos(max_view_deg * (M_PI / 180.0)); }
+
+// Visibility rule of the reproject refresh (semantics: include/agt_hip.h; device side: agt_device.h agt_tag_visible, the refresh block of
+// agt_pnp_body.h).  Nothing about the launch forms changes: the refresh runs only under reproject, which is stage by stage already.
+int agt_tracker_visibility(agt_ctx* c, int corners_per_tag, double max_view_deg, int facing)
+{
+    if (!c || !visibility_args_ok(corners_per_tag, max_view_deg, facing)) return AGT_ERR_ARG;
+    if (max_view_deg > 0.0 && c->trk_ready && c->trk_n % corners_per_tag) return AGT_ERR_ARG;      // (switching off succeeds whatever the corner count)
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->vis_deg = max_view_deg; c->vis_cos_max = visibility_cos_max(max_view_deg); c->vis_cpt = corners_per_tag; c->vis_facing = facing;
+    return AGT_OK;
+}
+
 // move frame `f`'s ring entry when the ring size changes (only the newest frame is live after a join)
 static void ring_move(agt_ctx* c, long f, int old_ring, int new_ring)
 {
@@ -351,6 +372,7 @@ static void fill_estimate(const agt_ctx* c, AgtPnpParams* p, const float* d_img,
     p->track = c->tstate; p->state_out = d_state_out; p->corners_rw = corners_rw; p->status_rw = status_rw;
     p->enhance_ape = c->enhance_ape; p->reproject = c->reproject; p->min_points = c->min_points; p->gate_px = c->gate_px;
     p->tag_gate = c->tag_gate; p->fault = c->fault_dev;
+    if (c->vis_deg > 0.0) { p->vis_cpt = c->vis_cpt; p->vis_cos_max = c->vis_cos_max; p->vis_facing = c->vis_facing; }
 }
 
 // the solver of the launch's first frame `frame` (tracker frame index) reports to the polling host thread (agt_track_host_frame)
@@ -1215,6 +1237,7 @@ int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
 {
     if (!c || !d_frames || !d_dense_out) return AGT_ERR_ARG;
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
+    if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
@@ -1230,6 +1253,7 @@ int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, si
 {
     if (!c || !d_frames || !d_dense_out || count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
+    if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;

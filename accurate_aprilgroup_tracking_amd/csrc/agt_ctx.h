@@ -90,6 +90,8 @@ struct agt_ctx {
     int reproject, min_points, tag_gate;
     double gate_px;
     double fb_max_px;                        // agt_tracker_fb_check: forward-backward threshold of the tracker's LK, px (0 = off; on: stage-by-stage frames)
+    // agt_tracker_visibility: the reproject refresh revives visible tags only (vis_deg = 0: off)
+    double vis_deg, vis_cos_max; int vis_cpt, vis_facing;
     int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
     // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
     // record, +192 the word); seq(frame t) = hseq_off + t, monotonic across resets and rewinds
@@ -135,6 +137,9 @@ int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                   int n, int B, int crit_type, int crit_max_count, double crit_eps,
                   int flags, double min_eig_threshold, double fb_max_px);
 int lk_lds_min(int per_cu);
+// arguments of the visibility rule (agt_tracker_visibility, agt_tag_visibility): max_view_deg finite in [0, 90], facing +1 / -1, cpt >= 4
+bool visibility_args_ok(int corners_per_tag, double max_view_deg, int facing);
+double visibility_cos_max(double max_view_deg);                     // cos(max_view_deg), exactly 0 at 90
 
 // Wait for a sequence word in host-mapped memory that a kernel stores behind its results (system scope) to reach `want`; after 2 s
 // without it the stream is asked what happened (a launch failed, the device is gone).  Inline: the per-frame caller keeps it in its unit.

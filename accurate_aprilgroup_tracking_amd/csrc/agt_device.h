@@ -296,6 +296,35 @@ __device__ __forceinline__ void agt_project(const AgtCamera& cam, const double R
     }
 }
 
+// Pose-driven visibility of one planar tag (agt_tracker_visibility, agt_tag_visibility; the rule: include/agt_hip.h).  p: the tag's cpt
+// object points (x y z each); R, t: the pose.  With c = the mean of the points (summed in index order) and n = facing * (p3 - p0) x (p1 - p0),
+// the tag's +z axis under the reference's corner template (transform_helper.py:41-63), both taken to the camera frame:
+//     cos = -(n . c) / (|n| |c|),     visible <=> c.z > 0 && cos > cos_max
+// -- the cosine of the angle between the tag's outward normal and the ray back to the camera.  Correctly rounded sqrt and division: a
+// verdict, not a link of the solver's chain.  A degenerate tag (n = 0) has cos = NaN and is hidden.
+template <typename T>
+__device__ __forceinline__ bool agt_tag_visible(const T* p, int cpt, const double R[9], const double t[3], double facing, double cos_max, double& cos_out)
+{
+    double s[3] = { 0.0, 0.0, 0.0 };
+    for (int k = 0; k < cpt; k++) { s[0] += (double)p[k * 3]; s[1] += (double)p[k * 3 + 1]; s[2] += (double)p[k * 3 + 2]; }
+    const double inv = 1.0 / (double)cpt;
+    const double co[3] = { s[0] * inv, s[1] * inv, s[2] * inv };
+    const double a[3] = { (double)p[9] - (double)p[0], (double)p[10] - (double)p[1], (double)p[11] - (double)p[2] };      // p3 - p0
+    const double e[3] = { (double)p[3] - (double)p[0], (double)p[4] - (double)p[1], (double)p[5] - (double)p[2] };        // p1 - p0
+    const double no[3] = { facing * (a[1] * e[2] - a[2] * e[1]), facing * (a[2] * e[0] - a[0] * e[2]), facing * (a[0] * e[1] - a[1] * e[0]) };
+    double cc[3], nc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        cc[r] = R[r * 3] * co[0] + R[r * 3 + 1] * co[1] + R[r * 3 + 2] * co[2] + t[r];
+        nc[r] = R[r * 3] * no[0] + R[r * 3 + 1] * no[1] + R[r * 3 + 2] * no[2];
+    }
+    const double dot = nc[0] * cc[0] + nc[1] * cc[1] + nc[2] * cc[2];
+    const double nn = nc[0] * nc[0] + nc[1] * nc[1] + nc[2] * nc[2], cn = cc[0] * cc[0] + cc[1] * cc[1] + cc[2] * cc[2];
+    const double c = -dot / (sqrt(nn) * sqrt(cn));
+    cos_out = c;
+    return cc[2] > 0.0 && c > cos_max;
+}
+
 // One-sided Jacobi SVD of a 3x3 (row-major A).  Outputs sorted descending; U columns = left
 // vectors, Vt rows = right vectors (the layout of oracle cvo_svd).
 __device__ inline void agt_svd3(const double A[9], double W[3], double U[9], double Vt[9])

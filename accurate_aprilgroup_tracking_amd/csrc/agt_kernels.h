@@ -138,6 +138,11 @@ struct AgtPnpParams {
     // frame k of a launch stores host_seq_base + k.  null: off.
     unsigned long long* host_seq;
     unsigned long long host_seq_base;
+    // agt_tracker_visibility (vis_cpt != 0: on): the reproject refresh revives the corners of visible tags only (agt_device.h agt_tag_visible;
+    // tag t = corners vis_cpt * t ..) and clears the status of the others; read by the tracker-mode launches of agt_pnp.hip alone
+    double vis_cos_max;            // cos(max_view_deg); exactly 0 at 90 degrees
+    int vis_cpt;                   // corners per tag (>= 4; n / vis_cpt <= 64: one ballot holds the verdicts), 0 = rule off
+    int vis_facing;                // +1 / -1: the tag normal is facing * (p3 - p0) x (p1 - p0)
 };
 
 // device-resident per-stream tracker state: the attributes of PoseDetector
@@ -213,6 +218,12 @@ struct AgtProjParams {
     // agt_project_points_host (one block, B = 1): host-mapped sequence word stored behind the outputs (see AgtPnpParams::host_seq); null: off
     unsigned long long* host_seq;
     unsigned long long host_seq_base;
+    // visibility mode (agt_tag_visibility; vis_out != null): no projection -- thread i of stream b's blocks judges tag i (object points
+    // vis_cpt * i ..) under pose[b] with agt_tag_visible; img_out, jac and the camera are not read
+    uint8_t* vis_out;         // [B][n / vis_cpt]
+    double* vis_cos;          // [B][n / vis_cpt] or null
+    double vis_cos_max;
+    int vis_cpt, vis_facing;
 };
 
 // The dense stage's parameter block (agt_dense.hip: specification, mapping; agt_dense_body.h: the update).  The caller fills frame, model,

@@ -12,7 +12,7 @@ __global__ __launch_bounds__(AGT_WAVE) void pnp_kernel(const AgtPnpParams P)
 {
     __shared__ agt_pnp::PnpShared sh;
     // (issue priority 2 / 3 for the solver's wave beside co-tenant trackers at priority 1 gained nothing: profiles/r06_experiments.md)
-    agt_pnp::pnp_body<T, PPL>(P, blockIdx.x, sh, P.img, P.mask, P.state_out);
+    agt_pnp::pnp_body<T, PPL, agt_pnp::PnpNoHook, false, 1, false, true>(P, blockIdx.x, sh, P.img, P.mask, P.state_out);
     if (P.host_seq && blockIdx.x == 0) agt_host_seq_store(P.host_seq, P.host_seq_base, threadIdx.x == 0);
 }
 
@@ -39,8 +39,8 @@ __global__ __launch_bounds__(AGT_WAVE * COOP_WAVES) void pnp_coop_kernel(const A
     const bool guess = P.track ? (agt_uniform(P.track[b].has_guess) && P.enhance_ape) : P.use_guess != 0;
     // every wave has read the decision before wave 0 (alone, in the branch without a guess) may rewrite track[b].has_guess
     __syncthreads();
-    if (guess) agt_pnp::pnp_body<T, 1, agt_pnp::PnpNoHook, false, COOP_WAVES>(P, b, sh, P.img, P.mask, P.state_out);
-    else if (threadIdx.x < AGT_WAVE) agt_pnp::pnp_body<T, agt_pnp::MAX_PPL>(P, b, sh, P.img, P.mask, P.state_out);
+    if (guess) agt_pnp::pnp_body<T, 1, agt_pnp::PnpNoHook, false, COOP_WAVES, false, true>(P, b, sh, P.img, P.mask, P.state_out);
+    else if (threadIdx.x < AGT_WAVE) agt_pnp::pnp_body<T, agt_pnp::MAX_PPL, agt_pnp::PnpNoHook, false, 1, false, true>(P, b, sh, P.img, P.mask, P.state_out);
     if (P.host_seq && b == 0 && threadIdx.x < AGT_WAVE) agt_host_seq_store(P.host_seq, P.host_seq_base, threadIdx.x == 0);      // (wave 0 writes the record in both bodies)
 }
 
@@ -70,12 +70,29 @@ __device__ __forceinline__ void project_one(const AgtProjParams& P, int b, int i
     out[i * 2] = (T)u; out[i * 2 + 1] = (T)v;
 }
 
+// agt_tag_visibility: the visibility rule (agt_device.h agt_tag_visible) for tag i of stream b
+template <typename T>
+__device__ __forceinline__ void visible_one(const AgtProjParams& P, int b, int i)
+{
+    double param[6], R[9], G[9], cs;
+#pragma unroll
+    for (int k = 0; k < 6; k++) param[k] = P.pose[(long)b * 6 + k];
+    agt_rodrigues<false>(param, R, G);
+    const T* obj = reinterpret_cast<const T*>(P.obj) + (long)b * P.obj_bstride + (long)i * P.vis_cpt * 3;
+    const bool vis = agt_tag_visible(obj, P.vis_cpt, R, param + 3, (double)P.vis_facing, P.vis_cos_max, cs);
+    const long o = (long)b * (P.n / P.vis_cpt) + i;
+    P.vis_out[o] = vis ? 1 : 0;
+    if (P.vis_cos) P.vis_cos[o] = cs;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void project_kernel(const AgtProjParams P)
 {
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < P.n) project_one<T>(P, b, i);
+    if (P.vis_out) {
+        if (i < P.n / P.vis_cpt) visible_one<T>(P, b, i);      // (visibility mode: one thread per tag, nothing is projected)
+    } else if (i < P.n) project_one<T>(P, b, i);
     if (P.host_seq) {
         // one-block launch of agt_project_points_host: every wave's outputs (host-mapped memory) are performed at system scope before the
         // barrier, then one lane tells the polling host thread
@@ -113,7 +130,8 @@ hipError_t agt_launch_pnp(hipStream_t stream, const AgtPnpParams& p, int B, cons
 
 hipError_t agt_launch_project(hipStream_t stream, const AgtProjParams& p, int B)
 {
-    dim3 grid((p.n + 255) / 256, B), block(256);
+    const int items = p.vis_out ? p.n / p.vis_cpt : p.n;         // (visibility mode: tags)
+    dim3 grid((items + 255) / 256, B), block(256);
     if (p.dtype == AGT_F64) hipLaunchKernelGGL(project_kernel<double>, grid, block, 0, stream, p);
     else hipLaunchKernelGGL(project_kernel<float>, grid, block, 0, stream, p);
     return hipGetLastError();

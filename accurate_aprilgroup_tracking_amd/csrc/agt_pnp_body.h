@@ -497,7 +497,9 @@ struct PnpNoHook { __device__ __forceinline__ void operator()() const {} };
 // OPAQUE (a caller that runs the body inside a FRAME LOOP): the thread index goes through an empty volatile asm, so that nothing
 // derived from it is loop-invariant to the compiler -- hoisted out of the loop those values (lane-selected constants, addresses)
 // stay alive across both solver bodies and spill.
-template <typename T, int PPL, typename Hook = PnpNoHook, bool LDS_STATE = false, int COOP = 1, bool OPAQUE = false>
+// VIS: the corner refresh honours the visibility rule (P.vis_cpt; agt_tracker_visibility).  Set by the tracker-mode launches of agt_pnp.hip,
+// the only ones that run the refresh (reproject forces the stage-by-stage form): the frame-loop kernels do not carry the code.
+template <typename T, int PPL, typename Hook = PnpNoHook, bool LDS_STATE = false, int COOP = 1, bool OPAQUE = false, bool VIS = false>
 __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared& sh, const void* img_p, const uint8_t* mask_p,
                                          double* so_p, int extra_flags = 0, Hook before_state = Hook())
 {
@@ -1237,12 +1239,22 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
             double R[9], G[9];
             agt_rodrigues<false>(param, R, G);
             float* cw = P.corners_rw + (long)b * n * 2;
+            // visibility rule on: lane t judges tag t (at most 64 tags: n <= 256, >= 4 corners each), one ballot holds the verdicts
+            const int cpt = VIS ? P.vis_cpt : 0;
+            unsigned long long seen = ~0ull;
+            if (cpt > 0) {
+                double cs;
+                const bool vis = lane < n / cpt && agt_tag_visible(obj + (long)lane * cpt * 3, cpt, R, param + 3, (double)P.vis_facing, P.vis_cos_max, cs);
+                seen = __ballot(vis);
+                if (writer && so_p) so_p[(long)b * AGT_STATE_STRIDE + AGT_ST_NVISIBLE] = (double)__popcll(seen);
+            }
             for (int i = lane; i < n; i += AGT_WAVE) {
                 double u, v;
                 agt_project<false>(cam, R, G, param + 3, (double)obj[i * 3], (double)obj[i * 3 + 1], (double)obj[i * 3 + 2],
                                    u, v, nullptr, nullptr);
                 cw[i * 2] = (float)u; cw[i * 2 + 1] = (float)v;
-                if (P.status_rw) P.status_rw[(long)b * n + i] = 1;       // lost corners are re-seeded: trackable again
+                // lost corners are re-seeded: trackable again (under the rule: those of visible tags; a hidden tag's corners are not tracked)
+                if (P.status_rw) P.status_rw[(long)b * n + i] = cpt > 0 ? (uint8_t)((seen >> (i / cpt)) & 1) : 1;
             }
         }
         return;

@@ -294,6 +294,26 @@ class Context:
                                           _ptr(out), _ptr(jac)), "agt_project_points")
         return out, jac
 
+    def tag_visibility(self, obj, pose, corners_per_tag=4, max_view_deg=90.0, facing=1, want_cos=True):
+        """The visibility rule of agt_tracker_visibility for B poses (agt_tag_visibility): obj cuda [n,3] (shared) or [B,n,3], f32 or f64,
+        tag t = points corners_per_tag * t ..; pose cuda f64 [B,6].  A tag is visible when its centre is in front of the camera and the
+        angle between its outward normal (facing * (p3 - p0) x (p1 - p0)) and the ray back to the camera is below max_view_deg (0, 90].
+        -> (visible [B,T] u8, cos [B,T] f64 | None).  Enqueues only."""
+        assert obj.is_cuda and obj.is_contiguous() and obj.dtype in (torch.float32, torch.float64)
+        assert pose.dtype == torch.float64 and pose.is_contiguous() and pose.dim() == 2 and pose.shape[1] == 6
+        B = pose.shape[0]
+        shared = obj.dim() == 2
+        n = obj.shape[0] if shared else obj.shape[1]
+        assert shared or obj.shape[0] == B
+        cpt = int(corners_per_tag)
+        if cpt < 4 or n % cpt:
+            raise error("tag_visibility: %d points are not whole tags of %d corners (>= 4)" % (n, cpt))
+        vis = torch.empty((B, n // cpt), dtype=torch.uint8, device=obj.device)
+        cs = torch.empty((B, n // cpt), dtype=torch.float64, device=obj.device) if want_cos else None
+        H.check(self.L.agt_tag_visibility(self.h, _ptr(obj), 0 if shared else n * 3, H.F32 if obj.dtype == torch.float32 else H.F64, n, B,
+                                          _ptr(pose), cpt, float(max_view_deg), int(facing), _ptr(vis), _ptr(cs)), "agt_tag_visibility")
+        return vis, cs
+
 
 # ------------------------------------------------------------------------------------
 # numpy-in / numpy-out functions with cv2's signatures (one synchronous call per frame,
@@ -513,3 +533,31 @@ def projectPoints(objectPoints, rvec, tvec, cameraMatrix, distCoeffs, jacobian=F
         except H.AgtError as e:
             raise error(str(e))
         return out.cpu().numpy().reshape(n, 1, 2), (jac.cpu().numpy().reshape(2 * n, 6) if jacobian else None)
+
+
+def tagVisibility(objectPoints, rvec, tvec, cornersPerTag=4, maxViewDeg=90.0, facing=1):
+    """Which tags of a closed AprilGroup can be seen under a pose (no cv2 counterpart; the rule of agt_tracker_visibility, include/agt_hip.h):
+    objectPoints (N,3), tag t = points cornersPerTag * t ..; -> (visible (T,) bool, cos (T,) f64).  A tag is visible when its centre is
+    in front of the camera and cos -- of the angle between its outward normal and the ray back to the camera -- exceeds cos(maxViewDeg)."""
+    obj = np.asarray(objectPoints)
+    dt = np.float32 if obj.dtype == np.float32 else np.float64
+    obj = np.ascontiguousarray(obj.reshape(-1, 3), dtype=dt)
+    n, cpt = obj.shape[0], int(cornersPerTag)
+    if cpt < 4 or n == 0 or n % cpt:
+        raise error("tagVisibility: %d points are not whole tags of %d corners (>= 4)" % (n, cpt))
+    if not (0.0 < maxViewDeg <= 90.0) or facing not in (1, -1):
+        raise error("tagVisibility: maxViewDeg must be in (0, 90] and facing +1 or -1")
+    if np.size(rvec) != 3 or np.size(tvec) != 3:
+        raise error("tagVisibility: 3-element rvec and tvec are expected")
+    _require_gpu()
+    ctx = _geom_context(1)
+    with ctx.lock:
+        ctx.use_current_stream()
+        dev = torch.device("cuda", ctx.device)
+        g = np.concatenate([np.asarray(rvec, np.float64).reshape(3), np.asarray(tvec, np.float64).reshape(3)])
+        try:
+            vis, cs = ctx.tag_visibility(torch.from_numpy(obj).to(dev), torch.from_numpy(g).to(dev).reshape(1, 6).contiguous(),
+                                         cpt, float(maxViewDeg), int(facing))
+        except H.AgtError as e:
+            raise error(str(e))
+        return vis[0].cpu().numpy().astype(bool), cs[0].cpu().numpy()

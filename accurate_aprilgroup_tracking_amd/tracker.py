@@ -24,7 +24,10 @@ class TrackState(C.Structure):
 
 class StreamTracker:
     def __init__(self, width, height, obj_points, K, dist=None, n_streams=1, max_level=2, win=21,
-                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0):
+                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0, view_deg=0.0, facing=1):
+        if view_deg and not reproject:
+            # (the rule acts inside the reproject refresh only: accepting it here would be a silent no-op)
+            raise ValueError("StreamTracker: view_deg needs reproject=True (the visibility rule acts in the corner refresh)")
         obj = np.ascontiguousarray(np.asarray(obj_points, np.float32).reshape(-1, 3))
         self.n = obj.shape[0]
         self.B = n_streams
@@ -35,11 +38,14 @@ class StreamTracker:
         self.K, _ = _host_f64(K)
         self.dist, self.ndist = _host_f64(dist)
         self.enhance_ape = bool(enhance_ape)
+        self.reproject = bool(reproject)
         assert H.lib().agt_tracker_state_size() == C.sizeof(TrackState)
         H.check(self.ctx.L.agt_tracker_options(self.ctx.h, int(reproject), int(min_points), float(gate_px)),
                 "agt_tracker_options")
         if fb_check:
             self.fb_check(fb_check)
+        if view_deg:
+            self.visibility(view_deg, 4, facing)
         self._alive = []            # frames aliased by pyramid level 0 of the ring entries in flight
         self._keep_frames = max((max_level + 6) + 2, 12)
 
@@ -93,6 +99,17 @@ class StreamTracker:
         0 switches it off (the default).  While it is on, step() runs stage by stage whatever the pipeline depth, with one
         more LK launch per frame; step_dense() is refused.  May be changed mid-stream; joins the pipeline."""
         H.check(self.ctx.L.agt_tracker_fb_check(self.ctx.h, float(max_px)), "agt_tracker_fb_check")
+
+    def visibility(self, view_deg, corners_per_tag=4, facing=1):
+        """Visibility rule of the reproject refresh (agt_tracker_visibility): on a closed body the refresh revives only the corners of
+        tags whose centre is in front of the camera and whose outward normal (facing * (p3 - p0) x (p1 - p0)) is seen at less than
+        view_deg (0, 90] from the viewing ray; the corners of the other tags get status 0 (their positions are still refreshed) and
+        come back when the tag turns into view.  0 switches it off (the default).  Acts only with reproject=True; the record's
+        ST_NVISIBLE slot counts the visible tags.  While it is on, step_dense() is refused.  May be changed mid-stream; joins the
+        pipeline.  On a tracker built without reproject a non-zero view_deg raises ValueError, as in the constructor."""
+        if view_deg and not self.reproject:
+            raise ValueError("StreamTracker.visibility: view_deg needs reproject=True (the visibility rule acts in the corner refresh)")
+        H.check(self.ctx.L.agt_tracker_visibility(self.ctx.h, int(corners_per_tag), float(view_deg), int(facing)), "agt_tracker_visibility")
 
     def rewind(self):
         """Take the newest frame back as the tracking source: the next step() tracks from the frame before it (the reference

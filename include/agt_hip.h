@@ -79,6 +79,8 @@ extern "C" {
 #define AGT_ST_GUESS   10   /* 1.0 = an extrinsic guess was used for this frame */
 #define AGT_ST_FLAGS   11   /* AGT_PNP_* bits | AGT_TRK_* bits */
 #define AGT_ST_TVEC_F32 12  /* 1.0 = tvec carries float32 precision (cv2 wrote it into the f32 guess array) */
+#define AGT_ST_NVISIBLE 13  /* tags visible under the frame's accepted pose (agt_tracker_visibility); 0.0 while the rule is off, without the
+                               reproject option, or when the pose was not accepted */
 #define AGT_TRK_ZERO_VELOCITY 256  /* a velocity element was exactly 0: reference raises ValueError (detect_pose.py:236-237) */
 #define AGT_TRK_CHAIN_TIMEOUT 512  /* pipelined tracker: the pose solve gave up waiting for the frame's corners (or did so for an earlier frame of
                                       the stream): nothing was solved, the record is invalid, the stream's state is frozen until agt_tracker_reset */
@@ -189,6 +191,15 @@ int agt_project_points(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride,
                        const double* d_pose, const double* K, const double* dist, int ndist,
                        void* d_img_out, double* d_jac);
 
+/* ---- the visibility rule of agt_tracker_visibility as a call of its own ---- */
+/* d_obj: n x 3 (obj_batch_stride = 0: shared) or [B][n][3], dtype AGT_F32 / AGT_F64; n a multiple of corners_per_tag (>= 4);
+ * d_pose: [B][6] f64.  d_visible: [B][n / corners_per_tag] u8 (1 = visible), d_cos: the same shape in f64 or NULL: the cosine the
+ * verdict compares with cos(max_view_deg) (NaN for a degenerate tag, which is hidden).  max_view_deg in (0, 90], facing +1 / -1.  No
+ * camera is involved.  One launch on the context's stream; does not synchronise.  Present from ABI 505 on: look the symbol up. */
+int agt_tag_visibility(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
+                       const double* d_pose, int corners_per_tag, double max_view_deg, int facing,
+                       uint8_t* d_visible, double* d_cos);
+
 /* ---- the same two calls SYNCHRONOUS, host arrays in and out: what the reference does once per frame (cv2.solvePnP at
  * detect_pose.py:509-526, cv2.projectPoints at :441-465).  One launch each and no copy: the arguments are placed in a host-mapped
  * staging area of the context, the kernel reads them and writes its results there, the calling thread polls a sequence word the
@@ -249,6 +260,25 @@ int agt_tracker_tag_gate(agt_ctx* ctx, int corners_per_tag);
  * agt_track_frame_dense / agt_track_frames_dense return AGT_ERR_UNSUPPORTED while it is on.  Joins the pipeline.  fb_max_px must be
  * finite and >= 0 (AGT_ERR_ARG).  Present from ABI 505 on: look the symbol up. */
 int agt_tracker_fb_check(agt_ctx* ctx, double fb_max_px);
+/* Pose-driven tag visibility for the reproject refresh (max_view_deg = 0: off, the default).  An AprilGroup is a closed body: at most
+ * half of its tags face the camera, and the plain refresh -- projectPoints(all object points), every LK status back to 1 -- revives the
+ * corners of the tags on the far side, which LK then tracks on whatever front-side texture lies at those pixels.  With the rule on, the
+ * refresh still writes the position of every corner, but sets LK status 1 only for the corners of visible tags and 0 for the others.
+ * Tag t = corners corners_per_tag * t .. (p0 .. p(cpt-1)); in FP64, with the frame's accepted pose (R = Rodrigues(rvec), t):
+ *     c_o = mean of the tag's object points (summed in index order),   n_o = facing * (p3 - p0) x (p1 - p0)
+ *     c_c = R c_o + t,   n_c = R n_o,   cos = -(n_c . c_c) / (|n_c| |c_c|)
+ *     visible  <=>  c_c.z > 0  and  cos > cos(max_view_deg)
+ * With the reference's corner template (transform_helper.py:41-63) n_o is the tag's +z axis; facing = -1 is for models whose tag z axis
+ * points into the body.  max_view_deg = 90 is the plain back-face rule (the threshold is then exactly 0); a smaller angle also drops the
+ * tags seen at a grazing angle, whose LK windows are mostly background.  The frame's record carries the number of visible tags
+ * (AGT_ST_NVISIBLE).  The rule acts ONLY inside the reproject refresh (agt_tracker_options, of agt_track_frame* and of
+ * agt_track_frame_detected): without reproject it changes nothing.  It composes with agt_tracker_fb_check and agt_tracker_tag_gate: a
+ * corner either of them dropped is revived by the refresh only if its tag is visible.  agt_track_frame_dense / agt_track_frames_dense
+ * return AGT_ERR_UNSUPPORTED while it is on (their re-seed is a different kernel family, which does not carry the rule).  Joins the
+ * pipeline.  AGT_ERR_ARG: max_view_deg outside [0, 90] or not finite, facing not +1 / -1, corners_per_tag < 4, or -- once the tracker
+ * has been reset and max_view_deg > 0 -- a corner count that is no multiple of corners_per_tag; a later agt_tracker_reset with such a count returns
+ * AGT_ERR_ARG as well while the rule is on.  Present from ABI 505 on: look the symbol up. */
+int agt_tracker_visibility(agt_ctx* ctx, int corners_per_tag, double max_view_deg, int facing);
 /* Software pipelining across frames.  depth 0: separate launches per stage, the record of frame t is complete
  * in stream order after its call.  depth F in 1..32 (default 1; needs reproject == 0, otherwise the call falls back to
  * depth 0 behaviour): agt_track_frame registers the frame and, every F calls, issues ONE fused launch that advances every
