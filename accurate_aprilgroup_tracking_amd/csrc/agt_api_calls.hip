@@ -178,6 +178,82 @@ int agt_tag_visibility(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, i
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
+// ---- tag consensus (the rule: include/agt_hip.h agt_solve_pnp_consensus).  Three launches on one stream, nothing in between:
+//   1. the solver kernels over B * T problems of cpt points (hypothesis launch, agt_kernels.h AgtPnpParams::hyp_T)
+//   2. project_kernel in vote mode, one workgroup per stream: inlier bytes, votes, the winner's pose
+//   3. (stateless call) the ordinary masked solve from the winner's pose; (tracker) the unchanged pose step on the smaller mask
+int cons_scratch(agt_ctx* c, int B, int T, int n, ConsScratch* s)
+{
+    const size_t BT = (size_t)B * T;
+    const size_t o_info = BT * 6 * sizeof(double), o_win = o_info + BT * 4 * sizeof(int32_t), o_votes = o_win + (size_t)B * 6 * sizeof(double);
+    const size_t o_inl = o_votes + (size_t)B * 4 * sizeof(int32_t), need = o_inl + (size_t)B * n;
+    if (need > c->cons_cap) {
+        hipError_t e = hipStreamSynchronize(c->stream);          // (an earlier call's launches may still read the old block)
+        if (e != hipSuccess) return hip_fail(c, e);
+        if (c->cons_buf) (void)hipFree(c->cons_buf);
+        c->cons_buf = nullptr; c->cons_cap = 0;
+        if (hipMalloc((void**)&c->cons_buf, need) != hipSuccess) { hip_fail(c, hipGetLastError()); return AGT_ERR_ALLOC; }
+        c->cons_cap = need;
+    }
+    s->hyp_pose = (double*)c->cons_buf; s->hyp_info = (int32_t*)(c->cons_buf + o_info); s->win = (double*)(c->cons_buf + o_win);
+    s->votes = (int32_t*)(c->cons_buf + o_votes); s->inl = (uint8_t*)(c->cons_buf + o_inl);
+    return AGT_OK;
+}
+
+int consensus_on(agt_ctx* c, hipStream_t stream, const void* d_obj, long obj_bstride, const void* d_img, int dtype, const uint8_t* d_mask,
+                 int n, int B, const AgtCameraHost& cam, const double* d_start, int use_guess, const AgtTrackState* track,
+                 int cpt, double inlier_px, int min_inliers, uint8_t* d_inl, int32_t* d_votes, double* d_win, ConsScratch* s)
+{
+    const int T = n / cpt;
+    int rc = cons_scratch(c, B, T, n, s);
+    if (rc) return rc;
+    // a problem that ends early writes no pose: all-ones bytes are NaN poses and flags with every bit set, which the vote discards
+    hipError_t e = hipMemsetAsync(s->hyp_pose, 0xff, (size_t)B * T * (6 * sizeof(double) + 4 * sizeof(int32_t)), stream);
+    if (e != hipSuccess) return hip_fail(c, e);
+    AgtPnpParams h;
+    memset(&h, 0, sizeof(h));
+    h.cam = cam; h.obj = d_obj; h.obj_bstride = obj_bstride; h.img = d_img; h.mask = d_mask; h.dtype = dtype;
+    h.n = cpt; h.use_guess = use_guess ? 1 : 0; h.pose = s->hyp_pose; h.info = s->hyp_info; h.gate_px = 2.0;
+    h.hyp_T = T; h.hyp_pose = use_guess ? d_start : nullptr; h.hyp_track = track; h.enhance_ape = c->enhance_ape;
+    e = agt_launch_pnp(stream, h, B * T);
+    if (e != hipSuccess) return hip_fail(c, e);
+    AgtProjParams v;
+    memset(&v, 0, sizeof(v));
+    v.cam = cam; v.obj = d_obj; v.obj_bstride = obj_bstride; v.dtype = dtype; v.n = n;
+    v.vote_img = d_img; v.vote_mask = d_mask; v.vote_pose = s->hyp_pose; v.vote_info = s->hyp_info;
+    v.vote_inl = d_inl ? d_inl : s->inl; v.vote_votes = d_votes ? d_votes : s->votes; v.vote_win = d_win ? d_win : s->win;
+    v.vote_tau2 = inlier_px * inlier_px; v.vote_cpt = cpt; v.vote_min = min_inliers;
+    e = agt_launch_project(stream, v, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int agt_solve_pnp_consensus(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
+                            const uint8_t* d_mask, int n, int B, const double* K, const double* dist, int ndist,
+                            double* d_pose, int use_guess, int corners_per_tag, double inlier_px, int min_inliers,
+                            uint8_t* d_inliers, int32_t* d_votes, int32_t* d_info, double* d_err)
+{
+    if (!c || !d_obj || !d_img || !d_pose || !d_inliers || B <= 0 || n <= 0) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (!(inlier_px > 0.0) || !(inlier_px <= 1.0e150)) return AGT_ERR_ARG;             // (NaN fails both; the square stays finite)
+    if (corners_per_tag < 4 || n % corners_per_tag || min_inliers < corners_per_tag) return AGT_ERR_ARG;
+    if (n > 256 || n / corners_per_tag > 64) return AGT_ERR_NPOINTS;
+    AgtPnpParams p;
+    memset(&p, 0, sizeof(p));
+    int rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    ConsScratch s;
+    // (with a guess the hypotheses start from d_pose, which the vote then overwrites with the winner's pose: same stream, in order)
+    rc = consensus_on(c, c->stream, d_obj, (long)obj_batch_stride, d_img, dtype, d_mask, n, B, p.cam, d_pose, use_guess, nullptr,
+                      corners_per_tag, inlier_px, min_inliers, d_inliers, d_votes, d_pose, &s);
+    if (rc) return rc;
+    // the refit: agt_solve_pnp(mask = inliers, use_guess = 1).  A stream without consensus has an all-zero mask: pose untouched, info TOO_FEW
+    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.img = d_img; p.mask = d_inliers; p.dtype = dtype;
+    p.n = n; p.use_guess = 1; p.pose = d_pose; p.info = d_info; p.err = d_err;
+    p.gate_px = 2.0;
+    hipError_t e = agt_launch_pnp(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
 // ---- the reference's per-frame calls as ONE synchronous call each, host arrays in and out (detect_pose.py:509-526 solvePnP,
 // :441-465 projectPoints).  No copies are enqueued: the arguments go into a host-mapped staging area of the
 // context, the kernel reads them and writes its results there over PCIe and stores a sequence word behind them (system scope), the

@@ -8,6 +8,7 @@
 #include <math.h>
 
 // ---- the idioms of the unit: ring entry of tracker frame `frame`; level l of the pyramid in ring entry `slot` (level 0 is the caller's frame)
+static inline bool consensus_shape_ok(const agt_ctx* c, int n) { return n % c->cons_cpt == 0 && n / c->cons_cpt <= 64; }
 static inline int ring_slot(const agt_ctx* c, long frame) { return (int)(frame % c->live_ring); }
 static inline const uint8_t* level_ptr(const agt_ctx* c, int slot, int l) { return l == 0 ? c->l0_ptr[slot] : c->lmem[slot][l]; }
 static inline bool frame_args_ok(const agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t batch_stride)
@@ -225,6 +226,7 @@ int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float*
     if (n < 4 || n > c->cfg.max_points) return AGT_ERR_NPOINTS;
     if (c->tag_gate && n % c->tag_gate) return AGT_ERR_NPOINTS;      // whole tags: corners 4t .. 4t + 3
     if (c->vis_deg > 0.0 && n % c->vis_cpt) return AGT_ERR_ARG;      // (agt_tracker_visibility: whole tags as well)
+    if (c->cons_px > 0.0 && !consensus_shape_ok(c, n)) return AGT_ERR_ARG;      // (agt_tracker_consensus: whole tags, at most 64 of them)
     if (B <= 0 || B > c->cfg.max_streams) return AGT_ERR_ARG;
     if (d_corners && c->built_B[slot] < B) return AGT_ERR_STATE;
     int rc = join_pipeline(c);            // frames of an earlier run still in flight (fused pipeline or library streams)
@@ -325,6 +327,31 @@ int agt_tracker_visibility(agt_ctx* c, int corners_per_tag, double max_view_deg,
     int rc = join_pipeline(c);
     if (rc) return rc;
     c->vis_deg = max_view_deg; c->vis_cos_max = visibility_cos_max(max_view_deg); c->vis_cpt = corners_per_tag; c->vis_facing = facing;
+    return AGT_OK;
+}
+
+// Tag consensus in front of the tracker's pose step (semantics: include/agt_hip.h).  While it is on, frames take the stage-by-stage form
+// whatever the pipeline depth, as under fb_check and reproject: the hypothesis and vote launches sit between the LK and the pose launch.
+int agt_tracker_consensus(agt_ctx* c, int corners_per_tag, double inlier_px, int min_inliers)
+{
+    if (!c || !(inlier_px >= 0.0) || !(inlier_px <= 1.0e150)) return AGT_ERR_ARG;       // (NaN fails both)
+    if (corners_per_tag < 4 || corners_per_tag > 64 || min_inliers < corners_per_tag) return AGT_ERR_ARG;      // (the per-stream guess decision is the one-wave solver's)
+    if (inlier_px > 0.0 && c->trk_ready && (c->trk_n % corners_per_tag || c->trk_n / corners_per_tag > 64)) return AGT_ERR_ARG;
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    c->cons_px = inlier_px; c->cons_cpt = corners_per_tag; c->cons_min = min_inliers;
+    return AGT_OK;
+}
+
+// the frame's consensus over the corners the pose step `p` is about to solve on (p->img, p->mask): two launches on `stream`, after which
+// the step uses a corner only while it is an inlier as well and reports the winning count
+static int tracker_consensus_on(agt_ctx* c, hipStream_t stream, AgtPnpParams* p, int B)
+{
+    ConsScratch s;
+    int rc = consensus_on(c, stream, c->obj, 0, p->img, AGT_F32, p->mask, c->trk_n, B, c->cam, nullptr, 0, c->tstate,
+                          c->cons_cpt, c->cons_px, c->cons_min, nullptr, nullptr, nullptr, &s);
+    if (rc) return rc;
+    p->cons_inl = s.inl; p->cons_votes = s.votes;
     return AGT_OK;
 }
 
@@ -847,6 +874,7 @@ int agt_estimate_pose(agt_ctx* c, const float* d_img, const uint8_t* d_mask, int
     if (rc) return rc;
     AgtPnpParams p;
     fill_estimate(c, &p, d_img, d_mask, d_state_out, nullptr);
+    if (c->cons_px > 0.0 && (rc = tracker_consensus_on(c, c->stream, &p, B))) return rc;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
@@ -876,7 +904,7 @@ static SerialForm serial_form(const agt_ctx* c, int pslot, int slot, int nslot, 
     const bool wide = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
     // (forward-backward check on: the stand-alone LK launch, which the verdict launch follows -- not the LK role, not the chained or
     // the deferring forms that build on it)
-    const bool fb = c->fb_max_px > 0.0;
+    const bool fb = c->fb_max_px > 0.0 || c->cons_px > 0.0;      // (tag consensus: the same -- its launches go between LK and the pose launch)
     f.lk_role_launch = wide && !fb && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
     // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
     // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
@@ -992,6 +1020,7 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
     }
     if (rc) return rc;
     if (pev) (void)hipEventRecord(pev[2], M);
+    if (c->cons_px > 0.0 && (rc = tracker_consensus_on(c, M, &p, B))) return rc;
     hipError_t e = f.chain_pnp ? hipSuccess : agt_launch_pnp(M, p, B, f.ride_pnp ? npyr : nullptr);
     if (e != hipSuccess) return hip_fail(c, e);
     if (pev) { (void)hipEventRecord(pev[3], M); c->prof_n++; }
@@ -1015,7 +1044,7 @@ int agt_track_frame(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t ba
     hipEvent_t* pev = profile_events(c);
     // the fused launch pays off while the stages are latency-bound (few streams); the biggest batches fill
     // the chip per stage and run faster as separate launches with their own register budgets
-    if (c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && (agt_step_fits(c->trk_n, B) || !pev)) {
+    if (c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && (agt_step_fits(c->trk_n, B) || !pev)) {
         // fused launch: the three spans collapse into one (span 2 = the whole step_kernel launch)
         if (pev) { (void)hipEventRecord(pev[0], c->stream); (void)hipEventRecord(pev[1], c->stream); (void)hipEventRecord(pev[2], c->stream); }
         int rc = step_pipelined(c, d_frames, pitch, batch_stride, B, d_state_out);
@@ -1058,6 +1087,7 @@ int agt_track_frame_detected(agt_ctx* c, const uint8_t* d_frames, size_t pitch, 
     AgtPnpParams p;
     fill_estimate(c, &p, d_corners, d_mask, d_state_out, c->corners[slot], c->status[slot]);
     p.seed_pts = c->corners[slot]; p.seed_status = c->status[slot];
+    if (c->cons_px > 0.0 && (rc = tracker_consensus_on(c, c->stream, &p, B))) return rc;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     if (e != hipSuccess) return hip_fail(c, e);
     frame_complete(c, t);
@@ -1122,7 +1152,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
         // level 0 to d_gray on the way (step_pipelined_uploaded) -- one launch instead of a copy-engine transfer (19 us + ~8 us of
         // submission and hand-over) and a pyramid launch (6 us).  Pageable memory, frame sizes the rolling pass does not take, the
         // stage-by-stage mode and pending pyramid work of earlier frames keep the copy.
-        if (h_dev && polled && c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && agt_step_fits(c->trk_n, 1)) {
+        if (h_dev && polled && c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && agt_step_fits(c->trk_n, 1)) {
             int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
             if (rcu < 0) return rcu;
             registered = rcu == AGT_OK;
@@ -1238,6 +1268,7 @@ int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
     if (!c || !d_frames || !d_dense_out) return AGT_ERR_ARG;
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
+    if (c->cons_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor do they leave room for the consensus launches: agt_tracker_consensus)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
@@ -1254,6 +1285,7 @@ int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, si
     if (!c || !d_frames || !d_dense_out || count < 0 || (frame_stride & 3)) return AGT_ERR_ARG;
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
+    if (c->cons_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor do they leave room for the consensus launches: agt_tracker_consensus)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;

@@ -92,6 +92,9 @@ struct agt_ctx {
     double fb_max_px;                        // agt_tracker_fb_check: forward-backward threshold of the tracker's LK, px (0 = off; on: stage-by-stage frames)
     // agt_tracker_visibility: the reproject refresh revives visible tags only (vis_deg = 0: off)
     double vis_deg, vis_cos_max; int vis_cpt, vis_facing;
+    // agt_tracker_consensus: per-frame tag consensus in front of the pose step (cons_px = 0: off; on: stage-by-stage frames)
+    double cons_px; int cons_cpt, cons_min;
+    char* cons_buf; size_t cons_cap;         // scratch of the consensus calls (cons_scratch): hypotheses, and the tracker's inlier bytes / votes
     int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
     // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
     // record, +192 the word); seq(frame t) = hseq_off + t, monotonic across resets and rewinds
@@ -137,6 +140,14 @@ int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                   int n, int B, int crit_type, int crit_max_count, double crit_eps,
                   int flags, double min_eig_threshold, double fb_max_px);
 int lk_lds_min(int per_cu);
+// Scratch of one consensus call over B streams of T tags (agt_api_calls.hip): grown when too small, never shrunk
+struct ConsScratch { double* hyp_pose; int32_t* hyp_info; double* win; uint8_t* inl; int32_t* votes; };
+int cons_scratch(agt_ctx* c, int B, int T, int n, ConsScratch* s);
+// hypothesis launch + vote launch on `stream`; fills s.  track != null: the tracker's form (guess per stream from the state; the winner's
+// pose stays in scratch).  d_inl / d_votes / d_win null: the scratch arrays.
+int consensus_on(agt_ctx* c, hipStream_t stream, const void* d_obj, long obj_bstride, const void* d_img, int dtype, const uint8_t* d_mask,
+                 int n, int B, const AgtCameraHost& cam, const double* d_start, int use_guess, const AgtTrackState* track,
+                 int cpt, double inlier_px, int min_inliers, uint8_t* d_inl, int32_t* d_votes, double* d_win, ConsScratch* s);
 // arguments of the visibility rule (agt_tracker_visibility, agt_tag_visibility): max_view_deg finite in [0, 90], facing +1 / -1, cpt >= 4
 bool visibility_args_ok(int corners_per_tag, double max_view_deg, int facing);
 double visibility_cos_max(double max_view_deg);                     // cos(max_view_deg), exactly 0 at 90

@@ -143,6 +143,19 @@ struct AgtPnpParams {
     double vis_cos_max;            // cos(max_view_deg); exactly 0 at 90 degrees
     int vis_cpt;                   // corners per tag (>= 4; n / vis_cpt <= 64: one ballot holds the verdicts), 0 = rule off
     int vis_facing;                // +1 / -1: the tag normal is facing * (p3 - p0) x (p1 - p0)
+    // Tag consensus (agt_solve_pnp_consensus, agt_tracker_consensus); read by the launches of agt_pnp.hip alone (template flag CONS).
+    // Hypothesis launch (hyp_T != 0): problem g of the grid is tag g % hyp_T of stream s = g / hyp_T -- n is the corner count of ONE tag,
+    // img / mask / pose / info / err are indexed by g ([B * hyp_T][n] views of the caller's [B][n * hyp_T] arrays), the object points are
+    // obj + s * obj_bstride + (g % hyp_T) * n * 3, and the solve starts from hyp_pose[s] (use_guess) or, in the tracker, from
+    // hyp_track[s].guess when that stream has a guess and enhance_ape is set (which then decides use_guess per stream).
+    int hyp_T;
+    int pad2_;
+    const double* hyp_pose;                  // [B][6] or null: start from pose[g]
+    const struct AgtTrackState* hyp_track;   // [B] or null
+    // Pose step of the tracker under the option: a corner is used while mask AND cons_inl say so; the record's AGT_ST_NINLIER slot
+    // carries cons_votes[b][1].  Both null: off.
+    const uint8_t* cons_inl;                 // [B][n]
+    const int32_t* cons_votes;               // [B][4]
 };
 
 // device-resident per-stream tracker state: the attributes of PoseDetector
@@ -224,6 +237,19 @@ struct AgtProjParams {
     double* vis_cos;          // [B][n / vis_cpt] or null
     double vis_cos_max;
     int vis_cpt, vis_facing;
+    // vote mode (agt_solve_pnp_consensus; vote_inl != null): ONE workgroup per stream, thread i owns corner i (n <= 256).  Every usable
+    // corner is projected under every accepted hypothesis (vote_pose / vote_info: the hypothesis launch's results, [B][T][6] / [B][T][4],
+    // T = n / vote_cpt); the workgroup elects the hypothesis with the most inliers and writes the stream's inlier bytes, its votes row and,
+    // when there is a consensus, the winner's pose to vote_win[b].  img_out, jac and pose are not read.
+    const void* vote_img;     // [B][n][2], dtype as obj
+    const uint8_t* vote_mask; // [B][n] or null
+    const double* vote_pose;
+    const int32_t* vote_info;
+    uint8_t* vote_inl;        // [B][n]
+    int32_t* vote_votes;      // [B][4] or null: winning tag (-1: none), its inlier count (0: none), candidate tags, accepted hypotheses
+    double* vote_win;         // [B][6]
+    double vote_tau2;         // inlier_px^2
+    int vote_cpt, vote_min;
 };
 
 // The dense stage's parameter block (agt_dense.hip: specification, mapping; agt_dense_body.h: the update).  The caller fills frame, model,

@@ -12,7 +12,7 @@ __global__ __launch_bounds__(AGT_WAVE) void pnp_kernel(const AgtPnpParams P)
 {
     __shared__ agt_pnp::PnpShared sh;
     // (issue priority 2 / 3 for the solver's wave beside co-tenant trackers at priority 1 gained nothing: profiles/r06_experiments.md)
-    agt_pnp::pnp_body<T, PPL, agt_pnp::PnpNoHook, false, 1, false, true>(P, blockIdx.x, sh, P.img, P.mask, P.state_out);
+    agt_pnp::pnp_body<T, PPL, agt_pnp::PnpNoHook, false, 1, false, true, true>(P, blockIdx.x, sh, P.img, P.mask, P.state_out);
     if (P.host_seq && blockIdx.x == 0) agt_host_seq_store(P.host_seq, P.host_seq_base, threadIdx.x == 0);
 }
 
@@ -39,8 +39,8 @@ __global__ __launch_bounds__(AGT_WAVE * COOP_WAVES) void pnp_coop_kernel(const A
     const bool guess = P.track ? (agt_uniform(P.track[b].has_guess) && P.enhance_ape) : P.use_guess != 0;
     // every wave has read the decision before wave 0 (alone, in the branch without a guess) may rewrite track[b].has_guess
     __syncthreads();
-    if (guess) agt_pnp::pnp_body<T, 1, agt_pnp::PnpNoHook, false, COOP_WAVES, false, true>(P, b, sh, P.img, P.mask, P.state_out);
-    else if (threadIdx.x < AGT_WAVE) agt_pnp::pnp_body<T, agt_pnp::MAX_PPL, agt_pnp::PnpNoHook, false, 1, false, true>(P, b, sh, P.img, P.mask, P.state_out);
+    if (guess) agt_pnp::pnp_body<T, 1, agt_pnp::PnpNoHook, false, COOP_WAVES, false, true, true>(P, b, sh, P.img, P.mask, P.state_out);
+    else if (threadIdx.x < AGT_WAVE) agt_pnp::pnp_body<T, agt_pnp::MAX_PPL, agt_pnp::PnpNoHook, false, 1, false, true, true>(P, b, sh, P.img, P.mask, P.state_out);
     if (P.host_seq && b == 0 && threadIdx.x < AGT_WAVE) agt_host_seq_store(P.host_seq, P.host_seq_base, threadIdx.x == 0);      // (wave 0 writes the record in both bodies)
 }
 
@@ -85,12 +85,106 @@ __device__ __forceinline__ void visible_one(const AgtProjParams& P, int b, int i
     if (P.vis_cos) P.vis_cos[o] = cs;
 }
 
+// agt_solve_pnp_consensus: vote and selection for stream b by ONE workgroup of VOTE_WAVES waves (the rule: include/agt_hip.h).  Thread i
+// owns corner i and walks the T hypotheses; per hypothesis each wave files its inlier ballot and the sum of its inliers' squared
+// residuals in LDS.  Behind one barrier lane t of wave 0 totals hypothesis t (waves in order: the sums are reproducible), thread 0
+// elects, and behind a second barrier every thread reads its own bit of the winner's ballots.
+constexpr int VOTE_WAVES = 4, VOTE_TAGS = 64;
+struct VoteShared {
+    unsigned long long ballot[VOTE_WAVES][VOTE_TAGS];
+    double ssq[VOTE_WAVES][VOTE_TAGS];
+    double tssq[VOTE_TAGS];
+    int count[VOTE_TAGS];          // -1: no accepted hypothesis
+    int broken[VOTE_TAGS];         // != 0: a corner of the tag is not usable -- the tag is no candidate
+    int winner;
+};
+
+template <typename T>
+__device__ __forceinline__ void vote_stream(const AgtProjParams& P, int b, VoteShared& sh)
+{
+    const int n = P.n, cpt = P.vote_cpt, nt = n / cpt;
+    const int i = (int)threadIdx.x, lane = i & (AGT_WAVE - 1), wave = agt_uniform(i >> 6);
+    AgtCamera cam;
+    load_cam<T>(P.cam, cam);
+    const T* obj = reinterpret_cast<const T*>(P.obj) + (long)b * P.obj_bstride;
+    const T* img = reinterpret_cast<const T*>(P.vote_img) + (long)b * n * 2;
+    const bool usable = i < n && (!P.vote_mask || P.vote_mask[(long)b * n + i] != 0);
+    double X = 0.0, Y = 0.0, Z = 0.0, mx = 0.0, my = 0.0;
+    if (i < n) {
+        X = (double)obj[i * 3]; Y = (double)obj[i * 3 + 1]; Z = (double)obj[i * 3 + 2];
+        mx = (double)img[i * 2]; my = (double)img[i * 2 + 1];
+    }
+    if (i < VOTE_TAGS) sh.broken[i] = 0;
+    __syncthreads();
+    if (i < n && !usable) sh.broken[i / cpt] = 1;           // (every writer stores the same value)
+    __syncthreads();
+    for (int t = 0; t < nt; t++) {
+        // accepted: a candidate tag whose solve reported neither SINGULAR nor TOO_FEW and left six finite numbers (uniform)
+        const long g = (long)b * nt + t;
+        double prm[6];
+        bool ok = sh.broken[t] == 0 && (P.vote_info[g * 4 + AGT_INFO_FLAGS] & (AGT_PNP_SINGULAR | AGT_PNP_TOO_FEW)) == 0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) { prm[k] = P.vote_pose[g * 6 + k]; ok = ok && fabs(prm[k]) <= 1.7976931348623157e308; }     // (false for NaN, inf)
+        unsigned long long bal = 0;
+        double s = 0.0;
+        if (ok) {
+            double R[9], G[9], u, v;
+            agt_rodrigues<false>(prm, R, G);
+            agt_project<false>(cam, R, G, prm + 3, X, Y, Z, u, v, nullptr, nullptr);
+            const double zc = R[6] * X + R[7] * Y + R[8] * Z + prm[5];
+            const double du = u - mx, dv = v - my, d2 = du * du + dv * dv;
+            const bool inl = usable && zc > 0.0 && d2 < P.vote_tau2;          // (false for NaN)
+            bal = __ballot(inl);
+            s = agt_pnp::wave_sum_f64(inl ? d2 : 0.0);
+        }
+        if (lane == 0) { sh.ballot[wave][t] = bal; sh.ssq[wave][t] = s; }
+        if (i == 0) sh.count[t] = ok ? 0 : -1;
+    }
+    __syncthreads();
+    if (i < nt && sh.count[i] == 0) {
+        int cnt = 0;
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < VOTE_WAVES; w++) { cnt += __popcll(sh.ballot[w][i]); s += sh.ssq[w][i]; }
+        sh.count[i] = cnt; sh.tssq[i] = s;
+    }
+    __syncthreads();
+    if (i == 0) {
+        // most inliers; then the smaller sum of squares; then the lower tag (ascending walk, strict comparisons)
+        int best = -1, bc = -1, n_cand = 0, n_hyp = 0;
+        double bs = 0.0;
+        for (int t = 0; t < nt; t++) {
+            if (!sh.broken[t]) n_cand++;
+            const int ct = sh.count[t];
+            if (ct < 0) continue;
+            n_hyp++;
+            const double st = sh.tssq[t];
+            if (best < 0 || ct > bc || (ct == bc && st < bs)) { best = t; bc = ct; bs = st; }
+        }
+        if (best >= 0 && bc < P.vote_min) best = -1;
+        sh.winner = best;
+        if (P.vote_votes) {
+            int32_t* vo = P.vote_votes + (long)b * 4;
+            vo[0] = best; vo[1] = best >= 0 ? bc : 0; vo[2] = n_cand; vo[3] = n_hyp;
+        }
+        if (best >= 0) {
+            for (int k = 0; k < 6; k++) P.vote_win[(long)b * 6 + k] = P.vote_pose[((long)b * nt + best) * 6 + k];
+        }
+    }
+    __syncthreads();
+    const int win = sh.winner;
+    if (i < n) P.vote_inl[(long)b * n + i] = win >= 0 ? (uint8_t)((sh.ballot[wave][win] >> lane) & 1) : (uint8_t)0;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void project_kernel(const AgtProjParams P)
 {
     const int b = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (P.vis_out) {
+    if (P.vote_inl) {
+        __shared__ VoteShared vsh;
+        vote_stream<T>(P, b, vsh);           // (vote mode: one workgroup per stream, blockDim.x = 64 * VOTE_WAVES, nothing is written to img_out)
+    } else if (P.vis_out) {
         if (i < P.n / P.vis_cpt) visible_one<T>(P, b, i);      // (visibility mode: one thread per tag, nothing is projected)
     } else if (i < P.n) project_one<T>(P, b, i);
     if (P.host_seq) {
@@ -130,7 +224,8 @@ hipError_t agt_launch_pnp(hipStream_t stream, const AgtPnpParams& p, int B, cons
 
 hipError_t agt_launch_project(hipStream_t stream, const AgtProjParams& p, int B)
 {
-    const int items = p.vis_out ? p.n / p.vis_cpt : p.n;         // (visibility mode: tags)
+    if (p.vote_inl && (p.n > 64 * VOTE_WAVES || p.vote_cpt <= 0 || p.n / p.vote_cpt > VOTE_TAGS)) return hipErrorInvalidValue;
+    const int items = p.vote_inl ? 1 : p.vis_out ? p.n / p.vis_cpt : p.n;         // (vote mode: one workgroup per stream; visibility mode: tags)
     dim3 grid((items + 255) / 256, B), block(256);
     if (p.dtype == AGT_F64) hipLaunchKernelGGL(project_kernel<double>, grid, block, 0, stream, p);
     else hipLaunchKernelGGL(project_kernel<float>, grid, block, 0, stream, p);

@@ -499,7 +499,10 @@ struct PnpNoHook { __device__ __forceinline__ void operator()() const {} };
 // stay alive across both solver bodies and spill.
 // VIS: the corner refresh honours the visibility rule (P.vis_cpt; agt_tracker_visibility).  Set by the tracker-mode launches of agt_pnp.hip,
 // the only ones that run the refresh (reproject forces the stage-by-stage form): the frame-loop kernels do not carry the code.
-template <typename T, int PPL, typename Hook = PnpNoHook, bool LDS_STATE = false, int COOP = 1, bool OPAQUE = false, bool VIS = false>
+// CONS: the tag-consensus fields of AgtPnpParams are honoured (hypothesis launches: hyp_T, hyp_pose, hyp_track; the tracker's pose step
+// under agt_tracker_consensus: cons_inl, cons_votes).  Set by the launches of agt_pnp.hip alone, like VIS: the option forces the
+// stage-by-stage form.
+template <typename T, int PPL, typename Hook = PnpNoHook, bool LDS_STATE = false, int COOP = 1, bool OPAQUE = false, bool VIS = false, bool CONS = false>
 __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared& sh, const void* img_p, const uint8_t* mask_p,
                                          double* so_p, int extra_flags = 0, Hook before_state = Hook())
 {
@@ -535,14 +538,18 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
     // ---- this lane's correspondences
     double X[PPL], Y[PPL], Z[PPL], mu_[PPL], mv_[PPL];
     bool use[PPL];
-    const T* obj = reinterpret_cast<const T*>(P.obj) + (long)b * P.obj_bstride;
+    // hypothesis launch (CONS, P.hyp_T != 0): problem b is tag b % hyp_T of stream hs, its object points a slice of that stream's
+    const int hyp_T = CONS ? P.hyp_T : 0;
+    const int hs = hyp_T ? b / hyp_T : b;
+    const T* obj = reinterpret_cast<const T*>(P.obj) + (long)hs * P.obj_bstride + (hyp_T ? (long)(b - hs * hyp_T) * n * 3 : 0L);
     const T* img = reinterpret_cast<const T*>(img_p) + (long)b * n * 2;
     const uint8_t* mask = mask_p ? mask_p + (long)b * n : nullptr;
+    const uint8_t* cons = (CONS && P.cons_inl) ? P.cons_inl + (long)b * n : nullptr;      // (this frame's consensus inliers: agt_tracker_consensus)
     int cnt = 0;
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
         const int i = lane + (q * COOP + wave) * AGT_WAVE;
-        use[q] = i < n && (!mask || mask[i] != 0);
+        use[q] = i < n && (!mask || mask[i] != 0) && (!cons || cons[i] != 0);
         X[q] = Y[q] = Z[q] = mu_[q] = mv_[q] = 0.0;
         if (use[q]) {
             X[q] = (double)obj[i * 3]; Y[q] = (double)obj[i * 3 + 1]; Z[q] = (double)obj[i * 3 + 2];
@@ -622,13 +629,19 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                     double* so = so_p + (long)b * AGT_STATE_STRIDE;
                     for (int i = 0; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
                     so[AGT_ST_NTRACK] = n_used; so[AGT_ST_FLAGS] = AGT_PNP_TOO_FEW | flags;
+                    if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
                 }
             }
             return;
         }
     } else {
+        const double* start = P.pose + (long)b * 6;
+        if constexpr (CONS) {
+            if (P.hyp_track) { use_guess = agt_uniform(P.hyp_track[hs].has_guess) && P.enhance_ape; start = P.hyp_track[hs].guess; }
+            else if (P.hyp_pose) start = P.hyp_pose + (long)hs * 6;
+        }
 #pragma unroll
-        for (int i = 0; i < 6; i++) param[i] = P.pose[(long)b * 6 + i];
+        for (int i = 0; i < 6; i++) param[i] = start[i];
     }
 
     const bool enough = use_guess ? n_used >= 3 : n_used >= 4;      // the DLT branch re-checks for >= 6
@@ -943,6 +956,7 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                     double* so = so_p + (long)b * AGT_STATE_STRIDE;
                     for (int i = 0; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
                     so[AGT_ST_NTRACK] = n_used; so[AGT_ST_FLAGS] = AGT_PNP_TOO_FEW | flags;
+                    if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
                 }
             }
             return;
@@ -1232,6 +1246,7 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                 so[AGT_ST_ITERS] = iters; so[AGT_ST_GUESS] = use_guess ? 1.0 : 0.0; so[AGT_ST_FLAGS] = tflags;
                 so[AGT_ST_TVEC_F32] = tvec_f32 ? 1.0 : 0.0;
                 for (int i = AGT_ST_TVEC_F32 + 1; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
+                if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
             }
         }
         if (accepted && P.reproject && P.corners_rw) {

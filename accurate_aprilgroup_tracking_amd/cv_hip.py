@@ -277,6 +277,35 @@ class Context:
                                      _ptr(pose), 1 if use_guess else 0, _ptr(info), _ptr(err)), "agt_solve_pnp")
         return pose, info, err
 
+    def solve_pnp_consensus(self, obj, img, K, dist, pose=None, use_guess=False, mask=None, corners_per_tag=4, inlier_px=2.0, min_inliers=8):
+        """Tag-consensus solvePnP (agt_solve_pnp_consensus; the rule: include/agt_hip.h): arguments as solve_pnp, tag t = points
+        corners_per_tag * t ...  Every whole usable tag is solved alone, every usable corner votes on every tag's pose, the pose is the
+        masked solve on the winner's inliers.  -> (pose [B,6] f64, inliers [B,n] u8, votes [B,4] i32: winning tag (-1: none), its count,
+        candidate tags, accepted hypotheses; info [B,4] i32, err [B] f64).  A stream without consensus keeps its pose and reports
+        INFO_OK = 0 with PNP_TOO_FEW.  Enqueues only."""
+        assert obj.is_cuda and img.is_cuda and obj.dtype == img.dtype and obj.dtype in (torch.float32, torch.float64)
+        assert obj.is_contiguous() and img.is_contiguous()
+        B, n, _ = img.shape
+        shared = obj.dim() == 2
+        if (obj.shape[0] if shared else obj.shape[1]) != n:
+            raise error("solvePnPTagConsensus: object/image point counts differ")
+        if pose is None:
+            pose = torch.zeros((B, 6), dtype=torch.float64, device=img.device)
+        assert pose.dtype == torch.float64 and pose.is_contiguous() and pose.shape == (B, 6)
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (B, n)
+        inl = torch.zeros((B, n), dtype=torch.uint8, device=img.device)
+        votes = torch.zeros((B, 4), dtype=torch.int32, device=img.device)
+        info = torch.zeros((B, 4), dtype=torch.int32, device=img.device)
+        err = torch.zeros((B,), dtype=torch.float64, device=img.device)
+        Kh, _ = _host_f64(K)
+        dh, nd = _host_f64(dist)
+        H.check(self.L.agt_solve_pnp_consensus(self.h, _ptr(obj), 0 if shared else n * 3, _ptr(img), H.F32 if obj.dtype == torch.float32 else H.F64,
+                                               _ptr(mask), n, B, Kh.ctypes.data_as(C.c_void_p), dh.ctypes.data_as(C.c_void_p) if nd else None, nd,
+                                               _ptr(pose), 1 if use_guess else 0, int(corners_per_tag), float(inlier_px), int(min_inliers),
+                                               _ptr(inl), _ptr(votes), _ptr(info), _ptr(err)), "agt_solve_pnp_consensus")
+        return pose, inl, votes, info, err
+
     def project_points(self, obj, pose, K, dist, jacobian=False):
         """obj cuda [n,3] or [B,n,3]; pose cuda f64 [B,6] -> (img [B,n,2] obj.dtype, jac [B,2n,6] f64|None)"""
         assert obj.is_cuda and obj.is_contiguous() and obj.dtype in (torch.float32, torch.float64)
@@ -561,3 +590,45 @@ def tagVisibility(objectPoints, rvec, tvec, cornersPerTag=4, maxViewDeg=90.0, fa
         except H.AgtError as e:
             raise error(str(e))
         return vis[0].cpu().numpy().astype(bool), cs[0].cpu().numpy()
+
+
+def solvePnPTagConsensus(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec=None, tvec=None, useExtrinsicGuess=False,
+                         cornersPerTag=4, reprojectionError=2.0, minInliers=8):
+    """Outlier-tolerant solvePnP for AprilGroups, in the place cv2.solvePnPRansac has -- but NOT its random sampling: the hypotheses are
+    deterministic, one per tag (objectPoints rows cornersPerTag * t .. are tag t, a complete planar pose problem).  Every tag is solved
+    alone (from rvec / tvec with useExtrinsicGuess), every corner votes on every tag's pose with the threshold reprojectionError (px),
+    the largest consensus wins (ties: smaller sum of squared residuals, then the lower tag) and the pose is the iterative solve on its
+    inliers, started from the winner (the rule: include/agt_hip.h agt_solve_pnp_consensus).
+    -> (ok, rvec (3,1), tvec (3,1), inliers (k,1) int32 indices, as cv2.solvePnPRansac returns them).  ok is False, with the guess (or
+    zeros) returned and no inliers, when no tag gathers minInliers votes.  The guess arrays are not written."""
+    obj = np.asarray(objectPoints); img = np.asarray(imagePoints)
+    obj = obj.reshape(-1, 3); img = img.reshape(-1, 2)
+    n, cpt = obj.shape[0], int(cornersPerTag)
+    if img.shape[0] != n or n == 0 or n > 256:
+        raise error("solvePnPTagConsensus: need 1 <= N <= 256 matching object/image points")
+    if cpt < 4 or n % cpt or n // cpt > 64:
+        raise error("solvePnPTagConsensus: %d points are not at most 64 whole tags of %d corners (>= 4)" % (n, cpt))
+    if not (np.isfinite(reprojectionError) and reprojectionError > 0) or int(minInliers) < cpt:
+        raise error("solvePnPTagConsensus: reprojectionError must be finite and > 0, minInliers >= cornersPerTag")
+    if useExtrinsicGuess and (rvec is None or tvec is None or np.size(rvec) != 3 or np.size(tvec) != 3):
+        raise error("solvePnPTagConsensus: useExtrinsicGuess needs 3-element rvec and tvec")
+    _require_gpu()
+    dt = np.float32 if (obj.dtype == np.float32 and img.dtype == np.float32) else np.float64
+    ctx = _geom_context(n)
+    with ctx.lock:
+        ctx.use_current_stream()
+        dev = torch.device("cuda", ctx.device)
+        p = np.zeros((1, 6), np.float64)
+        if useExtrinsicGuess:
+            p[0, :3] = np.asarray(rvec, np.float64).reshape(3); p[0, 3:] = np.asarray(tvec, np.float64).reshape(3)
+        try:
+            pose, inl, _, info, _ = ctx.solve_pnp_consensus(torch.from_numpy(np.ascontiguousarray(obj, dtype=dt)).to(dev),
+                                                            torch.from_numpy(np.ascontiguousarray(img, dtype=dt)).to(dev).reshape(1, n, 2),
+                                                            cameraMatrix, distCoeffs, torch.from_numpy(p).to(dev), bool(useExtrinsicGuess), None,
+                                                            cpt, float(reprojectionError), int(minInliers))
+        except H.AgtError as e:
+            raise error(str(e))
+        pose = pose.cpu().numpy()[0]
+        idx = np.flatnonzero(inl.cpu().numpy()[0]).astype(np.int32).reshape(-1, 1)
+        ok = bool(info.cpu().numpy()[0, H.INFO_OK])
+        return ok, pose[:3].reshape(3, 1).copy(), pose[3:].reshape(3, 1).copy(), idx

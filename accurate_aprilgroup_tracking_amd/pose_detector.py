@@ -42,12 +42,19 @@ class PoseDetector(TransformHelper):
     ERROR_GATE_PX = 2       # detect_pose.py:539
     DECISION_MARGIN = 50    # detect_pose.py:389
 
-    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None):
+    CONSENSUS_MIN = 8       # inliers a tag hypothesis needs to be elected (pnp_consensus_px): more than one tag's own four
+
+    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None, pnp_consensus_px=None):
         """`detector(gray) -> iterable of objects with .tag_id, .corners (4,2), .decision_margin`
         stands in for apriltag.Detector(...).detect (detect_pose.py:368-371).
         lk_fb_px: forward-backward check of the LK step (None / 0 = off): a tracked corner whose track back into the previous
         frame ends that many pixels (max norm) or more from where it started is dropped, and with it its tag.  backend
-        "stream" hands it to its StreamTracker (fb_check); backend "cv" tracks back with a second calcOpticalFlowPyrLK."""
+        "stream" hands it to its StreamTracker (fb_check); backend "cv" tracks back with a second calcOpticalFlowPyrLK.
+        pnp_consensus_px: tag consensus in front of the pose solve (None / 0 = off): every tag of the frame is solved alone, every
+        corner votes on every tag's pose with this reprojection threshold, and only the tags whose four corners all agree with the
+        winner go into _estimate_pose (tag_consensus below; the rule: include/agt_hip.h agt_solve_pnp_consensus).  It is NOT
+        ERROR_GATE_PX: that gate judges the mean error of the finished solve, this one a single corner under one tag's pose.
+        Backend "stream" hands it to its StreamTracker (consensus_px); backend "cv" does it on the host with the cv module."""
         TransformHelper.__init__(self, logger, mtx, dist, cv=cv)
         if backend not in ("cv", "stream"):
             raise ValueError("backend must be 'cv' or 'stream'")
@@ -55,6 +62,10 @@ class PoseDetector(TransformHelper):
             raise ValueError("lk_fb_px must be None or a finite threshold >= 0")
         self.backend = backend
         self.lk_fb_px = float(lk_fb_px) if lk_fb_px else None
+        if pnp_consensus_px is not None and not (np.isfinite(pnp_consensus_px) and pnp_consensus_px >= 0):
+            raise ValueError("pnp_consensus_px must be None or a finite threshold >= 0")
+        self.pnp_consensus_px = float(pnp_consensus_px) if pnp_consensus_px else None
+        self.last_consensus = None      # backend "cv": (winning tag's index in the frame's tag list, its inlier count) or None
         self._dev = None                # stream backend: _DeviceStream, created at the first frame (its size fixes the context)
         self.img = None
         self.draw_frame = None
@@ -115,7 +126,8 @@ class PoseDetector(TransformHelper):
         self.__dict__["_st_" + name] = value
 
     @classmethod
-    def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv", lk_fb_px=None):
+    def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv", lk_fb_px=None,
+                   pnp_consensus_px=None):
         """Build from the reference's on-disk files: `CameraParams.npz` (calibrate_camera.py:107-123) and,
         optionally, an `april_group.json` somewhere else than DIRPATH/JSON_FILE (detect_pose.py:54-55).
         `detector` may be a recorded-detections .npz (formats.ReplayDetector) to replay a session."""
@@ -125,10 +137,12 @@ class PoseDetector(TransformHelper):
         if isinstance(detector, (str, os.PathLike)):
             detector = formats.ReplayDetector(detector)
         if april_group is None:
-            return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px)
+            return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
+                       pnp_consensus_px=pnp_consensus_px)
         folder, name = os.path.split(os.fspath(april_group))
         sub = type(cls.__name__, (cls,), {"DIRPATH": folder or ".", "JSON_FILE": name})
-        return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px)
+        return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
+                   pnp_consensus_px=pnp_consensus_px)
 
     # ------------------------------------------------------------------ model (detect_pose.py:105-227)
     def get_extrinsics(self):
@@ -214,6 +228,21 @@ class PoseDetector(TransformHelper):
             return self._stream().estimate(self, imgpoints_arr, objpoints_arr)
         prev_snapshot = deepcopy(self.prev_transform)        # solvePnP overwrites aliased guess arrays
         self.last_pose, self.last_error = (None, None), None
+        if self.pnp_consensus_px and imgpoints_arr and objpoints_arr:
+            # tag consensus: the state machine below is unchanged, it sees the tags whose corners all agree with the elected pose
+            # (the device: mask = status AND inliers, then the tag gate); no consensus = no tag = the too-few path
+            obj = np.array(objpoints_arr, dtype=np.float32).reshape(-1, 3)
+            img = np.array(imgpoints_arr, dtype=np.float32).reshape(-1, 2)
+            guess = self.extrinsic_guess if (self.extrinsic_guess[0] is not None and self.enhance_ape) else None
+            inl, win, cnt, _ = tag_consensus(self.cv, obj, img, self.mtx, self.dist, guess=guess, corners_per_tag=4,
+                                             inlier_px=self.pnp_consensus_px, min_inliers=self.CONSENSUS_MIN)
+            self.last_consensus = (win, cnt)
+            # (the reference solves on whole tags: a tag with a dissenting corner leaves altogether, as under the device's tag gate)
+            keep = np.repeat(inl.reshape(-1, 4).all(axis=1), 4)
+            ends = np.cumsum([np.asarray(a).reshape(-1, 2).shape[0] for a in imgpoints_arr])
+            sel = [bool(keep[e - np.asarray(a).reshape(-1, 2).shape[0]:e].all()) for a, e in zip(imgpoints_arr, ends)]
+            imgpoints_arr = [a for a, k in zip(imgpoints_arr, sel) if k]
+            objpoints_arr = [a for a, k in zip(objpoints_arr, sel) if k]
         if not (imgpoints_arr and objpoints_arr and len(imgpoints_arr) >= self.MIN_TAGS):
             self.extrinsic_guess = (None, None)
             return
@@ -330,6 +359,50 @@ class PoseDetector(TransformHelper):
 
 
 
+def tag_consensus(cv, obj, img, mtx, dist, usable=None, guess=None, corners_per_tag=4, inlier_px=2.0, min_inliers=8):
+    """The tag-consensus rule (include/agt_hip.h agt_solve_pnp_consensus, steps 1 - 5) on the host, with the `cv` module's solvePnP /
+    projectPoints / Rodrigues: obj (n,3), img (n,2), tag t = rows corners_per_tag * t ..; usable (n,) bool or None; guess (rvec, tvec) or
+    None -- every hypothesis starts from a float64 COPY of it (solvePnP writes into its guess arrays).
+    -> (inliers (n,) bool, winning tag or -1, its inlier count or 0, the winner's (rvec, tvec) or None)."""
+    cpt = int(corners_per_tag)
+    n = obj.shape[0]
+    if cpt < 4 or n == 0 or n % cpt or min_inliers < cpt or not (np.isfinite(inlier_px) and inlier_px > 0):
+        raise ValueError("tag_consensus: whole tags of >= 4 corners, min_inliers >= corners_per_tag and a finite inlier_px > 0 are expected")
+    usable = np.ones(n, bool) if usable is None else np.asarray(usable).reshape(n) != 0
+    img64 = np.asarray(img, np.float64).reshape(n, 2)
+    obj64 = np.asarray(obj, np.float64).reshape(n, 3)
+    tau2 = float(inlier_px) * float(inlier_px)
+    best = (-1, -1, 0.0, None, None)
+    for t in range(n // cpt):
+        sl = slice(t * cpt, (t + 1) * cpt)
+        if not usable[sl].all():
+            continue
+        try:
+            if guess is not None:
+                ok, r, tv = cv.solvePnP(obj[sl], img[sl], mtx, dist, np.array(guess[0], np.float64).reshape(3, 1),
+                                        np.array(guess[1], np.float64).reshape(3, 1), True, flags=cv.SOLVEPNP_ITERATIVE)
+            else:
+                ok, r, tv = cv.solvePnP(obj[sl], img[sl], mtx, dist, flags=cv.SOLVEPNP_ITERATIVE)
+        except ValueError:          # (a solver that reports too few points / a singular system by raising)
+            continue
+        r = np.asarray(r, np.float64).reshape(3); tv = np.asarray(tv, np.float64).reshape(3)
+        if not ok or not (np.isfinite(r).all() and np.isfinite(tv).all()):
+            continue
+        proj, _ = cv.projectPoints(obj64, r.reshape(3, 1), tv.reshape(3, 1), mtx, dist)
+        d = np.asarray(proj, np.float64).reshape(n, 2) - img64
+        d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        R = np.asarray(cv.Rodrigues(r.reshape(3, 1))[0], np.float64).reshape(3, 3)
+        zc = obj64 @ R[2] + tv[2]
+        with np.errstate(invalid="ignore"):
+            inl = usable & (zc > 0.0) & (d2 < tau2)
+        cnt, ssq = int(inl.sum()), float(d2[inl].sum())
+        if best[0] < 0 or cnt > best[1] or (cnt == best[1] and ssq < best[2]):
+            best = (t, cnt, ssq, inl, (r.reshape(3, 1), tv.reshape(3, 1)))
+    if best[0] < 0 or best[1] < min_inliers:
+        return np.zeros(n, bool), -1, 0, None
+    return best[3], best[0], best[1], best[4]
+
+
 class _DeviceStream:
     """backend "stream" of PoseDetector: one stream of tracker.StreamTracker plus the pinned staging buffers of the three
     copies a frame costs (frame up, corner table up when the detector spoke, 128-byte record down)."""
@@ -370,7 +443,8 @@ class _DeviceStream:
             new_k, self.roi, gw, gh = None, (0, 0, w, h), w, h
         self.trk = StreamTracker(gw, gh, det.all_objpts, det.mtx, det.dist, n_streams=1, max_level=2, win=21,
                                  enhance_ape=det.enhance_ape, reproject=False, min_points=4 * det.MIN_TAGS,
-                                 gate_px=float(det.ERROR_GATE_PX), fb_check=det.lk_fb_px or 0.0)
+                                 gate_px=float(det.ERROR_GATE_PX), fb_check=det.lk_fb_px or 0.0,
+                                 consensus_px=det.pnp_consensus_px or 0.0, consensus_min=det.CONSENSUS_MIN)
         self.trk.tag_gate(4)
         self.trk.pipeline(1)
         self.trk.reset()

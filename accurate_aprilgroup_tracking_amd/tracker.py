@@ -24,7 +24,8 @@ class TrackState(C.Structure):
 
 class StreamTracker:
     def __init__(self, width, height, obj_points, K, dist=None, n_streams=1, max_level=2, win=21,
-                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0, view_deg=0.0, facing=1):
+                 enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0, view_deg=0.0, facing=1,
+                 consensus_px=0.0, consensus_min=8):
         if view_deg and not reproject:
             # (the rule acts inside the reproject refresh only: accepting it here would be a silent no-op)
             raise ValueError("StreamTracker: view_deg needs reproject=True (the visibility rule acts in the corner refresh)")
@@ -46,6 +47,8 @@ class StreamTracker:
             self.fb_check(fb_check)
         if view_deg:
             self.visibility(view_deg, 4, facing)
+        if consensus_px:
+            self.consensus(consensus_px, 4, consensus_min)
         self._alive = []            # frames aliased by pyramid level 0 of the ring entries in flight
         self._keep_frames = max((max_level + 6) + 2, 12)
 
@@ -110,6 +113,16 @@ class StreamTracker:
         if view_deg and not self.reproject:
             raise ValueError("StreamTracker.visibility: view_deg needs reproject=True (the visibility rule acts in the corner refresh)")
         H.check(self.ctx.L.agt_tracker_visibility(self.ctx.h, int(corners_per_tag), float(view_deg), int(facing)), "agt_tracker_visibility")
+
+    def consensus(self, inlier_px, corners_per_tag=4, min_inliers=8):
+        """Tag consensus in front of the pose step (agt_tracker_consensus): every frame, each tag whose corners are all usable is solved
+        alone (from the stream's guess when it has one), every usable corner votes on every tag's pose with the threshold inlier_px,
+        and the pose step runs on status AND the winner's inliers -- a whole tag that slid consistently is outvoted by the others.  Per
+        frame, not sticky: the status bytes are not rewritten; the record's ST_NINLIER slot carries the winning count, a frame whose
+        best count is below min_inliers takes the too-few path.  inlier_px is not gate_px: the gate judges the mean error of the
+        finished solve.  0 switches it off (the default).  While it is on, step() runs stage by stage whatever the pipeline depth,
+        with two more launches per frame; step_dense() is refused.  May be changed mid-stream; joins the pipeline."""
+        H.check(self.ctx.L.agt_tracker_consensus(self.ctx.h, int(corners_per_tag), float(inlier_px), int(min_inliers)), "agt_tracker_consensus")
 
     def rewind(self):
         """Take the newest frame back as the tracking source: the next step() tracks from the frame before it (the reference

@@ -81,6 +81,8 @@ extern "C" {
 #define AGT_ST_TVEC_F32 12  /* 1.0 = tvec carries float32 precision (cv2 wrote it into the f32 guess array) */
 #define AGT_ST_NVISIBLE 13  /* tags visible under the frame's accepted pose (agt_tracker_visibility); 0.0 while the rule is off, without the
                                reproject option, or when the pose was not accepted */
+#define AGT_ST_NINLIER 14   /* inliers of the frame's winning tag hypothesis (agt_tracker_consensus); 0.0 while the option is off or when the
+                               frame had no consensus */
 #define AGT_TRK_ZERO_VELOCITY 256  /* a velocity element was exactly 0: reference raises ValueError (detect_pose.py:236-237) */
 #define AGT_TRK_CHAIN_TIMEOUT 512  /* pipelined tracker: the pose solve gave up waiting for the frame's corners (or did so for an earlier frame of
                                       the stream): nothing was solved, the record is invalid, the stream's state is frozen until agt_tracker_reset */
@@ -185,6 +187,33 @@ int agt_solve_pnp(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, cons
                   const double* K, const double* dist, int ndist,
                   double* d_pose, int use_guess, int32_t* d_info, double* d_err);
 
+/* ---- tag-consensus solvePnP: per-tag pose votes drop outlier TAGS before the solve ---- */
+/* The place cv2.solvePnPRansac has in a cv2 pipeline, without its random minimal sets: on an AprilGroup every tag is four coplanar
+ * corners, a complete minimal pose problem, so the hypotheses are deterministic -- one per tag.  Arguments as agt_solve_pnp, and with
+ * cpt = corners_per_tag, T = n / cpt (tag t = points cpt * t ..), per stream b, in FP64:
+ *   1. corner i is usable when d_mask is NULL or d_mask[b][i] != 0; tag t is a candidate when all its cpt corners are usable
+ *   2. the hypothesis of a candidate tag is what agt_solve_pnp returns for that tag's cpt points alone (same camera and dtype; with
+ *      use_guess from d_pose[b], without through the planar initialisation); it is discarded when its info flags carry
+ *      AGT_PNP_SINGULAR or AGT_PNP_TOO_FEW or one of its six pose numbers is not finite
+ *   3. every usable corner i votes on every hypothesis t: (u, v) = projectPoints, d2 = (u - x_i)^2 + (v - y_i)^2 (image point promoted
+ *      to double), Zc = (R X_i + t).z; inlier <=> Zc > 0 and d2 < inlier_px^2 (false for NaN).  count_t = inliers, ssq_t = sum of their d2
+ *   4. the winner has the largest count_t; a tie goes to the smaller ssq_t, a remaining tie to the lower t
+ *   5. no hypothesis, or a winning count below min_inliers: every inlier byte of the stream is 0, d_pose[b] is untouched, d_info[b]
+ *      reports AGT_INFO_OK = 0 with AGT_PNP_TOO_FEW (and d_err[b] = 0)
+ *   6. otherwise d_inliers[b] is the winner's inlier set and the pose is agt_solve_pnp(mask = d_inliers, use_guess = 1) started from
+ *      the winner's pose; d_info / d_err are that solve's.  One refit, no re-vote.
+ * d_inliers: [B][n] u8, required.  d_votes: [B][4] i32 or NULL: winning tag (-1: none), its inlier count (0: none), candidate tags,
+ * accepted hypotheses.  inlier_px is a knob of its own: the tracker's reprojection gate (agt_tracker_options gate_px) judges the MEAN
+ * error of the finished solve, inlier_px one corner under one tag's pose.  Keep min_inliers above cpt: a lone tag always agrees with
+ * itself.  Three launches on the context's stream (B * T tag solves side by side; vote and election, one workgroup per stream; the
+ * refit), no host round trip in between; does not synchronise.  AGT_ERR_ARG: inlier_px not finite or <= 0, corners_per_tag < 4, n no
+ * multiple of it, min_inliers < corners_per_tag, d_inliers NULL.  AGT_ERR_NPOINTS: T > 64 or n > 256.  Present from ABI 505 on: look
+ * the symbol up. */
+int agt_solve_pnp_consensus(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
+                            const uint8_t* d_mask, int n, int B, const double* K, const double* dist, int ndist,
+                            double* d_pose, int use_guess, int corners_per_tag, double inlier_px, int min_inliers,
+                            uint8_t* d_inliers, int32_t* d_votes, int32_t* d_info, double* d_err);
+
 /* ---- cv::projectPoints, batched ---- */
 /* d_pose: [B][6] f64.  d_img_out: [B][n][2] in dtype.  d_jac: [B][2n][6] f64 (d/dr | d/dt) or NULL. */
 int agt_project_points(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
@@ -279,6 +308,22 @@ int agt_tracker_fb_check(agt_ctx* ctx, double fb_max_px);
  * has been reset and max_view_deg > 0 -- a corner count that is no multiple of corners_per_tag; a later agt_tracker_reset with such a count returns
  * AGT_ERR_ARG as well while the rule is on.  Present from ABI 505 on: look the symbol up. */
 int agt_tracker_visibility(agt_ctx* ctx, int corners_per_tag, double max_view_deg, int facing);
+/* Tag consensus in front of the tracker's pose step (inlier_px = 0: off, the default).  A whole tag can slide consistently -- onto a
+ * neighbouring tag, a reflection, an occluder -- track back fine and enter the solve with status 1; neither agt_tracker_fb_check nor
+ * agt_tracker_visibility sees it.  With the option on, every frame of agt_track_frame, agt_track_frames, agt_track_host_frame,
+ * agt_track_frame_detected and agt_estimate_pose first computes the consensus inlier set (steps 1 - 5 of agt_solve_pnp_consensus)
+ * of the corners that would go into the solve: mask = the frame's LK status (after the forward-backward check) or the supplied mask;
+ * the hypotheses start from the stream's extrinsic guess when it has one and enhance_ape is set, otherwise without a guess.  The pose
+ * step then runs unchanged with mask = status AND inliers: the gate, the motion model, prev_transform, the tag gate, min_points, the
+ * reproject refresh and the visibility rule are the existing code on a smaller mask, and a frame without consensus takes the existing
+ * too-few path.  The exclusion is per frame, not sticky: the tracker's status bytes are not rewritten, AGT_ST_NTRACK counts the
+ * corners the solve used, AGT_ST_NINLIER carries the winning count.  inlier_px and the gate (agt_tracker_options gate_px) are separate
+ * knobs.  While it is on, frames run stage by stage whatever the pipeline depth (as under fb_check / reproject), with two more launches
+ * per frame, and agt_track_frame_dense / agt_track_frames_dense return AGT_ERR_UNSUPPORTED.  Joins the pipeline.  AGT_ERR_ARG:
+ * inlier_px not finite or < 0, corners_per_tag < 4 or > 64, min_inliers < corners_per_tag, or -- once the tracker has been reset and
+ * inlier_px > 0 -- a corner count that is no multiple of corners_per_tag or makes more than 64 tags; a later agt_tracker_reset with
+ * such a count returns AGT_ERR_ARG as well while the option is on.  Present from ABI 505 on: look the symbol up. */
+int agt_tracker_consensus(agt_ctx* ctx, int corners_per_tag, double inlier_px, int min_inliers);
 /* Software pipelining across frames.  depth 0: separate launches per stage, the record of frame t is complete
  * in stream order after its call.  depth F in 1..32 (default 1; needs reproject == 0, otherwise the call falls back to
  * depth 0 behaviour): agt_track_frame registers the frame and, every F calls, issues ONE fused launch that advances every
