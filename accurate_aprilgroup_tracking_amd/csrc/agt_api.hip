@@ -340,6 +340,7 @@ int agt_destroy(agt_ctx* c)
     if (c->fault_host) (void)hipHostFree(c->fault_host);
     if (c->dense_partials) (void)hipFree(c->dense_partials);
     if (c->cons_buf) (void)hipFree(c->cons_buf);
+    if (c->pred_hist) (void)hipFree(c->pred_hist);
     if (c->dense_done) (void)hipFree(c->dense_done);
     if (c->d_tilt) (void)hipFree(c->d_tilt);
     if (c->hcall_host) (void)hipHostFree(c->hcall_host);

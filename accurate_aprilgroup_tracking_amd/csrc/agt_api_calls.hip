@@ -178,6 +178,27 @@ int agt_tag_visibility(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, i
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
+// the seed rule of agt_tracker_predict for B pairs of poses: project_kernel in its flow mode (agt_pnp.hip), one workgroup per stream
+int agt_predict_flow(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
+                     const double* d_pose_older, const double* d_pose_newer, const double* K, const double* dist, int ndist,
+                     const float* d_prev_pts, const uint8_t* d_mask, double max_flow_px,
+                     float* d_seed_pts, float* d_flow, float* d_flow_max, double* d_pose_pred)
+{
+    if (!c || !d_obj || !d_pose_older || !d_pose_newer || !d_prev_pts || !d_seed_pts || n <= 0 || B <= 0) return AGT_ERR_ARG;
+    if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
+    if (!(max_flow_px > 0.0) || !(max_flow_px <= 1.7976931348623157e308)) return AGT_ERR_ARG;       // (NaN fails both)
+    if (n > 256) return AGT_ERR_NPOINTS;
+    AgtProjParams p;
+    memset(&p, 0, sizeof(p));
+    int rc = camera_on(c, K, dist, ndist, &p.cam);
+    if (rc) return rc;
+    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n;
+    p.flow_older = d_pose_older; p.flow_newer = d_pose_newer; p.flow_pstride = 6; p.flow_prev = d_prev_pts; p.flow_mask = d_mask;
+    p.flow_seed = d_seed_pts; p.flow_out = d_flow; p.flow_max = d_flow_max; p.flow_pred = d_pose_pred; p.flow_cap = (float)max_flow_px;
+    hipError_t e = agt_launch_project(c->stream, p, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
 // ---- tag consensus (the rule: include/agt_hip.h agt_solve_pnp_consensus).  Three launches on one stream, nothing in between:
 //   1. the solver kernels over B * T problems of cpt points (hypothesis launch, agt_kernels.h AgtPnpParams::hyp_T)
 //   2. project_kernel in vote mode, one workgroup per stream: inlier bytes, votes, the winner's pose

@@ -128,10 +128,11 @@ static int fill_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int next_slo
 }
 
 // the tracker's own LK from the frame in ring entry prev_slot to the one in `slot`: their corner / status entries, the tracker's criteria
-static void fill_tracker_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int slot)
+// (flags: AGT_LK_USE_INITIAL_FLOW when the frame's corner entry holds the seeds of agt_tracker_predict, else 0)
+static void fill_tracker_lk(const agt_ctx* c, AgtLkParams* p, int prev_slot, int slot, int flags = 0)
 {
     fill_lk(c, p, prev_slot, slot, c->corners[prev_slot], c->status[prev_slot], c->corners[slot], c->status[slot], nullptr, c->trk_n,
-            AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig);
+            AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, flags, c->lk_min_eig);
 }
 
 // image k of an LK group per level (k = 0: frame f0, the one before the group) and the corner / status entries of frames f0 + 1 .. f0 + count
@@ -189,34 +190,91 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
 // kept (d_status is its prev_status), in verdict mode (agt_kernels.h AgtLkVerdict): it writes no point and no err -- d_err only says
 // whether the pass measures one, as the forward pass did, since measuring can drop a corner whose final window left the image -- clears
 // the status byte of a corner that does not come home within fb_max_px of d_prev_pts, and files the distances in d_fb_dist (or null).
+// d_back_seed (agt_tracker_predict; null otherwise): [B][n][2] points the pass starts its search at instead, as an initial flow.
 int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                   const float* d_prev_pts, const float* d_next_pts, uint8_t* d_status, const float* d_err, float* d_fb_dist,
                   int n, int B, int crit_type, int crit_max_count, double crit_eps,
-                  int flags, double min_eig_threshold, double fb_max_px)
+                  int flags, double min_eig_threshold, double fb_max_px, const float* d_back_seed)
 {
     if (!c || !d_prev_pts || !d_next_pts || !d_status || n < 0 || B <= 0) return AGT_ERR_ARG;
     if (n == 0) return AGT_OK;
     AgtLkParams p;
-    fill_lk(c, &p, next_slot, prev_slot, d_next_pts, d_status, const_cast<float*>(d_next_pts), d_status, const_cast<float*>(d_err), n,
-            crit_type, crit_max_count, crit_eps, flags & 0xffff & ~AGT_LK_USE_INITIAL_FLOW, min_eig_threshold);
+    // (a verdict launch writes no point: next_pts is only ever read, and only under the initial-flow flag)
+    fill_lk(c, &p, next_slot, prev_slot, d_next_pts, d_status, const_cast<float*>(d_back_seed ? d_back_seed : d_next_pts), d_status,
+            const_cast<float*>(d_err), n, crit_type, crit_max_count, crit_eps,
+            (flags & 0xffff & ~AGT_LK_USE_INITIAL_FLOW) | (d_back_seed ? AGT_LK_USE_INITIAL_FLOW : 0), min_eig_threshold);
     p.fb.orig = d_prev_pts; p.fb.dist = d_fb_dist; p.fb.max_px = (float)fb_max_px;
     return lk_launch_on(c, stream, p, next_slot, prev_slot, B, 0, 0);
 }
 
 // the tracker's LK launch of streams b0 .. b0 + B - 1 between two of its ring entries (B >= 1 and trk_n >= 4 by agt_tracker_reset)
-static int track_lk_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B, int b0 = 0, int waves = 0)
+static int track_lk_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B, int b0 = 0, int waves = 0, int flags = 0)
 {
     AgtLkParams p;
-    fill_tracker_lk(c, &p, prev_slot, slot);
+    fill_tracker_lk(c, &p, prev_slot, slot, flags);
     return lk_launch_on(c, stream, p, prev_slot, slot, B, b0, waves);
 }
 
 // agt_tracker_fb_check: the verdict launch behind the tracker's LK launch prev_slot -> slot.  A dropped corner is a corner LK lost in
 // this frame: status 0 from here on (sticky), the forward position kept in its entry and carried.
+// Under agt_tracker_predict the backward pass starts at arrival - flow (one more small launch writes those points): started at the
+// arrival it would fail for the reason the unseeded forward pass does.
 static int track_fb_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B)
 {
+    const float* back = nullptr;
+    if (c->pred_px > 0.0) {
+        AgtProjParams q;
+        memset(&q, 0, sizeof(q));
+        q.n = c->trk_n; q.flow_prev = c->corners[slot]; q.flow_out = c->pred_flow; q.flow_back = c->pred_back;
+        hipError_t e = agt_launch_project(stream, q, B);
+        if (e != hipSuccess) return hip_fail(c, e);
+        back = c->pred_back;
+    }
     return lk_verdict_on(c, stream, prev_slot, slot, c->corners[prev_slot], c->corners[slot], c->status[slot], nullptr, nullptr, c->trk_n, B,
-                         AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, c->fb_max_px);
+                         AGT_TERM_COUNT | AGT_TERM_EPS, c->lk_max_count, c->lk_eps, 0, c->lk_min_eig, c->fb_max_px, back);
+}
+
+// ---- agt_tracker_predict (semantics: include/agt_hip.h; device side: agt_pnp.hip flow_stream, the history block: agt_kernels.h AGT_PRED_*).
+// Every record-producing pose launch is preceded by ONE launch of project_kernel in flow mode, which predicts from the stream's two
+// newest records, advances the history and leaves the frame's flow word for the pose launch.
+static int pred_clear(agt_ctx* c)
+{
+    if (!c->pred_hist) return AGT_OK;
+    hipError_t e = hipMemsetAsync(c->pred_hist, 0, (size_t)c->cfg.max_streams * AGT_PRED_STRIDE * sizeof(double), c->stream);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+// prev_slot >= 0: in front of the LK launch prev_slot -> slot -- seeds into the frame's corner entry (mask: the previous frame's LK status),
+// flows into the context's scratch.  prev_slot < 0: a frame without an LK step -- the history moves on, the flow word is 0.
+static int track_seed_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B)
+{
+    AgtProjParams q;
+    memset(&q, 0, sizeof(q));
+    q.flow_hist = c->pred_hist; q.flow_cap = (float)c->pred_px;
+    if (prev_slot >= 0) {
+        q.obj = c->obj; q.obj_bstride = 0; q.dtype = AGT_F32; q.n = c->trk_n; q.cam = c->cam;
+        q.flow_prev = c->corners[prev_slot]; q.flow_mask = c->status[prev_slot]; q.flow_seed = c->corners[slot]; q.flow_out = c->pred_flow;
+    }
+    hipError_t e = agt_launch_project(stream, q, B);
+    return e == hipSuccess ? AGT_OK : hip_fail(c, e);
+}
+
+int agt_tracker_predict(agt_ctx* c, double max_flow_px)
+{
+    if (!c || !(max_flow_px >= 0.0) || !(max_flow_px <= 1.7976931348623157e308)) return AGT_ERR_ARG;       // (NaN fails both)
+    int rc = join_pipeline(c);
+    if (rc) return rc;
+    if (max_flow_px > 0.0 && !c->pred_hist) {
+        const size_t B = (size_t)c->cfg.max_streams, N = (size_t)c->cfg.max_points;
+        const size_t o_flow = B * AGT_PRED_STRIDE * sizeof(double), o_back = o_flow + B * N * 2 * sizeof(float);
+        char* buf = nullptr;
+        if (hipMalloc((void**)&buf, o_back + B * N * 2 * sizeof(float)) != hipSuccess) { hip_fail(c, hipGetLastError()); return AGT_ERR_ALLOC; }
+        c->pred_hist = (double*)buf; c->pred_flow = (float*)(buf + o_flow); c->pred_back = (float*)(buf + o_back);
+    }
+    rc = pred_clear(c);
+    if (rc) return rc;
+    c->pred_px = max_flow_px;
+    return AGT_OK;
 }
 
 int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float* d_obj, int n, int B,
@@ -254,6 +312,8 @@ int agt_tracker_reset(agt_ctx* c, int slot, const float* d_corners, const float*
     if (e == hipSuccess) e = hipMemsetAsync(c->lk_done, 0, (size_t)AGT_RING_MAX * c->cfg.max_streams * sizeof(unsigned), c->stream);
     memset(c->lk_target, 0, sizeof(c->lk_target));
     if (e != hipSuccess) return hip_fail(c, e);
+    rc = pred_clear(c);                      // (agt_tracker_predict: a new run has no pose history)
+    if (rc) return rc;
     c->prebuilt_t = -1;
     c->hseq_off = c->hseq_last + 1;          // (sequence numbers of agt_track_host_frame stay monotonic across runs)
     c->trk_n = n; c->trk_B = B; c->enhance_ape = enhance_ape ? 1 : 0;
@@ -400,6 +460,7 @@ static void fill_estimate(const agt_ctx* c, AgtPnpParams* p, const float* d_img,
     p->enhance_ape = c->enhance_ape; p->reproject = c->reproject; p->min_points = c->min_points; p->gate_px = c->gate_px;
     p->tag_gate = c->tag_gate; p->fault = c->fault_dev;
     if (c->vis_deg > 0.0) { p->vis_cpt = c->vis_cpt; p->vis_cos_max = c->vis_cos_max; p->vis_facing = c->vis_facing; }
+    if (c->pred_px > 0.0) p->pred_hist = c->pred_hist;
 }
 
 // the solver of the launch's first frame `frame` (tracker frame index) reports to the polling host thread (agt_track_host_frame)
@@ -874,6 +935,7 @@ int agt_estimate_pose(agt_ctx* c, const float* d_img, const uint8_t* d_mask, int
     if (rc) return rc;
     AgtPnpParams p;
     fill_estimate(c, &p, d_img, d_mask, d_state_out, nullptr);
+    if (c->pred_px > 0.0 && (rc = track_seed_on(c, c->stream, -1, 0, B))) return rc;
     if (c->cons_px > 0.0 && (rc = tracker_consensus_on(c, c->stream, &p, B))) return rc;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
@@ -904,7 +966,8 @@ static SerialForm serial_form(const agt_ctx* c, int pslot, int slot, int nslot, 
     const bool wide = c->cfg.win == 21 && agt_lk_wide(c->trk_n, B);
     // (forward-backward check on: the stand-alone LK launch, which the verdict launch follows -- not the LK role, not the chained or
     // the deferring forms that build on it)
-    const bool fb = c->fb_max_px > 0.0 || c->cons_px > 0.0;      // (tag consensus: the same -- its launches go between LK and the pose launch)
+    // (tag consensus: the same -- its launches go between LK and the pose launch; agt_tracker_predict: the chain body of the LK role takes no initial flow)
+    const bool fb = c->fb_max_px > 0.0 || c->cons_px > 0.0 || c->pred_px > 0.0;
     f.lk_role_launch = wide && !fb && c->l0_pitch[pslot] == (long)pitch && c->l0_bstride[pslot] == (long)batch_stride;
     // Clip submission: the next frame's two-level pyramid pass rides in one of this frame's launches -- the PnP launch where that
     // is the four-wave kernel (n > 64: one workgroup per stream, the chip idles beside it), else the dense stage's second launch.
@@ -1015,7 +1078,9 @@ static int step_serial(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t
             hipError_t e = agt_launch_dense_final(M, c->dense_final, B);
             if (e != hipSuccess) return hip_fail(c, e);
         }
-        rc = track_lk_on(c, M, pslot, slot, B);
+        const bool pred = c->pred_px > 0.0;
+        if (pred && (rc = track_seed_on(c, M, pslot, slot, B))) return rc;
+        rc = track_lk_on(c, M, pslot, slot, B, 0, 0, pred ? AGT_LK_USE_INITIAL_FLOW : 0);
         if (rc == AGT_OK && c->fb_max_px > 0.0) rc = track_fb_on(c, M, pslot, slot, B);
     }
     if (rc) return rc;
@@ -1044,7 +1109,7 @@ int agt_track_frame(agt_ctx* c, const uint8_t* d_frames, size_t pitch, size_t ba
     hipEvent_t* pev = profile_events(c);
     // the fused launch pays off while the stages are latency-bound (few streams); the biggest batches fill
     // the chip per stage and run faster as separate launches with their own register budgets
-    if (c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && (agt_step_fits(c->trk_n, B) || !pev)) {
+    if (c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && !(c->pred_px > 0.0) && (agt_step_fits(c->trk_n, B) || !pev)) {
         // fused launch: the three spans collapse into one (span 2 = the whole step_kernel launch)
         if (pev) { (void)hipEventRecord(pev[0], c->stream); (void)hipEventRecord(pev[1], c->stream); (void)hipEventRecord(pev[2], c->stream); }
         int rc = step_pipelined(c, d_frames, pitch, batch_stride, B, d_state_out);
@@ -1087,6 +1152,7 @@ int agt_track_frame_detected(agt_ctx* c, const uint8_t* d_frames, size_t pitch, 
     AgtPnpParams p;
     fill_estimate(c, &p, d_corners, d_mask, d_state_out, c->corners[slot], c->status[slot]);
     p.seed_pts = c->corners[slot]; p.seed_status = c->status[slot];
+    if (c->pred_px > 0.0 && (rc = track_seed_on(c, c->stream, -1, 0, B))) return rc;
     if (c->cons_px > 0.0 && (rc = tracker_consensus_on(c, c->stream, &p, B))) return rc;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     if (e != hipSuccess) return hip_fail(c, e);
@@ -1152,7 +1218,7 @@ int agt_track_host_frame(agt_ctx* c, const uint8_t* h_frame, int channels, int s
         // level 0 to d_gray on the way (step_pipelined_uploaded) -- one launch instead of a copy-engine transfer (19 us + ~8 us of
         // submission and hand-over) and a pyramid launch (6 us).  Pageable memory, frame sizes the rolling pass does not take, the
         // stage-by-stage mode and pending pyramid work of earlier frames keep the copy.
-        if (h_dev && polled && c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && agt_step_fits(c->trk_n, 1)) {
+        if (h_dev && polled && c->pipeline && !c->reproject && !(c->fb_max_px > 0.0) && !(c->cons_px > 0.0) && !(c->pred_px > 0.0) && agt_step_fits(c->trk_n, 1)) {
             int rcu = step_pipelined_uploaded(c, h_dev, d_gray, gpitch, d_rec);
             if (rcu < 0) return rcu;
             registered = rcu == AGT_OK;
@@ -1269,6 +1335,7 @@ int agt_track_frame_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, siz
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
     if (c->cons_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor do they leave room for the consensus launches: agt_tracker_consensus)
+    if (c->pred_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does their LK role take an initial flow: agt_tracker_predict)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;
@@ -1286,6 +1353,7 @@ int agt_track_frames_dense(agt_ctx* c, const uint8_t* d_frames, size_t pitch, si
     if (c->fb_max_px > 0.0) return AGT_ERR_UNSUPPORTED;      // (the dense stage's launch forms carry no backward pass: agt_tracker_fb_check)
     if (c->vis_deg > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does its re-seed carry the visibility rule: agt_tracker_visibility)
     if (c->cons_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor do they leave room for the consensus launches: agt_tracker_consensus)
+    if (c->pred_px > 0.0) return AGT_ERR_UNSUPPORTED;        // (nor does their LK role take an initial flow: agt_tracker_predict)
     if (c->trk_ready != 2 || c->dn_M <= 0) return AGT_ERR_STATE;
     if (B <= 0 || B != c->trk_B) return AGT_ERR_ARG;
     if (!frame_args_ok(c, d_frames, pitch, batch_stride)) return AGT_ERR_ARG;

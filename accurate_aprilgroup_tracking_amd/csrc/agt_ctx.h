@@ -94,6 +94,10 @@ struct agt_ctx {
     double vis_deg, vis_cos_max; int vis_cpt, vis_facing;
     // agt_tracker_consensus: per-frame tag consensus in front of the pose step (cons_px = 0: off; on: stage-by-stage frames)
     double cons_px; int cons_cpt, cons_min;
+    // agt_tracker_predict: motion-predicted initial flow of the tracker's LK step (pred_px = 0: off; on: stage-by-stage frames).  One
+    // allocation made when the option is first switched on: the per-stream pose history (AGT_PRED_* of agt_kernels.h), the frame's flows and
+    // the start points of the backward pass of the forward-backward check
+    double pred_px; double* pred_hist; float* pred_flow; float* pred_back;
     char* cons_buf; size_t cons_cap;         // scratch of the consensus calls (cons_scratch): hypotheses, and the tracker's inlier bytes / votes
     int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
     // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
@@ -138,7 +142,7 @@ int lk_track_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
 int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                   const float* d_prev_pts, const float* d_next_pts, uint8_t* d_status, const float* d_err, float* d_fb_dist,
                   int n, int B, int crit_type, int crit_max_count, double crit_eps,
-                  int flags, double min_eig_threshold, double fb_max_px);
+                  int flags, double min_eig_threshold, double fb_max_px, const float* d_back_seed = nullptr);
 int lk_lds_min(int per_cu);
 // Scratch of one consensus call over B streams of T tags (agt_api_calls.hip): grown when too small, never shrunk
 struct ConsScratch { double* hyp_pose; int32_t* hyp_info; double* win; uint8_t* inl; int32_t* votes; };

@@ -156,7 +156,18 @@ struct AgtPnpParams {
     // carries cons_votes[b][1].  Both null: off.
     const uint8_t* cons_inl;                 // [B][n]
     const int32_t* cons_votes;               // [B][4]
+    // agt_tracker_predict (null: off): the stream's block of the pose history, AGT_PRED_STRIDE doubles (layout below).  The pose step files
+    // the pose and the verdict of EVERY record it writes in the block's `last` entry and copies the flow word into the record's AGT_ST_FLOW
+    // slot; read by the launches of agt_pnp.hip alone (template flag CONS)
+    double* pred_hist;                       // [B][AGT_PRED_STRIDE]
 };
+// Pose history of agt_tracker_predict, per stream: the record the pose step wrote last (pose, accepted), the flow word of the frame (the seed
+// launch's flow_max, handed to the pose launch), and the record before that one.  The seed launch of project_kernel (flow mode) predicts
+// from the two entries while both are accepted, then moves `last` to `before` and clears `last`.
+#define AGT_PRED_STRIDE 16
+#define AGT_PRED_LAST   0     // 0..5 pose, 6 accepted (1.0 / 0.0)
+#define AGT_PRED_FLOW   7
+#define AGT_PRED_BEFORE 8     // 8..13 pose, 14 accepted
 
 // device-resident per-stream tracker state: the attributes of PoseDetector
 // (detect_pose.py:74-83) that _estimate_pose mutates
@@ -250,6 +261,28 @@ struct AgtProjParams {
     double* vote_win;         // [B][6]
     double vote_tau2;         // inlier_px^2
     int vote_cpt, vote_min;
+    // flow mode (agt_predict_flow, agt_tracker_predict; flow_seed or flow_hist != null): ONE workgroup per stream, thread i owns corner i
+    // (n <= 256).  The constant-velocity extrapolation of the poses flow_older[b] -> flow_newer[b] (stride flow_pstride doubles) is computed
+    // once per workgroup, every usable corner is projected under the newer and the predicted pose, the workgroup decides whether the
+    // prediction is trusted and writes seeds, flows, flow_max and the predicted pose (the rule: include/agt_hip.h).  flow_hist != null: the
+    // tracker's form -- the poses are the two entries of the stream's history block (AGT_PRED_*), a stream whose entries are not both
+    // accepted has no prediction (seeds = flow_prev, flow_max 0), and the block is advanced for the frame's pose step.  n = 0 with
+    // flow_seed null: only that.  img_out, jac and pose are not read.
+    const double* flow_older; // [B][6]
+    const double* flow_newer;
+    long flow_pstride;
+    const float* flow_prev;   // [B][n][2]
+    const uint8_t* flow_mask; // [B][n] or null
+    float* flow_seed;         // [B][n][2]
+    float* flow_out;          // [B][n][2] or null
+    float* flow_max;          // [B] or null
+    double* flow_pred;        // [B][6] or null
+    double* flow_hist;        // [B][AGT_PRED_STRIDE] or null
+    // back-seed mode (flow_back != null; the tracker's forward-backward check under agt_tracker_predict): thread i of stream b's blocks
+    // writes flow_back[b][i] = flow_prev[b][i] - flow_out[b][i] (float32), where the backward LK pass starts; nothing else is read
+    float* flow_back;         // [B][n][2]
+    float flow_cap;           // (float)max_flow_px
+    int flow_pad_;
 };
 
 // The dense stage's parameter block (agt_dense.hip: specification, mapping; agt_dense_body.h: the update).  The caller fills frame, model,

@@ -630,6 +630,7 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                     for (int i = 0; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
                     so[AGT_ST_NTRACK] = n_used; so[AGT_ST_FLAGS] = AGT_PNP_TOO_FEW | flags;
                     if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
+                    if constexpr (CONS) { if (P.pred_hist) so[AGT_ST_FLOW] = P.pred_hist[(long)b * AGT_PRED_STRIDE + AGT_PRED_FLOW]; }
                 }
             }
             return;
@@ -957,6 +958,7 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                     for (int i = 0; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
                     so[AGT_ST_NTRACK] = n_used; so[AGT_ST_FLAGS] = AGT_PNP_TOO_FEW | flags;
                     if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
+                    if constexpr (CONS) { if (P.pred_hist) so[AGT_ST_FLOW] = P.pred_hist[(long)b * AGT_PRED_STRIDE + AGT_PRED_FLOW]; }
                 }
             }
             return;
@@ -1247,6 +1249,16 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                 so[AGT_ST_TVEC_F32] = tvec_f32 ? 1.0 : 0.0;
                 for (int i = AGT_ST_TVEC_F32 + 1; i < AGT_STATE_STRIDE; i++) so[i] = 0.0;
                 if constexpr (CONS) { if (P.cons_votes) so[AGT_ST_NINLIER] = (double)P.cons_votes[b * 4 + 1]; }
+                if constexpr (CONS) { if (P.pred_hist) so[AGT_ST_FLOW] = P.pred_hist[(long)b * AGT_PRED_STRIDE + AGT_PRED_FLOW]; }
+            }
+            if constexpr (CONS) {
+                // agt_tracker_predict: the record's pose and verdict go into the stream's history (a record that ends on one of the
+                // too-few paths leaves the entry as the seed launch cleared it: not accepted)
+                if (P.pred_hist) {
+                    double* h = P.pred_hist + (long)b * AGT_PRED_STRIDE + AGT_PRED_LAST;
+                    for (int i = 0; i < 6; i++) h[i] = param[i];
+                    h[6] = accepted ? 1.0 : 0.0;
+                }
             }
         }
         if (accepted && P.reproject && P.corners_rw) {

@@ -343,6 +343,35 @@ class Context:
                                           _ptr(pose), cpt, float(max_view_deg), int(facing), _ptr(vis), _ptr(cs)), "agt_tag_visibility")
         return vis, cs
 
+    def predict_flow(self, obj, pose_older, pose_newer, K, dist, prev_pts, mask=None, max_flow_px=64.0):
+        """Motion-predicted LK seeds (agt_predict_flow; the rule: include/agt_hip.h): obj cuda [n,3] (shared) or [B,n,3], f32 or f64;
+        pose_older / pose_newer cuda f64 [B,6], the poses of two consecutive frames; prev_pts cuda f32 [B,n,2], the corners in the newer
+        one; mask cuda u8 [B,n] or None.  The constant-velocity extrapolation of the two poses moves every usable corner by the
+        difference of its projections; a prediction with a corner behind the camera, a flow beyond max_flow_px or a non-finite number
+        is distrusted as a whole.  -> (seeds [B,n,2] f32 -- pass them to lk_track as next_pts with LK_USE_INITIAL_FLOW --, flow [B,n,2]
+        f32, flow_max [B] f32: -1 when distrusted, pose_pred [B,6] f64).  Enqueues only."""
+        assert obj.is_cuda and obj.is_contiguous() and obj.dtype in (torch.float32, torch.float64)
+        assert prev_pts.is_cuda and prev_pts.dtype == torch.float32 and prev_pts.is_contiguous() and prev_pts.dim() == 3
+        B, n, _ = prev_pts.shape
+        shared = obj.dim() == 2
+        if (obj.shape[0] if shared else obj.shape[1]) != n:
+            raise error("predictFlow: object/image point counts differ")
+        for p in (pose_older, pose_newer):
+            assert p.is_cuda and p.dtype == torch.float64 and p.is_contiguous() and p.shape == (B, 6)
+        if mask is not None:
+            assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (B, n)
+        seeds = torch.empty_like(prev_pts)
+        flow = torch.empty_like(prev_pts)
+        fmax = torch.empty((B,), dtype=torch.float32, device=prev_pts.device)
+        pred = torch.empty((B, 6), dtype=torch.float64, device=prev_pts.device)
+        Kh, _ = _host_f64(K)
+        dh, nd = _host_f64(dist)
+        H.check(self.L.agt_predict_flow(self.h, _ptr(obj), 0 if shared else n * 3, H.F32 if obj.dtype == torch.float32 else H.F64, n, B,
+                                        _ptr(pose_older), _ptr(pose_newer), Kh.ctypes.data_as(C.c_void_p),
+                                        dh.ctypes.data_as(C.c_void_p) if nd else None, nd, _ptr(prev_pts), _ptr(mask), float(max_flow_px),
+                                        _ptr(seeds), _ptr(flow), _ptr(fmax), _ptr(pred)), "agt_predict_flow")
+        return seeds, flow, fmax, pred
+
 
 # ------------------------------------------------------------------------------------
 # numpy-in / numpy-out functions with cv2's signatures (one synchronous call per frame,
@@ -632,3 +661,47 @@ def solvePnPTagConsensus(objectPoints, imagePoints, cameraMatrix, distCoeffs, rv
         idx = np.flatnonzero(inl.cpu().numpy()[0]).astype(np.int32).reshape(-1, 1)
         ok = bool(info.cpu().numpy()[0, H.INFO_OK])
         return ok, pose[:3].reshape(3, 1).copy(), pose[3:].reshape(3, 1).copy(), idx
+
+
+def predictFlow(objectPoints, rvecOlder, tvecOlder, rvecNewer, tvecNewer, cameraMatrix, distCoeffs, prevPts, mask=None, maxFlow=64.0):
+    """Where to start calcOpticalFlowPyrLK when the body moves fast (no cv2 counterpart; the rule: include/agt_hip.h agt_predict_flow).
+    The poses of the two frames before the one to be tracked are extrapolated at constant velocity (equal frame intervals), every
+    corner of prevPts ((N,2) or (N,1,2) f32, seen in the newer frame; mask (N,) marks the usable ones) is moved by the difference of its
+    projections under the predicted and the newer pose.  -> (seedPts in prevPts' shape, f32: pass them as nextPts with
+    OPTFLOW_USE_INITIAL_FLOW; flow, the same shape; flowMax: the largest flow component in px, -1.0 when the prediction is distrusted --
+    a corner behind the camera, a flow beyond maxFlow, a non-finite number -- and the seeds are prevPts; (rvecPred (3,1), tvecPred (3,1)))."""
+    obj = np.asarray(objectPoints)
+    dt = np.float32 if obj.dtype == np.float32 else np.float64
+    obj = np.ascontiguousarray(obj.reshape(-1, 3), dtype=dt)
+    prev = np.asarray(prevPts)
+    shape = prev.shape
+    prev = np.ascontiguousarray(prev.reshape(-1, 2), dtype=np.float32)
+    n = obj.shape[0]
+    if prev.shape[0] != n or n == 0 or n > 256:
+        raise error("predictFlow: need 1 <= N <= 256 matching object points and previous points")
+    if not (np.isfinite(maxFlow) and maxFlow > 0):
+        raise error("predictFlow: maxFlow must be finite and > 0")
+    for v in (rvecOlder, tvecOlder, rvecNewer, tvecNewer):
+        if np.size(v) != 3:
+            raise error("predictFlow: 3-element rvecs and tvecs are expected")
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0).astype(np.uint8)
+        if m.shape[0] != n:
+            raise error("predictFlow: mask must have one entry per point")
+    _require_gpu()
+    ctx = _geom_context(n)
+    with ctx.lock:
+        ctx.use_current_stream()
+        dev = torch.device("cuda", ctx.device)
+        po = np.concatenate([np.asarray(rvecOlder, np.float64).reshape(3), np.asarray(tvecOlder, np.float64).reshape(3)]).reshape(1, 6)
+        pn = np.concatenate([np.asarray(rvecNewer, np.float64).reshape(3), np.asarray(tvecNewer, np.float64).reshape(3)]).reshape(1, 6)
+        try:
+            seeds, flow, fmax, pred = ctx.predict_flow(torch.from_numpy(obj).to(dev), torch.from_numpy(po).to(dev), torch.from_numpy(pn).to(dev),
+                                                       cameraMatrix, distCoeffs, torch.from_numpy(prev).to(dev).reshape(1, n, 2),
+                                                       None if m is None else torch.from_numpy(m).to(dev).reshape(1, n), float(maxFlow))
+        except H.AgtError as e:
+            raise error(str(e))
+        pred = pred.cpu().numpy()[0]
+        return (seeds.cpu().numpy().reshape(shape), flow.cpu().numpy().reshape(shape), float(fmax.cpu().numpy()[0]),
+                (pred[:3].reshape(3, 1).copy(), pred[3:].reshape(3, 1).copy()))

@@ -23,6 +23,7 @@ STATE_STRIDE = 16
 ST_RVEC, ST_TVEC, ST_OK, ST_ERR, ST_NTRACK, ST_ITERS, ST_GUESS, ST_FLAGS, ST_TVEC_F32 = 0, 3, 6, 7, 8, 9, 10, 11, 12
 ST_NVISIBLE = 13
 ST_NINLIER = 14
+ST_FLOW = 15
 TRK_ZERO_VELOCITY = 256
 TRK_CHAIN_TIMEOUT = 512
 PROF_SPANS = 5
@@ -43,6 +44,7 @@ SYMBOLS = [
     "agt_device_info", "agt_xcd_tile_order", "agt_lk_occupancy", "agt_lk_occupancy_cu", "agt_lk_lds_request",
     "agt_solve_pnp_host", "agt_project_points_host", "agt_lk_track_fb", "agt_tracker_fb_check",
     "agt_tracker_visibility", "agt_tag_visibility", "agt_solve_pnp_consensus", "agt_tracker_consensus",
+    "agt_predict_flow", "agt_tracker_predict",
 ]
 
 
@@ -99,6 +101,8 @@ def lib():
     L.agt_tag_visibility.argtypes = [vp, vp, sz, i32, i32, i32, vp, i32, f64, i32, vp, vp]
     L.agt_solve_pnp_consensus.argtypes = [vp, vp, sz, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, f64, i32, vp, vp, vp, vp]
     L.agt_tracker_consensus.argtypes = [vp, i32, f64, i32]
+    L.agt_predict_flow.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, f64, vp, vp, vp, vp]
+    L.agt_tracker_predict.argtypes = [vp, f64]
     L.agt_solve_pnp.argtypes = [vp, vp, sz, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
     L.agt_project_points.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.agt_tracker_reset.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32]

@@ -33,6 +33,8 @@ import numpy as np
 
 from .geometry import TransformHelper
 
+OPTFLOW_USE_INITIAL_FLOW = 4        # cv2's value (a cv module handed in need not carry the constant)
+
 
 class PoseDetector(TransformHelper):
     DIRPATH = 'aprilgroup_tracking/aprilgroup_pose_estimation'
@@ -44,7 +46,8 @@ class PoseDetector(TransformHelper):
 
     CONSENSUS_MIN = 8       # inliers a tag hypothesis needs to be elected (pnp_consensus_px): more than one tag's own four
 
-    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None, pnp_consensus_px=None):
+    def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None, pnp_consensus_px=None,
+                 lk_predict_px=None):
         """`detector(gray) -> iterable of objects with .tag_id, .corners (4,2), .decision_margin`
         stands in for apriltag.Detector(...).detect (detect_pose.py:368-371).
         lk_fb_px: forward-backward check of the LK step (None / 0 = off): a tracked corner whose track back into the previous
@@ -54,7 +57,12 @@ class PoseDetector(TransformHelper):
         corner votes on every tag's pose with this reprojection threshold, and only the tags whose four corners all agree with the
         winner go into _estimate_pose (tag_consensus below; the rule: include/agt_hip.h agt_solve_pnp_consensus).  It is NOT
         ERROR_GATE_PX: that gate judges the mean error of the finished solve, this one a single corner under one tag's pose.
-        Backend "stream" hands it to its StreamTracker (consensus_px); backend "cv" does it on the host with the cv module."""
+        Backend "stream" hands it to its StreamTracker (consensus_px); backend "cv" does it on the host with the cv module.
+        lk_predict_px: motion-predicted initial flow of the LK step (None / 0 = off): once the two frames before the one to be tracked
+        both gave an accepted pose, the constant-velocity extrapolation of those poses moves the start of every corner's search
+        (predict_flow below; the rule: include/agt_hip.h agt_predict_flow); a prediction with a flow beyond this many pixels is not
+        trusted and the frame is tracked as ever.  Backend "stream" hands it to its StreamTracker (predict_px); backend "cv" seeds
+        calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW."""
         TransformHelper.__init__(self, logger, mtx, dist, cv=cv)
         if backend not in ("cv", "stream"):
             raise ValueError("backend must be 'cv' or 'stream'")
@@ -65,6 +73,12 @@ class PoseDetector(TransformHelper):
         if pnp_consensus_px is not None and not (np.isfinite(pnp_consensus_px) and pnp_consensus_px >= 0):
             raise ValueError("pnp_consensus_px must be None or a finite threshold >= 0")
         self.pnp_consensus_px = float(pnp_consensus_px) if pnp_consensus_px else None
+        if lk_predict_px is not None and not (np.isfinite(lk_predict_px) and lk_predict_px >= 0):
+            raise ValueError("lk_predict_px must be None or a finite threshold >= 0")
+        self.lk_predict_px = float(lk_predict_px) if lk_predict_px else None
+        self.last_flow_max = None       # backend "cv": flow_max of the latest LK step (0.0 without a prediction, -1.0 when distrusted)
+        self._records = 0               # backend "cv": calls of _estimate_pose so far, and the (record index, pose) of the accepted
+        self._pose_history = []         # ones among the last two -- what the LK step predicts from
         self.last_consensus = None      # backend "cv": (winning tag's index in the frame's tag list, its inlier count) or None
         self._dev = None                # stream backend: _DeviceStream, created at the first frame (its size fixes the context)
         self.img = None
@@ -127,7 +141,7 @@ class PoseDetector(TransformHelper):
 
     @classmethod
     def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv", lk_fb_px=None,
-                   pnp_consensus_px=None):
+                   pnp_consensus_px=None, lk_predict_px=None):
         """Build from the reference's on-disk files: `CameraParams.npz` (calibrate_camera.py:107-123) and,
         optionally, an `april_group.json` somewhere else than DIRPATH/JSON_FILE (detect_pose.py:54-55).
         `detector` may be a recorded-detections .npz (formats.ReplayDetector) to replay a session."""
@@ -138,11 +152,11 @@ class PoseDetector(TransformHelper):
             detector = formats.ReplayDetector(detector)
         if april_group is None:
             return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
-                       pnp_consensus_px=pnp_consensus_px)
+                       pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px)
         folder, name = os.path.split(os.fspath(april_group))
         sub = type(cls.__name__, (cls,), {"DIRPATH": folder or ".", "JSON_FILE": name})
         return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
-                   pnp_consensus_px=pnp_consensus_px)
+                   pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px)
 
     # ------------------------------------------------------------------ model (detect_pose.py:105-227)
     def get_extrinsics(self):
@@ -228,6 +242,7 @@ class PoseDetector(TransformHelper):
             return self._stream().estimate(self, imgpoints_arr, objpoints_arr)
         prev_snapshot = deepcopy(self.prev_transform)        # solvePnP overwrites aliased guess arrays
         self.last_pose, self.last_error = (None, None), None
+        self._records += 1
         if self.pnp_consensus_px and imgpoints_arr and objpoints_arr:
             # tag consensus: the state machine below is unchanged, it sees the tags whose corners all agree with the elected pose
             # (the device: mask = status AND inliers, then the tag gate); no consensus = no tag = the too-few path
@@ -263,6 +278,10 @@ class PoseDetector(TransformHelper):
             self.extrinsic_guess = (None, None)
             return
         self._project_draw_points(pose)
+        if self.lk_predict_px:
+            # (a float64 copy: solvePnP keeps writing into the guess arrays the pose may alias)
+            self._pose_history = self._pose_history[-1:] + [(self._records, (np.array(rvec, np.float64).reshape(3, 1),
+                                                                               np.array(tvec, np.float64).reshape(3, 1)))]
         if not guided:
             self.extrinsic_guess = pose
         else:
@@ -295,11 +314,31 @@ class PoseDetector(TransformHelper):
     def track_corners(self, gray):
         """North-star step: carry the previous frame's corners into `gray` with pyramidal LK
         (21x21 window, 3 levels, COUNT+EPS (30, 0.01)) and return them per tag."""
-        nxt, status, _ = self.cv.calcOpticalFlowPyrLK(self._prev_gray, gray, self._prev_corners, None,
-                                                      winSize=(21, 21), maxLevel=2)
+        seeds, flow, lk_flags = None, None, 0
+        if self.lk_predict_px:
+            # the frame's record will be number _records + 1: predicted when the two records before it were both accepted
+            self.last_flow_max = 0.0
+            h = self._pose_history
+            if len(h) == 2 and h[0][0] == self._records - 1 and h[1][0] == self._records:
+                obj = np.concatenate([self.transform_marker_corners(self.get_initial_pts(self.extrinsics[i][0]), (self.extrinsics[i][2], self.extrinsics[i][1]))
+                                      for i in self._prev_ids]).astype(np.float32).reshape(-1, 3)
+                seeds, flow, self.last_flow_max, _ = predict_flow(self.cv, obj, self._prev_corners, h[0][1], h[1][1], self.mtx, self.dist,
+                                                                  None, self.lk_predict_px)
+                lk_flags = OPTFLOW_USE_INITIAL_FLOW
+        if seeds is None:
+            nxt, status, _ = self.cv.calcOpticalFlowPyrLK(self._prev_gray, gray, self._prev_corners, None, winSize=(21, 21), maxLevel=2)
+        else:
+            nxt, status, _ = self.cv.calcOpticalFlowPyrLK(self._prev_gray, gray, self._prev_corners, seeds.copy(), winSize=(21, 21), maxLevel=2,
+                                                          flags=lk_flags)
         if self.lk_fb_px:
-            # forward-backward check (OpenCV's lk_track.py sample): back from where the corners arrived; float32 max norm
-            back, st_b, _ = self.cv.calcOpticalFlowPyrLK(gray, self._prev_gray, nxt, None, winSize=(21, 21), maxLevel=2)
+            # forward-backward check (OpenCV's lk_track.py sample): back from where the corners arrived; float32 max norm.  Under
+            # lk_predict_px the way back starts at arrival - flow: started at the arrival it would fail as the unseeded forward pass does
+            if seeds is None:
+                back, st_b, _ = self.cv.calcOpticalFlowPyrLK(gray, self._prev_gray, nxt, None, winSize=(21, 21), maxLevel=2)
+            else:
+                start = (np.asarray(nxt, np.float32).reshape(-1, 2) - flow).astype(np.float32)
+                back, st_b, _ = self.cv.calcOpticalFlowPyrLK(gray, self._prev_gray, np.asarray(nxt, np.float32).reshape(-1, 2), start,
+                                                             winSize=(21, 21), maxLevel=2, flags=lk_flags)
             d = np.abs(np.asarray(self._prev_corners, np.float32).reshape(-1, 2) - np.asarray(back, np.float32).reshape(-1, 2)).max(axis=1)
             status = (status.reshape(-1) != 0) & (st_b.reshape(-1) != 0) & (d < np.float32(self.lk_fb_px))
         nxt = nxt.reshape(-1, 4, 2); ok = status.reshape(-1, 4).all(axis=1)
@@ -357,6 +396,48 @@ class PoseDetector(TransformHelper):
             self._prev_corners = np.array(img_list, dtype=np.float32).reshape(-1, 2)
             self._prev_ids = list(ids)
 
+
+def predict_flow(cv, obj, prev_pts, older, newer, mtx, dist, usable, max_flow_px):
+    """The seed rule of the motion-predicted initial flow (include/agt_hip.h agt_predict_flow) on the host, with the `cv` module's
+    Rodrigues / projectPoints: obj (n,3), prev_pts (n,2) float32 (the corners in the newer frame), older / newer = (rvec, tvec) of the two
+    frames before the one to be tracked, usable (n,) bool or None.
+    -> (seeds (n,2) float32, flow (n,2) float32, flow_max: 0.0 without usable corners, -1.0 when the prediction is not trusted (the seeds
+    are then prev_pts bit for bit), (rvec, tvec) of the predicted pose)."""
+    if not (np.isfinite(max_flow_px) and max_flow_px > 0):
+        raise ValueError("predict_flow: a finite max_flow_px > 0 is expected")
+    prev = np.ascontiguousarray(np.asarray(prev_pts, np.float32).reshape(-1, 2))
+    n = prev.shape[0]
+    obj64 = np.asarray(obj).reshape(n, 3).astype(np.float64)
+    usable = np.ones(n, bool) if usable is None else np.asarray(usable).reshape(n) != 0
+    r2, t2 = (np.asarray(v, np.float64).reshape(3, 1) for v in older)
+    r1, t1 = (np.asarray(v, np.float64).reshape(3, 1) for v in newer)
+    nothing = (prev.copy(), np.zeros((n, 2), np.float32), -1.0)
+    nan_pose = (np.full((3, 1), np.nan), np.full((3, 1), np.nan))
+    if not all(np.isfinite(v).all() for v in (r2, t2, r1, t1)):
+        return nothing + (nan_pose,)
+    R2 = np.asarray(cv.Rodrigues(r2)[0], np.float64).reshape(3, 3)
+    R1 = np.asarray(cv.Rodrigues(r1)[0], np.float64).reshape(3, 3)
+    D = R1 @ R2.T                       # the camera-frame motion older -> newer, applied once more
+    Rp = D @ R1
+    tp = D @ (t1 - t2) + t1
+    rp = np.asarray(cv.Rodrigues(Rp)[0], np.float64).reshape(3, 1)
+    pred = (rp, tp)
+    p1, _ = cv.projectPoints(obj64, r1, t1, mtx, dist)
+    pp, _ = cv.projectPoints(obj64, rp, tp, mtx, dist)
+    with np.errstate(over="ignore", invalid="ignore"):
+        flow = (np.asarray(pp, np.float64).reshape(n, 2) - np.asarray(p1, np.float64).reshape(n, 2)).astype(np.float32)
+    Rpp = np.asarray(cv.Rodrigues(rp)[0], np.float64).reshape(3, 3)
+    z1 = obj64 @ R1[2] + t1[2, 0]
+    zp = obj64 @ Rpp[2] + tp[2, 0]
+    mag = np.abs(flow).max(axis=1) if n else np.zeros(0, np.float32)
+    with np.errstate(invalid="ignore"):
+        fine = (z1 > 0.0) & (zp > 0.0) & np.isfinite(flow).all(axis=1) & (mag <= np.float32(max_flow_px))
+    if not fine[usable].all():
+        return nothing + (pred,)
+    flow[~usable] = 0.0
+    seeds = prev.copy()
+    seeds[usable] = prev[usable] + flow[usable]          # (float32 add per component)
+    return seeds, flow, float(mag[usable].max()) if usable.any() else 0.0, pred
 
 
 def tag_consensus(cv, obj, img, mtx, dist, usable=None, guess=None, corners_per_tag=4, inlier_px=2.0, min_inliers=8):
@@ -444,7 +525,8 @@ class _DeviceStream:
         self.trk = StreamTracker(gw, gh, det.all_objpts, det.mtx, det.dist, n_streams=1, max_level=2, win=21,
                                  enhance_ape=det.enhance_ape, reproject=False, min_points=4 * det.MIN_TAGS,
                                  gate_px=float(det.ERROR_GATE_PX), fb_check=det.lk_fb_px or 0.0,
-                                 consensus_px=det.pnp_consensus_px or 0.0, consensus_min=det.CONSENSUS_MIN)
+                                 consensus_px=det.pnp_consensus_px or 0.0, consensus_min=det.CONSENSUS_MIN,
+                                 predict_px=det.lk_predict_px or 0.0)
         self.trk.tag_gate(4)
         self.trk.pipeline(1)
         self.trk.reset()

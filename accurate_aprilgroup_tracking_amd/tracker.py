@@ -25,7 +25,9 @@ class TrackState(C.Structure):
 class StreamTracker:
     def __init__(self, width, height, obj_points, K, dist=None, n_streams=1, max_level=2, win=21,
                  enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0, view_deg=0.0, facing=1,
-                 consensus_px=0.0, consensus_min=8):
+                 consensus_px=0.0, consensus_min=8, predict_px=0.0):
+        if not (np.isfinite(predict_px) and predict_px >= 0):
+            raise ValueError("StreamTracker: predict_px must be finite and >= 0")
         if view_deg and not reproject:
             # (the rule acts inside the reproject refresh only: accepting it here would be a silent no-op)
             raise ValueError("StreamTracker: view_deg needs reproject=True (the visibility rule acts in the corner refresh)")
@@ -49,6 +51,8 @@ class StreamTracker:
             self.visibility(view_deg, 4, facing)
         if consensus_px:
             self.consensus(consensus_px, 4, consensus_min)
+        if predict_px:
+            self.predict(predict_px)
         self._alive = []            # frames aliased by pyramid level 0 of the ring entries in flight
         self._keep_frames = max((max_level + 6) + 2, 12)
 
@@ -123,6 +127,19 @@ class StreamTracker:
         finished solve.  0 switches it off (the default).  While it is on, step() runs stage by stage whatever the pipeline depth,
         with two more launches per frame; step_dense() is refused.  May be changed mid-stream; joins the pipeline."""
         H.check(self.ctx.L.agt_tracker_consensus(self.ctx.h, int(corners_per_tag), float(inlier_px), int(min_inliers)), "agt_tracker_consensus")
+
+    def predict(self, max_px=64.0):
+        """Motion-predicted initial flow for the LK step (agt_tracker_predict): once a stream's last two records were both accepted, the
+        constant-velocity extrapolation of their poses moves the start of every corner's search by the difference of its projections,
+        so LK follows image motion far beyond its ~15 px reach.  A prediction with a corner behind the camera or a flow beyond max_px is
+        distrusted as a whole and the frame is the plain step; the record's ST_FLOW slot carries the largest flow component (0.0 without
+        a prediction, -1.0 when distrusted).  Assumes equal frame intervals; raw LK chaining still drifts under fast motion, so pair it
+        with reproject=True on long stretches.  0 switches it off (the default).  While it is on, step() runs stage by stage whatever
+        the pipeline depth, with one more launch per frame; step_dense() is refused.  May be changed mid-stream; joins the pipeline and
+        clears the pose history."""
+        if not (np.isfinite(max_px) and max_px >= 0):
+            raise ValueError("StreamTracker.predict: max_px must be finite and >= 0")
+        H.check(self.ctx.L.agt_tracker_predict(self.ctx.h, float(max_px)), "agt_tracker_predict")
 
     def rewind(self):
         """Take the newest frame back as the tracking source: the next step() tracks from the frame before it (the reference

@@ -83,6 +83,9 @@ extern "C" {
                                reproject option, or when the pose was not accepted */
 #define AGT_ST_NINLIER 14   /* inliers of the frame's winning tag hypothesis (agt_tracker_consensus); 0.0 while the option is off or when the
                                frame had no consensus */
+#define AGT_ST_FLOW 15      /* flow_max of the frame's LK step (agt_tracker_predict): the largest component of the predicted flows, px; 0.0 while
+                               the option is off, for a frame without a prediction and for frames without an LK step; -1.0 when the
+                               prediction was distrusted */
 #define AGT_TRK_ZERO_VELOCITY 256  /* a velocity element was exactly 0: reference raises ValueError (detect_pose.py:236-237) */
 #define AGT_TRK_CHAIN_TIMEOUT 512  /* pipelined tracker: the pose solve gave up waiting for the frame's corners (or did so for an earlier frame of
                                       the stream): nothing was solved, the record is invalid, the stream's state is frozen until agt_tracker_reset */
@@ -229,6 +232,28 @@ int agt_tag_visibility(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride,
                        const double* d_pose, int corners_per_tag, double max_view_deg, int facing,
                        uint8_t* d_visible, double* d_cos);
 
+/* ---- motion-predicted initial flow: the seed rule of agt_tracker_predict as a call of its own ---- */
+/* LK searches from a corner's previous position and loses a body that moves more than about 15 px per frame; this call predicts where
+ * the corners go from two poses.  d_obj as agt_project_points; d_pose_older = (r2, t2), d_pose_newer = (r1, t1): [B][6] f64, the poses of
+ * two consecutive frames; d_prev_pts [B][n][2] f32: the corners in the newer frame; d_mask [B][n] u8 or NULL.  Per stream, in FP64:
+ *   1. R2 = Rodrigues(r2), R1 = Rodrigues(r1);  D = R1 R2^T;  Rp = D R1,  tp = D (t1 - t2) + t1  -- constant velocity in the camera frame
+ *      over equal frame intervals;  pose_pred = (Rodrigues^-1(Rp), tp)
+ *   2. (u1, v1)_i = projectPoints(X_i; newer), (up, vp)_i = projectPoints(X_i; pose_pred), full camera model;
+ *      f_i = ((float)(up - u1), (float)(vp - v1)): subtracted in double, rounded once
+ *   3. corner i is usable when d_mask is NULL or d_mask[b][i] != 0.  The prediction is TRUSTED when all 12 pose numbers are finite and
+ *      every usable corner has Zc > 0 under both poses, finite f_i and max(|f_i.x|, |f_i.y|) <= (float)max_flow_px
+ *   4. trusted: seed_i = p_i + f_i (float32) for usable corners, seed_i = p_i and f_i = 0 for the others, flow_max = the largest
+ *      max(|f_i.x|, |f_i.y|) over usable corners (0 without any);  not trusted: every seed_i = p_i, every f_i = 0, flow_max = -1
+ * so a wild prediction never pushes a search window out of the image.  d_seed_pts [B][n][2] f32 (required; hand it to agt_lk_track as
+ * d_next_pts with AGT_LK_USE_INITIAL_FLOW: seeds equal to the previous points give the bits of a call without initial flow),
+ * d_flow [B][n][2] f32, d_flow_max [B] f32, d_pose_pred [B][6] f64 (six NaNs when a pose number is not finite): each may be NULL.
+ * One launch on the context's stream (one workgroup per stream); does not synchronise.  AGT_ERR_ARG: a required pointer NULL,
+ * max_flow_px not finite or <= 0; AGT_ERR_NPOINTS: n > 256; AGT_ERR_DIST as elsewhere.  Present from ABI 505 on: look the symbol up. */
+int agt_predict_flow(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
+                     const double* d_pose_older, const double* d_pose_newer, const double* K, const double* dist, int ndist,
+                     const float* d_prev_pts, const uint8_t* d_mask, double max_flow_px,
+                     float* d_seed_pts, float* d_flow, float* d_flow_max, double* d_pose_pred);
+
 /* ---- the same two calls SYNCHRONOUS, host arrays in and out: what the reference does once per frame (cv2.solvePnP at
  * detect_pose.py:509-526, cv2.projectPoints at :441-465).  One launch each and no copy: the arguments are placed in a host-mapped
  * staging area of the context, the kernel reads them and writes its results there, the calling thread polls a sequence word the
@@ -324,6 +349,25 @@ int agt_tracker_visibility(agt_ctx* ctx, int corners_per_tag, double max_view_de
  * inlier_px > 0 -- a corner count that is no multiple of corners_per_tag or makes more than 64 tags; a later agt_tracker_reset with
  * such a count returns AGT_ERR_ARG as well while the option is on.  Present from ABI 505 on: look the symbol up. */
 int agt_tracker_consensus(agt_ctx* ctx, int corners_per_tag, double inlier_px, int min_inliers);
+/* Motion-predicted initial flow for the tracker's LK step (max_flow_px = 0: off, the default).  The forward-backward check, the
+ * visibility rule and the tag consensus repair what LK gets wrong after it latched onto something; none of them helps when the search
+ * never reaches the corner, which happens from about 15 px of image motion per frame on.  With the option on, the tracker keeps, per
+ * stream and on the device, the poses of the stream's last two records (whatever produced them: agt_track_frame*, agt_track_host_frame,
+ * agt_track_frame_detected, agt_estimate_pose).  The LK step of a frame has a prediction if and only if those two records were both
+ * accepted (AGT_ST_OK): one launch in front of the LK launch writes the seeds of agt_predict_flow's rule (older / newer = the two
+ * records' poses, mask = the previous frame's LK status, so a dead corner carries its position) into the frame's corner entry, and LK
+ * runs with AGT_LK_USE_INITIAL_FLOW.  A stream without a prediction, and one whose prediction is distrusted, gets seeds equal to its
+ * previous corners, which is bitwise the plain step.  The record's AGT_ST_FLOW slot carries flow_max (0.0 without a prediction, -1.0
+ * when distrusted).  The pose state machine (guess, prev_transform, velocities) is not touched: the reference's motion-model guess is
+ * a poor predictor of the NEXT frame's corners and is not used for this.  Under agt_tracker_fb_check the backward pass starts at
+ * arrival - flow (one more small launch); the verdict rule is unchanged.  Tag gate, consensus, reproject and the visibility rule act
+ * after LK and are unchanged.  Limits: equal frame intervals and constant velocity are assumed; the first prediction needs two accepted
+ * frames; raw LK chaining still drifts under fast motion, so pair the option with reproject on long stretches.  While it is on, frames
+ * run stage by stage whatever the pipeline depth (as under fb_check / reproject / consensus) with one more launch per frame, and
+ * agt_track_frame_dense / agt_track_frames_dense return AGT_ERR_UNSUPPORTED; switching it off brings the pipelined forms back.  Joins
+ * the pipeline and clears the pose history, as agt_tracker_reset does.  AGT_ERR_ARG: max_flow_px not finite or < 0.  Present from ABI
+ * 505 on: look the symbol up. */
+int agt_tracker_predict(agt_ctx* ctx, double max_flow_px);
 /* Software pipelining across frames.  depth 0: separate launches per stage, the record of frame t is complete
  * in stream order after its call.  depth F in 1..32 (default 1; needs reproject == 0, otherwise the call falls back to
  * depth 0 behaviour): agt_track_frame registers the frame and, every F calls, issues ONE fused launch that advances every
