@@ -705,3 +705,10 @@ def predictFlow(objectPoints, rvecOlder, tvecOlder, rvecNewer, tvecNewer, camera
         pred = pred.cpu().numpy()[0]
         return (seeds.cpu().numpy().reshape(shape), flow.cpu().numpy().reshape(shape), float(fmax.cpu().numpy()[0]),
                 (pred[:3].reshape(3, 1).copy(), pred[3:].reshape(3, 1).copy()))
+
+
+def calibrateAprilGroup(frames, tagSizes, cameraMatrix, distCoeffs, initGroup=None, anchor=None, maxIters=50, **kwargs):
+    """Offline calibration of the AprilGroup model from a detection recording (no cv2 counterpart; group_calib.calibrate_group,
+    include/agt_calib.h): -> (april_group dict, rvecs (F,3), tvecs (F,3), report)."""
+    from . import group_calib
+    return group_calib.calibrate_group(frames, tagSizes, cameraMatrix, distCoeffs, init_group=initGroup, anchor=anchor, max_iters=maxIters, **kwargs)

@@ -74,7 +74,10 @@ def load_april_group(path):
 
 
 def save_april_group(path, extrinsics):
-    """Inverse of load_april_group; accepts {id: [size, tvec, rvec]} or {id: {"size":, "extrinsics":}}."""
+    """Inverse of load_april_group; accepts {id: [size, tvec, rvec]}, {id: {"size":, "extrinsics":}} or the whole file's
+    {"tags": {id: {"size":, "extrinsics":}}} (what synthetic.make_april_group and group_calib.calibrate_group return)."""
+    if isinstance(extrinsics, dict) and set(extrinsics) == {"tags"} and isinstance(extrinsics["tags"], dict):
+        extrinsics = extrinsics["tags"]
     tags = {}
     for tag_id, v in extrinsics.items():
         if isinstance(v, dict):

@@ -1,0 +1,175 @@
+"""Scene builders of the group-calibration tests (TEST INFRASTRUCTURE): noise-free (or seeded-noise) projections of a
+synthetic.make_april_group model along a synthetic.trajectory-style path, visibility by a facing test, optionally thinned by an explicit
+(F, T) mask so that a test can ask for exact co-visibility patterns."""
+import numpy as np
+from scipy.spatial.transform import Rotation
+
+from accurate_aprilgroup_tracking_amd import formats, synthetic
+
+import group_ba_numpy as ba
+import pnp_numpy
+
+TILT14 = np.array([0.05, -0.1, 1e-3, -1e-3, 0.02, 0.01, -0.02, 0.005, 1e-3, -5e-4, 5e-4, 1e-3, 0.02, -0.015])
+
+
+def compose(a, b):
+    Ra, Rb = Rotation.from_rotvec(a[:3]).as_matrix(), Rotation.from_rotvec(b[:3]).as_matrix()
+    return np.concatenate([Rotation.from_matrix(Ra @ Rb).as_rotvec(), Ra @ b[3:] + a[3:]])
+
+
+def invert(a):
+    Ra = Rotation.from_rotvec(a[:3]).as_matrix()
+    return np.concatenate([Rotation.from_matrix(Ra.T).as_rotvec(), -Ra.T @ a[3:]])
+
+
+def perturb(pose, angle_deg, shift, rng):
+    """pose with a rotation of angle_deg about a random axis applied on the left and a random shift of length `shift`"""
+    ax = rng.standard_normal(3); ax /= np.linalg.norm(ax)
+    sh = rng.standard_normal(3); sh *= shift / np.linalg.norm(sh)
+    R = Rotation.from_rotvec(ax * np.deg2rad(angle_deg)).as_matrix() @ Rotation.from_rotvec(pose[:3]).as_matrix()
+    return np.concatenate([Rotation.from_matrix(R).as_rotvec(), pose[3:] + sh])
+
+
+class Scene:
+    def __init__(self, n_tags, n_frames, seed=0, dist=None, noise=0.0, keep=None, max_view_deg=70.0, max_polar_deg=46.0, swing=1.0,
+                 width=1280, height=720, tag_size=0.020):
+        self.group = synthetic.make_april_group(n_tags=n_tags, tag_size=tag_size, max_polar_deg=max_polar_deg, seed=seed)
+        self.tag_ids = [int(k) for k in self.group["tags"]]
+        self.sizes = np.array([self.group["tags"][str(t)]["size"] for t in self.tag_ids])
+        self.K = synthetic.camera_matrix(width, height)
+        self.dist = None if dist is None else np.asarray(dist, np.float64).reshape(-1)
+        # the truth: float64 of what the JSON holds (float32-rounded), rvec | tvec
+        self.tag_poses = np.array([[*self.group["tags"][str(t)]["extrinsics"][3:], *self.group["tags"][str(t)]["extrinsics"][:3]] for t in self.tag_ids])
+        rv, tv = synthetic.trajectory(n_frames, seed)
+        # synthetic.trajectory swings by a few degrees; the calibration needs every tag seen from several sides
+        k = np.arange(n_frames)[:, None]
+        rng = np.random.default_rng(seed + 31)
+        ph = rng.uniform(0, 2 * np.pi, 3)
+        rv = rv + swing * np.array([0.5, 0.6, 0.3]) * np.sin(2 * np.pi * k / np.array([7.3, 5.1, 9.7]) + ph)
+        self.frame_poses = np.concatenate([rv, tv], axis=1)
+        self.visible = np.zeros((n_frames, n_tags), bool)
+        cos_max = np.cos(np.deg2rad(max_view_deg))
+        noise_rng = np.random.default_rng(seed + 977)
+        self.frames = []
+        for f in range(n_frames):
+            Rf = Rotation.from_rotvec(rv[f]).as_matrix()
+            dets = []
+            for i, t in enumerate(self.tag_ids):
+                Rt = Rotation.from_rotvec(self.tag_poses[i, :3]).as_matrix()
+                centre = Rf @ self.tag_poses[i, 3:] + tv[f]
+                normal = Rf @ Rt[:, 2]
+                facing = -(normal @ centre) / np.linalg.norm(centre) > cos_max and centre[2] > 0
+                if not facing or (keep is not None and not keep[f][i]):
+                    continue
+                X = ba.corners3d(self.sizes[i]) @ Rt.T + self.tag_poses[i, 3:]
+                px = pnp_numpy.project(X, rv[f], tv[f], self.K, self.dist)
+                if noise:
+                    px = px + noise * noise_rng.standard_normal(px.shape)
+                self.visible[f, i] = True
+                dets.append(formats.make_detection(t, px))
+            self.frames.append(dets)
+
+    @property
+    def tag_sizes(self):
+        return {t: float(s) for t, s in zip(self.tag_ids, self.sizes)}
+
+    def table(self):
+        fr, tg, co = [], [], []
+        for f, dets in enumerate(self.frames):
+            for d in dets:
+                fr.append(f); tg.append(self.tag_ids.index(d.tag_id)); co.append(d.corners)
+        return np.asarray(fr, np.int32), np.asarray(tg, np.int32), np.asarray(co, np.float64).reshape(-1, 4, 2)
+
+    def problem(self, anchor=0):
+        fr, tg, co = self.table()
+        return ba.make_problem(self.K, self.dist, self.sizes, anchor, len(self.frames), fr, tg, co)
+
+    def in_anchor_frame(self, anchor):
+        """the truth with the body frame moved into the anchor tag's frame: (tag_poses, frame_poses)"""
+        qa = self.tag_poses[anchor]
+        return (np.array([compose(invert(qa), q) for q in self.tag_poses]), np.array([compose(p, qa) for p in self.frame_poses]))
+
+    def connected(self, anchor=0):
+        reach, grew = {anchor}, True
+        while grew:
+            grew = False
+            for row in self.visible:
+                seen = set(np.flatnonzero(row))
+                if seen & reach and not seen <= reach:
+                    reach |= seen; grew = True
+        return len(reach) == len(self.tag_ids) and self.visible.any(axis=0).all()
+
+
+def keep_mask(n_frames, n_tags, rows):
+    """(F, T) bool from {frame: [tags]}"""
+    m = np.zeros((n_frames, n_tags), bool)
+    for f, tags in rows.items():
+        m[f, list(tags)] = True
+    return m
+
+
+def parity_scene(dist=None):
+    """T = 5, F = 7: frame 0 sees one tag, frame 1 all five, tag 4 is seen in two frames only"""
+    keep = keep_mask(7, 5, {0: [0], 1: [0, 1, 2, 3, 4], 2: [0, 1], 3: [1, 2, 3], 4: [2, 3], 5: [3, 4], 6: [0, 2, 3]})
+    return Scene(5, 7, seed=3, dist=dist, keep=keep, max_view_deg=89.0, swing=0.35)
+
+
+def wave_scene():
+    """T = 17, F = 9: frame 4 sees all 17 tags (68 corners), the others two or three"""
+    rows = {4: range(17)}
+    for f in [0, 1, 2, 3, 5, 6, 7, 8]:
+        rows[f] = [(2 * f + j) % 17 for j in range(2 + f % 2)]
+    return Scene(17, 9, seed=5, keep=keep_mask(9, 17, rows), max_view_deg=89.0, swing=0.3, tag_size=0.010)
+
+
+def smallest_scene():
+    """T = 2, F = 3"""
+    return Scene(2, 3, seed=7, max_view_deg=89.0, swing=0.3)
+
+
+def recovery_scene():
+    """T = 6, F = 12, noise-free, visibility by the facing test alone"""
+    return Scene(6, 12, seed=11, max_view_deg=55.0, max_polar_deg=60.0)
+
+
+def noisy_scene(n_frames=40, seed=13, noise=0.2):
+    """T = 12, F = 40, sigma = 0.2 px"""
+    return Scene(12, n_frames, seed=seed, noise=noise, max_view_deg=60.0, max_polar_deg=60.0)
+
+
+def perturbed_start(sc, seed=1, frames=True):
+    """the truth with every tag but tag 0 moved by 1 degree and 1 mm (and, with frames, every frame pose by 0.5 degree and 1 mm)"""
+    rng = np.random.default_rng(seed)
+    tp = np.array([perturb(q, 1.0, 1e-3, rng) if i else q for i, q in enumerate(sc.tag_poses)])
+    fp = np.array([perturb(q, 0.5, 1e-3, rng) for q in sc.frame_poses]) if frames else sc.frame_poses.copy()
+    return tp, fp
+
+
+# the nominal model's error in the end-to-end test: 2 degrees give 1.32 px at worst on this clip, under the tracker's 2 px gate
+# (tests/test_group_calib.py::test_nominal_model_fails_the_gate measures both), so the perturbation is 4 degrees
+E2E_PERTURB_DEG = 4.0
+
+
+def e2e_scene():
+    """the clip of the end-to-end test: noise-free, every frame sees two tags or more"""
+    sc = Scene(12, 20, seed=13, max_view_deg=60.0, max_polar_deg=60.0)
+    assert (sc.visible.sum(axis=1) >= 2).all()
+    return sc
+
+
+def e2e_nominal(sc):
+    rng = np.random.default_rng(5)
+    return np.array([perturb(q, E2E_PERTURB_DEG, 0.0, rng) for q in sc.tag_poses])
+
+
+def flipped_view(pose):
+    """the second minimum of a planar four-point pose, to first order: the tag (pose: tag -> camera) turned about its centre so that its
+    normal is mirrored across the line of sight"""
+    R = Rotation.from_rotvec(pose[:3]).as_matrix()
+    v = pose[3:] / np.linalg.norm(pose[3:])
+    n = R[:, 2]
+    m = 2.0 * (n @ v) * v - n
+    axis = np.cross(n, m)
+    s = np.linalg.norm(axis)
+    turn = Rotation.from_rotvec(axis / s * np.arctan2(s, n @ m)).as_matrix()
+    return np.concatenate([Rotation.from_matrix(turn @ R).as_rotvec(), pose[3:]])

@@ -1,0 +1,272 @@
+"""GPU: the AprilGroup bundle adjustment of libagt_calib.so (include/agt_calib.h) against the numpy / scipy statement of the same
+problem (tests/group_ba_numpy.py), from one evaluation up to the command-line tool.
+
+Bounds.  Residuals: 1e-9 px, the project's bound for agt_project_points.  A damped step: relative to the step's norm, ten times the
+floor -- the largest difference between numpy's own Schur and dense steps over the lambdas of the scene (the two sides order their
+sums differently; tests/test_group_calib.py::test_numpy_schur_step_equals_dense_step prints the same figures on the CPU).
+Recovered parameters: ten times the distance between scipy's solution and the truth.  Final cost of the noisy solve: ten times the
+larger of the spread of scipy's own final cost over two different starts and n_residuals * eps, the worst-case relative rounding
+error of a sum of n_residuals squares.  Every figure is printed before it is asserted; profiles/group_calib.md records them.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import calib_scenes as cs          # noqa: E402
+import group_ba_numpy as ba        # noqa: E402
+
+from accurate_aprilgroup_tracking_amd import synthetic    # noqa: E402
+
+pytestmark = pytest.mark.gpu
+EPS = float(np.finfo(np.float64).eps)
+LAMBDAS = (0.0, 1e-3, 10.0)
+SCENES = {"plain": cs.parity_scene, "mild": lambda: cs.parity_scene(synthetic.MILD_DIST), "tilt14": lambda: cs.parity_scene(cs.TILT14),
+          "wave": cs.wave_scene, "smallest": cs.smallest_scene}
+
+
+def gpu_solver(prob, order=None):
+    from accurate_aprilgroup_tracking_amd import caliblib
+    o = np.arange(len(prob["obs_tag"])) if order is None else order
+    return caliblib.GroupCalib(prob["K"], prob["dist"], prob["sizes"], prob["anchor"], prob["F"], prob["obs_frame"][o], prob["obs_tag"][o],
+                               prob["corners"][o])
+
+
+def check_eval(sc):
+    prob = sc.problem(0)
+    tp, fp = cs.perturbed_start(sc)
+    want = ba.residuals(prob, tp, fp)
+    # the table goes in shuffled: the library sorts by frame and answers in the caller's order
+    order = np.random.default_rng(0).permutation(len(want))
+    s = gpu_solver(prob, order)
+    got, cost = s.eval(tp, fp)
+    s.close()
+    d = np.abs(got - want[order]).max()
+    print("residuals: |gpu - numpy| max %.3g px (largest residual %.3g px); cost %.17g vs %.17g" % (d, np.abs(want).max(), cost, 0.5 * (want * want).sum()))
+    assert d <= 1e-9
+    assert abs(cost - 0.5 * (want * want).sum()) <= 1e-9 * np.abs(want).sum()
+
+
+def check_step(sc):
+    prob = sc.problem(0)
+    tp, fp = cs.perturbed_start(sc)
+    dense = {lam: ba.dense_step(prob, tp, fp, lam) for lam in LAMBDAS}
+    floor = max(ba.step_difference(ba.schur_step(prob, tp, fp, lam), dense[lam]) for lam in LAMBDAS)
+    s = gpu_solver(prob)
+    worst = 0.0
+    for lam in LAMBDAS:
+        got = s.step(lam, tp, fp)
+        d = ba.step_difference(got, dense[lam])
+        print("lambda %g: |gpu - dense| / |dense| = %.3g (floor %.3g, bound %.3g)" % (lam, d, floor, 10 * floor))
+        worst = max(worst, d)
+        assert np.array_equal(got[0][prob["anchor"]], np.zeros(6))
+    s.close()
+    assert worst <= 10 * floor
+
+
+@pytest.mark.parametrize("name", ["plain", "mild", "tilt14"])
+def test_evaluation_parity(name):
+    check_eval(SCENES[name]())
+
+
+@pytest.mark.parametrize("name", ["plain", "mild", "tilt14"])
+def test_step_parity(name):
+    check_step(SCENES[name]())
+
+
+def test_wave_boundary():
+    """one frame with 17 tags (68 corners) among frames with two or three; F = 9"""
+    sc = SCENES["wave"]()
+    assert sc.visible.sum(axis=1).max() == 17
+    check_eval(sc)
+    check_step(sc)
+
+
+def test_smallest_system():
+    """T = 2: the reduced system is one 6 x 6 block; F = 3"""
+    sc = SCENES["smallest"]()
+    check_eval(sc)
+    check_step(sc)
+
+
+def test_noise_free_recovery():
+    """T = 6, F = 12, the tags start 1 degree and 1 mm off: the solve reaches scipy's solution from the same start.
+    Measured on the MI355X: see profiles/group_calib.md."""
+    sc = cs.recovery_scene()
+    prob = sc.problem(0)
+    tag0, frame0 = cs.perturbed_start(sc, frames=False)
+    tp_s, fp_s, cost_s, rms_s = ba.solve(prob, tag0, frame0)
+    floor = max(np.abs(tp_s - sc.tag_poses).max(), np.abs(fp_s - sc.frame_poses).max())
+    s = gpu_solver(prob)
+    tp_g, fp_g, rep = s.solve(tag0, frame0, max_iters=100)
+    s.close()
+    d = max(np.abs(tp_g - tp_s).max(), np.abs(fp_g - fp_s).max())
+    print("scipy vs truth %.3g (floor), gpu vs scipy %.3g (bound %.3g), gpu vs truth %.3g; rms scipy %.3g gpu %.3g; %d iterations, %d accepted, stop %d"
+          % (floor, d, 10 * floor, max(np.abs(tp_g - sc.tag_poses).max(), np.abs(fp_g - sc.frame_poses).max()), rms_s, rep.final_rms_px,
+             rep.iterations, rep.accepted, rep.stop_reason))
+    assert np.array_equal(tp_g[0], tag0[0])
+    assert rep.final_cost < rep.initial_cost and rep.accepted >= 1
+    assert d <= 10 * floor
+    assert abs(rep.final_rms_px - rms_s) <= 10 * rms_s
+
+
+N_CAL, N_HELD = 40, 8
+
+
+@pytest.fixture(scope="module")
+def noisy():
+    """the T = 12, F = 40, sigma = 0.2 px solve with bootstrap (and eight more frames of the same path, held out), shared by the tests below"""
+    from accurate_aprilgroup_tracking_amd import group_calib
+    sc = cs.noisy_scene(N_CAL + N_HELD)
+    out = group_calib.calibrate_group(sc.frames[:N_CAL], sc.tag_sizes, sc.K, None)
+    return sc, out
+
+
+def corner_distance(a, b, size):
+    """largest distance between the body-frame corners of a tag under two poses"""
+    from accurate_aprilgroup_tracking_amd import group_calib
+    return np.linalg.norm(group_calib.object_points(a[None], [size]) - group_calib.object_points(b[None], [size]), axis=1).max()
+
+
+def test_noisy_recovery_with_bootstrap(noisy):
+    from accurate_aprilgroup_tracking_amd import cv_hip, group_calib
+    sc, (group, rvecs, tvecs, report) = noisy
+    a = sc.tag_ids.index(report["anchor"])
+    fr, tg, co = group_calib.observation_table(sc.frames[:N_CAL], sc.tag_ids)
+    prob = ba.make_problem(sc.K, None, sc.sizes, a, N_CAL, fr, tg, co)
+    truth_t, truth_f = sc.in_anchor_frame(a)
+    # the reference from the same start, and from the truth: the spread of its own final cost is the floor
+    _, _, cost_ref, _ = ba.solve(prob, report["initial_tag_poses"], report["initial_frame_poses"])
+    _, _, cost_ref2, _ = ba.solve(prob, truth_t, truth_f[:N_CAL])
+    floor = max(abs(cost_ref - cost_ref2) / cost_ref, 8 * len(tg) * EPS)
+    d = abs(report["final_cost"] - cost_ref) / cost_ref
+    print("final cost: gpu %.17g, scipy %.17g (from the truth: %.17g); relative difference %.3g, floor %.3g, bound %.3g; %d iterations, rms %.4f px"
+          % (report["final_cost"], cost_ref, cost_ref2, d, floor, 10 * floor, report["iterations"], report["final_rms_px"]))
+    assert d <= 10 * floor
+    # every tag is closer to the truth than the bootstrap left it
+    cal, boot = report["tag_poses"], report["initial_tag_poses"]
+    for i in range(len(sc.tag_ids)):
+        if i == a:
+            assert np.array_equal(cal[i], np.zeros(6))
+            continue
+        dc, db = corner_distance(cal[i], truth_t[i], sc.sizes[i]), corner_distance(boot[i], truth_t[i], sc.sizes[i])
+        print("tag %d: corners off the truth by %.3g m calibrated, %.3g m bootstrap" % (sc.tag_ids[i], dc, db))
+        assert dc < db
+    # held-out frames: solvePnP with the calibrated model reprojects better than with the bootstrap's
+    err = {}
+    for name, g in (("calibrated", group), ("bootstrap", report["initial_group"])):
+        obj = group_calib.object_points(group_calib.group_to_poses(g, sc.tag_ids), sc.sizes).reshape(-1, 4, 3)
+        e = []
+        for dets in sc.frames[N_CAL:]:
+            o = obj[[sc.tag_ids.index(d.tag_id) for d in dets]].reshape(-1, 3)
+            img = np.concatenate([d.corners for d in dets])
+            ok, r, t = cv_hip.solvePnP(o, img, sc.K, None)
+            proj, _ = cv_hip.projectPoints(o, r, t, sc.K, None)
+            e.append(np.linalg.norm(proj.reshape(-1, 2) - img, axis=1).mean())
+        err[name] = float(np.mean(e))
+    print("held-out mean reprojection error: calibrated %.4f px, bootstrap %.4f px" % (err["calibrated"], err["bootstrap"]))
+    assert err["calibrated"] < err["bootstrap"]
+
+
+def test_bootstrap_rejects_a_flipped_candidate(noisy):
+    from accurate_aprilgroup_tracking_amd import group_calib
+    sc, (_, _, _, report) = noisy
+    a = sc.tag_ids.index(report["anchor"])
+    truth_t, truth_f = sc.in_anchor_frame(a)
+    fr, tg, co = group_calib.observation_table(sc.frames[:N_CAL], sc.tag_ids)
+    # the most oblique view of a tag other than the anchor: there the flipped pose is far from the true one
+    best = None
+    for f, t in zip(fr, tg):
+        if t == a:
+            continue
+        view = cs.compose(truth_f[f], truth_t[t])
+        n = cs.Rotation.from_rotvec(view[:3]).as_matrix()[:, 2]
+        c = abs(n @ view[3:]) / np.linalg.norm(view[3:])
+        if best is None or c < best[0]:
+            best = (c, int(f), int(t), view)
+    _, f, b, view = best
+    flipped = cs.compose(cs.invert(truth_f[f]), cs.flipped_view(view))
+    assert corner_distance(flipped, truth_t[b], sc.sizes[b]) > 0.2 * sc.sizes[b]
+    poses, chosen = group_calib.bootstrap(fr, tg, co, sc.sizes, a, N_CAL, sc.K, None, extra_candidates={b: [flipped]})
+    k, errs = chosen[b]
+    print("tag %d: %d candidates, chosen %d, summed squared error %.3g px^2; the injected flipped pose: %.3g px^2" % (sc.tag_ids[b], len(errs), k, errs[k], errs[-1]))
+    assert k != len(errs) - 1 and errs[k] < errs[-1]
+    assert corner_distance(poses[b], truth_t[b], sc.sizes[b]) < corner_distance(flipped, truth_t[b], sc.sizes[b])
+
+
+def test_determinism(noisy):
+    from accurate_aprilgroup_tracking_amd import group_calib
+    sc, (group, rvecs, tvecs, report) = noisy
+    group2, rvecs2, tvecs2, report2 = group_calib.calibrate_group(sc.frames[:N_CAL], sc.tag_sizes, sc.K, None)
+    assert group2 == group
+    assert np.array_equal(rvecs2.view(np.uint64), rvecs.view(np.uint64)) and np.array_equal(tvecs2.view(np.uint64), tvecs.view(np.uint64))
+    assert sorted(report2) == sorted(report)
+    for k, v in report.items():
+        if isinstance(v, np.ndarray):
+            assert np.array_equal(np.ascontiguousarray(v).view(np.uint64), np.ascontiguousarray(report2[k]).view(np.uint64)), k
+        elif isinstance(v, float):
+            assert np.float64(v).view(np.uint64) == np.float64(report2[k]).view(np.uint64), k
+        else:
+            assert v == report2[k], k
+
+
+def test_refusals():
+    from accurate_aprilgroup_tracking_amd import caliblib, group_calib
+    # tag 3 is never seen together with another tag
+    lone = cs.Scene(5, 4, seed=3, keep=cs.keep_mask(4, 5, {0: [0, 1, 2], 1: [1, 2, 4], 2: [0, 4], 3: [3]}), max_view_deg=89.0, swing=0.3)
+    assert lone.visible[:, 3].sum() == 1 and lone.visible[3].sum() == 1
+    with pytest.raises(caliblib.CalibError) as e:
+        gpu_solver(lone.problem(0))
+    assert e.value.code == caliblib.ERR_DISCONNECTED
+    with pytest.raises(caliblib.CalibError) as e:
+        group_calib.calibrate_group(lone.frames, lone.tag_sizes, lone.K, None)
+    assert e.value.code == caliblib.ERR_DISCONNECTED
+    one = cs.Scene(3, 1, seed=3, max_view_deg=89.0, swing=0.3)
+    with pytest.raises(caliblib.CalibError) as e:
+        gpu_solver(one.problem(0))
+    assert e.value.code == caliblib.ERR_TOO_FEW_FRAMES
+    ok = cs.smallest_scene().problem(0)
+    with pytest.raises(caliblib.CalibError) as e:
+        gpu_solver(dict(ok, sizes=np.full(65, 0.02)))
+    assert e.value.code == caliblib.ERR_ARG
+    with pytest.raises(caliblib.CalibError) as e:
+        gpu_solver(dict(ok, dist=np.zeros(6)))
+    assert e.value.code == caliblib.ERR_CAMERA
+    # ... and the same problem is accepted once it is whole
+    gpu_solver(ok).close()
+
+
+def test_end_to_end_tool(tmp_path):
+    """recording -> tools/calibrate_group.py -> april_group.json -> PoseDetector: every frame of the clip passes the 2 px gate with the
+    calibrated model, not with the nominal one it started from (tags cs.E2E_PERTURB_DEG degrees off)"""
+    import logging
+    from accurate_aprilgroup_tracking_amd import formats, group_calib
+    from accurate_aprilgroup_tracking_amd.pose_detector import PoseDetector
+    sc = cs.e2e_scene()
+    formats.save_detections(tmp_path / "rec.npz", sc.frames)
+    formats.save_camera_params(tmp_path / "CameraParams.npz", sc.K, np.zeros(5))
+    formats.save_april_group(tmp_path / "nominal.json", group_calib.poses_to_group(cs.e2e_nominal(sc), sc.tag_ids, sc.sizes))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "calibrate_group.py"), str(tmp_path / "rec.npz"), str(tmp_path / "CameraParams.npz"),
+                        "--init", str(tmp_path / "nominal.json"), "-o", str(tmp_path / "april_group.json")], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and "final RMS" in r.stdout
+    model = formats.load_april_group(tmp_path / "april_group.json")
+    assert sorted(model) == sc.tag_ids
+    log = logging.getLogger("calib"); log.setLevel(logging.CRITICAL)
+    accepted = {}
+    for name in ("april_group.json", "nominal.json"):
+        det = PoseDetector.from_files(log, tmp_path / "CameraParams.npz", True, detector=tmp_path / "rec.npz", april_group=tmp_path / name)
+        ok = []
+        for _ in sc.frames:
+            il, ol, _ = det._obtain_detections(None)
+            det._estimate_pose(il, ol)
+            ok.append(det.last_error is not None and det.last_error < det.ERROR_GATE_PX)
+        accepted[name] = ok
+    print("accepted frames: calibrated %d / %d, nominal %d / %d" % (sum(accepted["april_group.json"]), len(sc.frames), sum(accepted["nominal.json"]), len(sc.frames)))
+    assert all(accepted["april_group.json"])
+    assert not all(accepted["nominal.json"])
