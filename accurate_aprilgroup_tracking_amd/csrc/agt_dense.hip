@@ -68,12 +68,13 @@ __global__ __launch_bounds__(256) void dense_accum_kernel(const DenseParams P)
     DSTAMP(0);
     const int smp = blockIdx.x * 256 + tid;
     // (branch-free: behind a branch the compiler waits for the loads at the join.  Indices are clamped, pointers selected per block,
-    // a block without a mask reads a byte it ignores.)
+    // a block without a mask reads a byte it ignores -- of the point it loads anyway: the model pointers are null in a
+    // corners-only call, M == 0.)
     const int si = smp < P.M ? smp : P.M - 1, ci = tid < P.N ? tid : (P.N > 0 ? P.N - 1 : 0);
     const float* p3 = geo ? P.obj + ci * 3 : P.mxyz + (long)si * 3;
     const float* p2 = geo ? P.ipts + ((long)b * P.N + ci) * 2 : P.mt + si;
     const bool masked = geo && P.mask != nullptr;
-    const uint8_t* pm = masked ? P.mask + (long)b * P.N + ci : reinterpret_cast<const uint8_t*>(P.mt);
+    const uint8_t* pm = masked ? P.mask + (long)b * P.N + ci : reinterpret_cast<const uint8_t*>(p3);
     float sX = p3[0], sY = p3[1], sZ = p3[2];
     const float f0 = p2[0], f1 = p2[geo ? 1 : 0];
     const uint8_t mb = *pm;

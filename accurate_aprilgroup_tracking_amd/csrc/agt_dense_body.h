@@ -53,6 +53,8 @@ __device__ __forceinline__ bool dense_update(const DenseParams& P, DenseShared& 
 #pragma unroll
             for (int u = 0; u < 32; u++) s += v[u];
         }
+        // (a corners-only call, M == 0, has no photometric row: the loop above never tests the word)
+        if (P.nblk == 0 && done_v) return true;
         DSTAMP(8);
         sh.rows8[g][k] = s;
         if (g == 0) sh.geo[k] = geo;

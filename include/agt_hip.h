@@ -473,7 +473,8 @@ int agt_preprocess_bgr(agt_ctx* ctx, const uint8_t* d_bgr, size_t spitch, size_t
  * Gauss-Newton (mu = 1e-3), `iters` iterations at most, early stop at relative step < FLT_EPSILON.
  * d_img: B gray u8 frames (w x h).  d_model_xyz [M][3] f32 / d_model_t [M] f32: model samples and
  * template intensities (shared by the B streams).  d_obj [N][3] f32, d_img_pts [B][N][2] f32,
- * d_mask [B][N] u8 or NULL: corner term (N may be 0).  d_pose [B][6] f64 in/out.
+ * d_mask [B][N] u8 or NULL: corner term (N may be 0; so may M, with NULL model arrays: corners only;
+ * M + N > 0).  d_pose [B][6] f64 in/out.
  * d_stats [B][8] f64: photometric RMS, geometric RMS, valid samples, iterations run, corners used. */
 int agt_dense_refine(agt_ctx* ctx, const uint8_t* d_img, size_t pitch, size_t batch_stride, int w, int h,
                      const float* d_model_xyz, const float* d_model_t, int M,
