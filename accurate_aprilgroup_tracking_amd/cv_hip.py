@@ -712,3 +712,11 @@ def calibrateAprilGroup(frames, tagSizes, cameraMatrix, distCoeffs, initGroup=No
     include/agt_calib.h): -> (april_group dict, rvecs (F,3), tvecs (F,3), report)."""
     from . import group_calib
     return group_calib.calibrate_group(frames, tagSizes, cameraMatrix, distCoeffs, init_group=initGroup, anchor=anchor, max_iters=maxIters, **kwargs)
+
+
+def buildDenseModel(frames, rvecs, tvecs, group, cameraMatrix, distCoeffs=None, use=None, **kwargs):
+    """The dense model's template learned from a recording with known poses (no cv2 counterpart; dense_model.build_dense_model,
+    include/agt_model.h): frames (F, H, W) u8, rvecs / tvecs (F, 3) -> dense_model.DenseModel."""
+    from . import dense_model
+    poses = np.concatenate([np.asarray(rvecs, np.float64).reshape(-1, 3), np.asarray(tvecs, np.float64).reshape(-1, 3)], axis=1)
+    return dense_model.build_dense_model(frames, poses, group, cameraMatrix, distCoeffs, use=use, **kwargs)

@@ -183,3 +183,30 @@ def detections_to_corner_table(detections, tag_ids, decision_margin=DECISION_MAR
         corners[4 * i:4 * i + 4] = np.asarray(d.corners, np.float64).reshape(4, 2)
         mask[4 * i:4 * i + 4] = 1
     return corners, mask, int(mask.sum()) // 4
+
+
+# ------------------------------------------------------------------ dense model (.npz)
+_DENSE_MODEL_FORMAT = 1
+
+
+def save_dense_model(path, model):
+    """One .npz with the arrays of a dense_model.DenseModel and its settings as plain numbers (keys `set_<name>`); nothing else."""
+    arrays = {k: getattr(model, k) for k in model.FIELDS}
+    for k, v in model.settings.items():
+        arrays["set_" + k] = np.asarray(v)
+    arrays["format"] = np.int64(_DENSE_MODEL_FORMAT)
+    with open(path, "wb") as f:               # (a file object: np.savez would append .npz to a name without it)
+        np.savez(f, **arrays)
+
+
+def load_dense_model(path):
+    """-> dense_model.DenseModel; arrays and settings come back bitwise"""
+    from .dense_model import DenseModel
+    with np.load(path, allow_pickle=False) as f:
+        missing = [k for k in DenseModel.FIELDS + ("format",) if k not in f.files]
+        if missing:
+            raise ValueError("%s: missing key(s) %s" % (path, ", ".join(missing)))
+        if int(f["format"]) != _DENSE_MODEL_FORMAT:
+            raise ValueError("%s: dense model format %d, %d expected" % (path, int(f["format"]), _DENSE_MODEL_FORMAT))
+        settings = {k[4:]: f[k][()].item() for k in f.files if k.startswith("set_")}
+        return DenseModel(*[f[k] for k in DenseModel.FIELDS], settings=settings)

@@ -191,6 +191,19 @@ class StreamTracker:
                                              float(photo_weight), int(bool(reseed))), "agt_tracker_dense")
         self._dense = (model_xyz, model_t)
 
+    def load_dense_model(self, model_or_path, iters=5, photo_weight=0.05, reseed=True):
+        """Register a dense model learned from a recording (dense_model.build_dense_model, tools/build_dense_model.py): a
+        dense_model.DenseModel or the .npz formats.save_dense_model wrote.  Its usable samples are uploaded and handed to
+        dense_model().  -> the compacted DenseModel"""
+        from . import dense_model as DM, formats
+        model = model_or_path if isinstance(model_or_path, DM.DenseModel) else formats.load_dense_model(model_or_path)
+        model = model.compact()
+        if model.model_xyz.shape[0] == 0:
+            raise ValueError("StreamTracker.load_dense_model: the model has no usable sample")
+        self.dense_model(torch.from_numpy(model.model_xyz).to(self.dev), torch.from_numpy(model.model_t).to(self.dev), iters=iters,
+                         photo_weight=photo_weight, reseed=reseed)
+        return model
+
     def step_dense(self, frames, state_out=None, dense_out=None):
         """One frame with the dense stage: pyramid -> LK -> solvePnP(guess) + gate + motion model -> dense refinement of the
         accepted pose (-> corner re-seed).  dense_out: cuda f64 [B, DENSE_STRIDE] (created when None).  Enqueues only."""
