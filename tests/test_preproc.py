@@ -1,24 +1,15 @@
 """Frame pre-processing (detect_pose.py:147-183 undistort_frame, :602 cvtColor).
 CPU: oracle self-checks + the host-only getOptimalNewCameraMatrix of the C ABI vs the oracle.
-GPU: maps, cv.undistort, and the fused undistort+gray+crop kernel, all BIT-EXACT vs the oracle."""
+GPU: maps, cv.undistort, and the fused undistort+gray+crop kernel, all BIT-EXACT vs the oracle.
+The numpy statement lives in tests/preproc_numpy.py; the edge scenes are tests/preproc_scenes.py + tests/test_preproc_edges.py."""
 import numpy as np
 import pytest
 
 from accurate_aprilgroup_tracking_amd import synthetic as syn
+from preproc_numpy import remap as _numpy_remap, undistort_maps as _numpy_undistort_maps
+from preproc_scenes import TILTED_DIST, bgr as _bgr
 
 DISTS = [np.array([[-0.25, 0.1, 1e-3, -5e-4, -0.02]]), syn.MILD_DIST, np.array([[0.1, -0.05, 0.0, 0.0]]), None]
-
-
-# the full 14-coefficient model: rational radial, tangential, thin prism and a TILTED sensor (tau_x, tau_y in radians)
-TILTED_DIST = np.array([[0.05, -0.02, 1e-3, 2e-3, 0.01, 0.02, -0.01, 0.005, 1e-3, -2e-3, 5e-4, 1e-3, 0.03, -0.02]])
-
-
-def _bgr(h, w, seed):
-    rng = np.random.default_rng(seed)
-    from scipy.ndimage import gaussian_filter
-    img = np.stack([gaussian_filter(rng.standard_normal((h, w)), 1.2) for _ in range(3)], axis=-1)
-    img = (img - img.min()) / (img.max() - img.min()) * 255
-    return img.astype(np.uint8)
 
 
 def test_oracle_preproc_self_checks(oracle):
@@ -41,51 +32,6 @@ def test_oracle_preproc_self_checks(oracle):
     # alpha = 0 keeps only valid pixels: the whole new image is the ROI (up to the 1-px rounding OpenCV has)
     nk0, roi0 = oracle.getOptimalNewCameraMatrix(K, DISTS[0], (640, 480), 0, (640, 480))
     assert roi0[2] >= 638 and roi0[3] >= 478
-
-
-def _numpy_undistort_maps(K, dist, newK, w, h):
-    """cv::initUndistortRectifyMap(K, dist, I, newK, (w, h), CV_16SC2), vectorised (written from OpenCV's documented model:
-    inverse new camera matrix -> normalised point -> Brown-Conrady + thin prism -> pixel -> 1/32-pixel fixed point)"""
-    k = np.zeros(14)
-    if dist is not None:
-        d = np.asarray(dist, np.float64).reshape(-1); k[:d.size] = d
-    ir = np.linalg.inv(np.asarray(newK, np.float64))
-    j, i = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
-    _x = j * ir[0, 0] + (i * ir[0, 1] + ir[0, 2]); _y = j * ir[1, 0] + (i * ir[1, 1] + ir[1, 2]); _w = j * ir[2, 0] + (i * ir[2, 1] + ir[2, 2])
-    x, y = _x * (1.0 / _w), _y * (1.0 / _w)
-    x2, y2 = x * x, y * y
-    r2, _2xy = x2 + y2, 2 * x * y
-    kr = (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2) / (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2)
-    xd = x * kr + k[2] * _2xy + k[3] * (r2 + 2 * x2) + k[8] * r2 + k[9] * r2 * r2
-    yd = y * kr + k[2] * (r2 + 2 * y2) + k[3] * _2xy + k[10] * r2 + k[11] * r2 * r2
-    if k[12] != 0 or k[13] != 0:        # tilted sensor (tests/pnp_numpy.py tilt_matrix)
-        from tests.pnp_numpy import tilt_matrix
-        T = tilt_matrix(k[12], k[13])
-        hx, hy, hw = (T[q, 0] * xd + T[q, 1] * yd + T[q, 2] for q in range(3))
-        xd, yd = hx / hw, hy / hw
-    iu = np.rint((K[0, 0] * xd + K[0, 2]) * 32).astype(np.int64); iv = np.rint((K[1, 1] * yd + K[1, 2]) * 32).astype(np.int64)
-    m1 = np.stack([iu >> 5, iv >> 5], axis=-1).astype(np.int16)
-    m2 = ((iv & 31) * 32 + (iu & 31)).astype(np.uint16)
-    return m1, m2
-
-
-def _numpy_remap(src, m1, m2):
-    """cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) with CV_16SC2 maps on 8-bit images: 15-bit weights from the 5-bit fractions"""
-    h, w = src.shape[:2]
-    sx, sy = m1[..., 0].astype(np.int64), m1[..., 1].astype(np.int64)
-    fx, fy = (m2 & 31).astype(np.int64), (m2 >> 5).astype(np.int64)
-    pad = np.zeros((h + 2, w + 2) + src.shape[2:], np.int64); pad[1:-1, 1:-1] = src
-
-    def tap(dy, dx):
-        yy, xx = sy + dy, sx + dx
-        ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
-        v = pad[np.clip(yy, -1, h) + 1, np.clip(xx, -1, w) + 1]
-        return np.where(ok[..., None] if src.ndim == 3 else ok, v, 0)
-    ws = [(32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32]
-    if src.ndim == 3:
-        ws = [x[..., None] for x in ws]
-    acc = tap(0, 0) * ws[0] + tap(0, 1) * ws[1] + tap(1, 0) * ws[2] + tap(1, 1) * ws[3]
-    return ((acc + (1 << 14)) >> 15).astype(np.uint8)
 
 
 def test_oracle_maps_and_remap_equal_numpy_statement(oracle):
