@@ -14,9 +14,13 @@
 //     and wave w finishes level w -- three barriers per frame instead of nine;
 //   * the level loop is unrolled (per-level quantities are plain registers), the iteration makes one vector -> scalar decision,
 //     its sums cross the waves as int32 hi / lo pairs;
-//   * the result is stored at once (device-scope stores when the PnP role of the same launch waits for it) and counted into
-//     the arrival counter one frame later, under the next frame's image-side work.
-// Measured on production code with fixed iteration counts: 5.8 us per frame + 0.62 us per iteration (profiles/r02_summary.md).
+//   * the result is stored (device-scope stores when the PnP role of the same launch waits for it) and counted into the
+//     arrival counter one frame later, both under the next frame's image-side work: the stores behind its Scharr barrier, the
+//     arrival two barriers on (stores count in vmcnt: issued at the frame's end, their acknowledgement was waited for by the
+//     hand-over's wait for the prefetched tiles);
+//   * the 2 x 2 systems of all levels are read once behind the reduction's barrier, with one crossing to the scalar unit.
+// Measured on production code with fixed iteration counts: 5.8 us per frame + 0.62 us per iteration (profiles/r02_summary.md);
+// 5.45 us since the last two items (profiles/lk_frame_fixed.md).
 // Only what the tracker uses is covered: flags == 0, no error output (lk_role keeps lk_body otherwise); the frames of a group
 // share their geometry, the image before the group may differ in pitch.  A one-frame group is fine: its image-(k-1) tiles are
 // loaded on demand like the first frame's of any group.
@@ -63,8 +67,8 @@ struct ChainCfg {
     static constexpr int OFF_SD = 2 * NLEV * TILE;
     static constexpr int OFF_SLOTS = OFF_SD + NLEV * SD;                // iteration sums: three rotating int4 accumulators (256 B reserved)
     static constexpr int OFF_RED = OFF_SLOTS + 2 * 4 * 4 * 8;           // covariance partials: [3 * NLEV][256 threads] int
-    static constexpr int OFF_LVL = OFF_RED + 3 * NLEV * 256 * 4;        // per level: A11, A12, A22, 1 / det, usable (8 floats)
-    static constexpr int BYTES = OFF_LVL + NLEV * 8 * 4;
+    static constexpr int OFF_LVL = OFF_RED + 3 * NLEV * 256 * 4;        // per level: A11, A12, A22, 1 / det (0: level not usable)
+    static constexpr int BYTES = OFF_LVL + NLEV * 4 * 4;
     static_assert(TILE % 16 == 0 && SD % 16 == 0, "16-byte aligned LDS sections");
 };
 
@@ -221,6 +225,14 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
     int jox[NLEV], joy[NLEV], sox[NLEV], soy[NLEV];        // tile origins (x as requested, the stored tile starts at x & ~3)
     int jmask = 0, smask = 0;                  // levels whose tile in buf[cur] / buf[cur ^ 1] is valid
     unsigned* owed = nullptr;                  // arrival counter of the previous frame, not yet counted into (see the frame's end)
+    float* owed_pts = nullptr;                 // ... and where its result (px, py, pst) is still to be stored
+    uint8_t* owed_status = nullptr;
+    // (thread 0 only) the owed result goes out: device-scope stores; lk_arrive follows once their acknowledgement has had time
+    auto owed_stores = [&]() {
+        LkFrameIo<NLEV> o;
+        o.next_pts = owed_pts; o.status = owed_status;
+        lk_publish_stores(o, pidx, px, py, pst);
+    };
 #pragma unroll
     for (int l = 0; l < NLEV; l++) { jox[l] = joy[l] = sox[l] = soy[l] = 0; }
 
@@ -228,7 +240,7 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
         if (k) lds_barrier();                  // everyone is done with the previous frame's LDS; the table copy is visible
         const LkFrameIo<NLEV> io = frame(k);
         if (io.bad) {                          // the frame's table entries cannot be addresses: the group ends here for this corner (uniform over
-            if (tid == 0 && owed) lk_arrive(owed, b);      // the workgroup); whoever waits for its frames gives up and reports (agt_step.hip)
+            if (tid == 0 && owed) { owed_stores(); lk_arrive(owed, b); }      // the workgroup); whoever waits for its frames gives up and reports (agt_step.hip)
             return;
         }
         if (k == 0) {
@@ -246,7 +258,7 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
         CSTAMP(0);
         if (!pst) {                            // sticky: a lost corner stays lost, position carried (see lk_body)
             if (tid == 0) {
-                if (owed) lk_arrive(owed, b);
+                if (owed) { owed_stores(); lk_arrive(owed, b); }
                 lk_publish(io, pidx, b, px, py, 0, 0.f);
             }
             owed = nullptr;
@@ -346,6 +358,11 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             if (sv) *reinterpret_cast<int2*>(sDall + l * (K::SD / 4) + sY * DW + sX) = make_int2(val[0], val[1]);
         }
         lds_barrier();
+        // The previous frame's result is stored HERE, not at that frame's end: a write-through store is acknowledged after ~0.8 us and
+        // is counted in vmcnt like a load, so every wait for loads between the stores and their acknowledgement stands still for it --
+        // the hand-over's wait for the prefetched tiles did, and so did the frame head's.  From here to lk_arrive two barriers below
+        // (~1.4 us of LDS-only work) nothing waits for vector memory; whoever reads the result waits for the arrival, which has not moved.
+        CREPS(6) if (owed && tid == 0) owed_stores();
         CSTAMP(3);
 
         // ---- interpolated patch of every level (registers) + this thread's share of the covariance sums
@@ -391,12 +408,27 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             const float minEig = (A[2] + A[0] - sqrtf((A[0] - A[2]) * (A[0] - A[2]) + 4.f * A[1] * A[1])) / (float)(2 * WIN * WIN);
             const bool ok = ((lvA >> l) & 1) && !lk_flat(minEig, D, min_eig_threshold);
             if (lane == 0) {
-                float* o = lvl + l * 8;
-                o[0] = A[0]; o[1] = A[1]; o[2] = A[2]; o[3] = ok ? 1.f / D : 0.f; o[4] = ok ? 1.f : 0.f;
+                // (a usable level has det >= FLT_EPSILON, and det < 2^26 -- |A| <= 441 * 4080^2 / 2^20 < 2^13 --, so its 1 / det is
+                // neither 0 nor infinite: the word doubles as the level's flag; a NaN stays a NaN and stays usable, as in OpenCV)
+                *reinterpret_cast<float4*>(lvl + l * 4) = make_float4(A[0], A[1], A[2], ok ? 1.f / D : 0.f);
             }
         }
         lds_barrier();
-        // the previous frame's result was stored ~3 us ago: its stores have long been acknowledged, count the corner in now
+        // every level's system in ONE LDS round trip and one crossing to the scalar unit, here, under the arrival's bookkeeping: read at
+        // the levels' entries they were two dependent round trips (flag, branch, system) and a crossing per level on the chain.
+        // (more than three levels: made scalars at once -- as 24 vector registers the words take lk_group_kernel<21, 4, 6, 1> past 256
+        // registers and its second workgroup per CU; three levels: made scalars at each level's entry, which measured 1 % faster on c2)
+        float4 lv[NLEV];
+        float lv11[NLEV], lv12[NLEV], lv22[NLEV], lvD[NLEV];
+        int lvOK = 0;
+#pragma unroll
+        for (int l = 0; l < NLEV; l++) {
+            lv[l] = *reinterpret_cast<const float4*>(lvl + l * 4);
+            lvOK |= lv[l].w != 0.f ? 1 << l : 0;
+            if constexpr (NLEV > 3) { lv11[l] = agt_uniform(lv[l].x); lv12[l] = agt_uniform(lv[l].y); lv22[l] = agt_uniform(lv[l].z); lvD[l] = agt_uniform(lv[l].w); }
+        }
+        lvOK = agt_uniform(lvOK) & lvA;
+        // the previous frame's result was stored two barriers ago: its stores have been acknowledged, count the corner in now
         if (owed && tid == 0) lk_arrive(owed, b);
         owed = nullptr;
         CSTAMP(4);
@@ -451,15 +483,15 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
                     pre = true;
                 }
             }
-            if (!((lvA >> level) & 1)) { if (level == 0) st = 0; continue; }
-            const float4 lv4 = *reinterpret_cast<const float4*>(lvl + level * 8);
-            if (!agt_uniform((int)(lvl[level * 8 + 4] != 0.f))) { if (level == 0) st = 0; continue; }
+            if (!((lvOK >> level) & 1)) { if (level == 0) st = 0; continue; }
             // (`level` is a compile-time constant here: plain indexing, no selects)
             AgtLevel LJ;
             LJ.ptr = nullptr; LJ.w = gw[level]; LJ.h = gh[level]; LJ.pitch = gpitch[level]; LJ.bstride = gbs[level];
             const uint8_t* imgJ = io.imgJ[level] + (long)b * LJ.bstride;
             uint8_t* sJ = lds + (cur * NLEV + level) * K::TILE;
-            const float a11 = agt_uniform(lv4.x), a12 = agt_uniform(lv4.y), a22 = agt_uniform(lv4.z), D = agt_uniform(lv4.w);
+            const float4 lv4 = lv[level];
+            const float a11 = NLEV > 3 ? lv11[level] : agt_uniform(lv4.x), a12 = NLEV > 3 ? lv12[level] : agt_uniform(lv4.y);
+            const float a22 = NLEV > 3 ? lv22[level] : agt_uniform(lv4.z), D = NLEV > 3 ? lvD[level] : agt_uniform(lv4.w);
             int iv[C::NPX], ix[C::NPX], iy[C::NPX];
 #pragma unroll
             for (int q = 0; q < C::NPX; q++) { iv[q] = Iv[level][q]; ix[q] = Ix[level][q]; iy[q] = Iy[level][q]; }
@@ -541,12 +573,11 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             CSTAMP(9 + level * 2);
         }
         CSTAMP(5);
-        // the result: stores now; the arrival is counted after their acknowledgement -- at once for the last frame of the group
-        // (its pose solve is the launch's tail), otherwise under the next frame's image-side work
+        // the result: stored and counted at once for the last frame of the group (its pose solve is the launch's tail), otherwise
+        // both are owed to the next frame's image-side work (px, py, pst carry the values)
         if (io.done) {
-            CREPS(6) if (tid == 0) lk_publish_stores(io, pidx, outx, outy, st);
-            if (k + 1 < nf) owed = io.done;
-            else if (tid == 0) lk_arrive(io.done, b);
+            if (k + 1 < nf) { owed = io.done; owed_pts = io.next_pts; owed_status = io.status; }
+            else if (tid == 0) { lk_publish_stores(io, pidx, outx, outy, st); lk_arrive(io.done, b); }
         } else if (tid == 0) lk_publish(io, pidx, b, outx, outy, st, 0.f);
 
         // ---- hand-over: image k's search tiles become the next frame's previous-image tiles; the requested tiles of image
