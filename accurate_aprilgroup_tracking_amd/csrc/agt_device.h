@@ -441,7 +441,15 @@ __device__ inline void agt_rodrigues_inv(const double Rin[9], double r[3])
     double s = agt_sqrtp((rx * rx + ry * ry + rz * rz) * 0.25);
     double c = (R[0] + R[4] + R[8] - 1) * 0.5;
     c = c > 1.0 ? 1.0 : c < -1.0 ? -1.0 : c;
+    // OpenCV's acos(c) loses eps / sin(theta) -- 5e-12 of a 2e-5 rad rotation, 1.5e-8 when the last bit of c decides between -1 and its
+    // neighbour -- so below sin(theta) = 1/4 the angle comes from s instead, which is the well-conditioned one of the two there: within
+    // 4 eps everywhere (tests/test_gpu_pose_range.py).  acos stays unconditional: it does not wait for s, and the usual rotation of a
+    // tracked body takes no other path than before.  (atan2(s, c) costs the fused step's kernel registers it does not have.)
     double theta = acos(c);
+    if (s < 0.25) {
+        const double a = asin(s);
+        theta = c < 0.0 ? 3.14159265358979323846 - a : a;
+    }
     if (s < 1e-5) {
         if (c > 0) rx = ry = rz = 0;
         else {
@@ -453,10 +461,30 @@ __device__ inline void agt_rodrigues_inv(const double Rin[9], double r[3])
             theta /= sqrt(rx * rx + ry * ry + rz * rz);
             rx *= theta; ry *= theta; rz *= theta;
         }
-    } else {
+    } else if (c >= 0.0) {
         double vth = agt_rcp(2 * s);      // (s >= 1e-5 here)
         vth *= theta;
         rx *= vth; ry *= vth; rz *= vth;
+    } else {
+        // Beyond a quarter turn the antisymmetric part, 2 sin(theta) a, fades (the axis it gives is off by eps / (2 sin theta): 1e-11 of
+        // the vector at s = 1e-5) while the symmetric part, (R + R^T) / 2 = c I + (1 - c) a a^T, holds the axis at full precision
+        // (1 - c > 1): its largest diagonal entry gives |a_i| >= 1 / sqrt(3), the antisymmetric part that component's sign (sin theta
+        // > 0), row i the other two.  Same rotation vector as OpenCV's formula to the 1e-11 above.
+        const double ic = agt_rcp(1.0 - c);
+        const double d0 = (R[0] - c) * ic, d1 = (R[4] - c) * ic, d2 = (R[8] - c) * ic;
+        const double s01 = 0.5 * (R[1] + R[3]) * ic, s02 = 0.5 * (R[2] + R[6]) * ic, s12 = 0.5 * (R[5] + R[7]) * ic;     // a_i a_j
+        // (selects, not three bodies: the pivot is data, and branches here cost the callers registers)
+        const bool p0 = d0 >= d1 && d0 >= d2, p1 = !p0 && d1 >= d2;
+        const double dm = p0 ? d0 : p1 ? d1 : d2, vm = p0 ? rx : p1 ? ry : rz;
+        double am = agt_sqrtp(dm);
+        am = vm < 0.0 ? -am : am;
+        const double ia = agt_rcp(am);
+        const double ax = p0 ? am : (p1 ? s01 : s02) * ia;
+        const double ay = p1 ? am : (p0 ? s01 : s12) * ia;
+        const double az = (p0 || p1) ? (p0 ? s02 : s12) * ia : am;
+        // (unit length restored: the three come from different entries)
+        const double nrm = theta * agt_rcp(agt_sqrtp(ax * ax + ay * ay + az * az));
+        rx = ax * nrm; ry = ay * nrm; rz = az * nrm;
     }
     r[0] = rx; r[1] = ry; r[2] = rz;
 }

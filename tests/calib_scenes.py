@@ -32,8 +32,8 @@ def perturb(pose, angle_deg, shift, rng):
 
 class Scene:
     def __init__(self, n_tags, n_frames, seed=0, dist=None, noise=0.0, keep=None, max_view_deg=70.0, max_polar_deg=46.0, swing=1.0,
-                 width=1280, height=720, tag_size=0.020):
-        self.group = synthetic.make_april_group(n_tags=n_tags, tag_size=tag_size, max_polar_deg=max_polar_deg, seed=seed)
+                 width=1280, height=720, tag_size=0.020, group=None, two_sided=False):
+        self.group = group if group is not None else synthetic.make_april_group(n_tags=n_tags, tag_size=tag_size, max_polar_deg=max_polar_deg, seed=seed)
         self.tag_ids = [int(k) for k in self.group["tags"]]
         self.sizes = np.array([self.group["tags"][str(t)]["size"] for t in self.tag_ids])
         self.K = synthetic.camera_matrix(width, height)
@@ -58,7 +58,8 @@ class Scene:
                 Rt = Rotation.from_rotvec(self.tag_poses[i, :3]).as_matrix()
                 centre = Rf @ self.tag_poses[i, 3:] + tv[f]
                 normal = Rf @ Rt[:, 2]
-                facing = -(normal @ centre) / np.linalg.norm(centre) > cos_max and centre[2] > 0
+                cos_view = -(normal @ centre) / np.linalg.norm(centre)
+                facing = (abs(cos_view) if two_sided else cos_view) > cos_max and centre[2] > 0
                 if not facing or (keep is not None and not keep[f][i]):
                     continue
                 X = ba.corners3d(self.sizes[i]) @ Rt.T + self.tag_poses[i, 3:]
@@ -135,6 +136,32 @@ def recovery_scene():
 def noisy_scene(n_frames=40, seed=13, noise=0.2):
     """T = 12, F = 40, sigma = 0.2 px"""
     return Scene(12, n_frames, seed=seed, noise=noise, max_view_deg=60.0, max_polar_deg=60.0)
+
+
+FLAT_ANCHOR = 4
+
+
+def flat_board_scene():
+    """T = 9, F = 5: a 3 x 3 grid of tags in one plane, 30 mm apart, every tag's rvec exactly 0; tag 4, the anchor, is the origin"""
+    tags = {str(3 * i + j): {"size": 0.020, "extrinsics": [0.03 * (j - 1), 0.03 * (i - 1), 0.0, 0.0, 0.0, 0.0]} for i in range(3) for j in range(3)}
+    # (rvec = 0 turns the tags' +z away from the camera of synthetic.trajectory: the board is seen from behind, which the geometry allows)
+    sc = Scene(9, 5, seed=9, max_view_deg=89.0, swing=0.3, group={"tags": tags}, two_sided=True)
+    assert not sc.tag_poses[:, :3].any() and not sc.tag_poses[FLAT_ANCHOR].any()
+    return sc
+
+
+def flat_start(sc, seed=1):
+    """the truth with every tag but the anchor SHIFTED by 1 mm (the rotation vectors stay exactly 0) and every frame pose moved by
+    0.5 degree and 1 mm"""
+    rng = np.random.default_rng(seed)
+    tp = sc.tag_poses.copy()
+    for i in range(len(tp)):
+        if i != FLAT_ANCHOR:
+            sh = rng.standard_normal(3)
+            tp[i, 3:] += 1e-3 * sh / np.linalg.norm(sh)
+    fp = np.array([perturb(q, 0.5, 1e-3, rng) for q in sc.frame_poses])
+    assert not tp[:, :3].any()
+    return tp, fp
 
 
 def perturbed_start(sc, seed=1, frames=True):

@@ -37,9 +37,9 @@ def gpu_solver(prob, order=None):
                                prob["corners"][o])
 
 
-def check_eval(sc):
-    prob = sc.problem(0)
-    tp, fp = cs.perturbed_start(sc)
+def check_eval(sc, anchor=0, start=cs.perturbed_start):
+    prob = sc.problem(anchor)
+    tp, fp = start(sc)
     want = ba.residuals(prob, tp, fp)
     # the table goes in shuffled: the library sorts by frame and answers in the caller's order
     order = np.random.default_rng(0).permutation(len(want))
@@ -52,9 +52,9 @@ def check_eval(sc):
     assert abs(cost - 0.5 * (want * want).sum()) <= 1e-9 * np.abs(want).sum()
 
 
-def check_step(sc):
-    prob = sc.problem(0)
-    tp, fp = cs.perturbed_start(sc)
+def check_step(sc, anchor=0, start=cs.perturbed_start):
+    prob = sc.problem(anchor)
+    tp, fp = start(sc)
     dense = {lam: ba.dense_step(prob, tp, fp, lam) for lam in LAMBDAS}
     floor = max(ba.step_difference(ba.schur_step(prob, tp, fp, lam), dense[lam]) for lam in LAMBDAS)
     s = gpu_solver(prob)
@@ -92,6 +92,15 @@ def test_smallest_system():
     sc = SCENES["smallest"]()
     check_eval(sc)
     check_step(sc)
+
+
+def test_flat_board_anchor_4():
+    """T = 9, F = 5, a 3 x 3 grid in one plane: every free tag's rotation vector is exactly 0 in the truth and in the start, so the
+    tag block of the accumulation takes agt_rodrigues' identity branch (theta < DBL_EPSILON: R = I, G = I); the anchor is tag 4"""
+    sc = cs.flat_board_scene()
+    assert sc.visible.all() and sc.connected(cs.FLAT_ANCHOR)
+    check_eval(sc, cs.FLAT_ANCHOR, cs.flat_start)
+    check_step(sc, cs.FLAT_ANCHOR, cs.flat_start)
 
 
 def test_noise_free_recovery():

@@ -64,6 +64,12 @@ def test_scene_builders():
     for sc, want in [(cs.parity_scene(), [1, 5, 2, 3, 2, 2, 3]), (cs.wave_scene(), [2, 3, 2, 3, 17, 3, 2, 3, 2]), (cs.smallest_scene(), [2, 2, 2])]:
         assert sc.visible.sum(axis=1).tolist() == want and sc.connected(0)
     assert cs.parity_scene().visible[:, 4].sum() == 2
+    # the flat board: every tag in every frame, rotation vectors exactly 0 in the truth and in the start, the anchor (tag 4) the origin
+    sc = cs.flat_board_scene()
+    tp, fp = cs.flat_start(sc)
+    assert sc.visible.all() and sc.connected(cs.FLAT_ANCHOR) and not tp[:, :3].any() and not tp[cs.FLAT_ANCHOR].any()
+    assert np.abs(ba.residuals(sc.problem(cs.FLAT_ANCHOR), sc.tag_poses, sc.frame_poses)).max() < 1e-9
+    assert 0.1 < np.abs(ba.residuals(sc.problem(cs.FLAT_ANCHOR), tp, fp)).max() < 20.0
     for sc in (cs.recovery_scene(), cs.noisy_scene(48)):
         assert sc.connected(0)
         assert (sc.visible.sum(axis=1) >= 2).mean() > 0.9 and sc.visible.any(axis=0).all()
@@ -105,12 +111,13 @@ def test_numpy_jacobian_is_the_derivative():
                 assert np.abs(num - J[:, c + j]).max() < 1e-4 * max(1.0, np.abs(J[:, c + j]).max())
 
 
-@pytest.mark.parametrize("name", ["parity", "tilt", "wave", "smallest"])
+@pytest.mark.parametrize("name", ["parity", "tilt", "wave", "smallest", "flat"])
 def test_numpy_schur_step_equals_dense_step(name):
     """the difference measured here is the floor of the GPU step tolerance (tests/test_gpu_group_calib.py)"""
-    sc = {"parity": cs.parity_scene, "tilt": lambda: cs.parity_scene(cs.TILT14), "wave": cs.wave_scene, "smallest": cs.smallest_scene}[name]()
-    prob = sc.problem(0)
-    tp, fp = cs.perturbed_start(sc)
+    sc = {"parity": cs.parity_scene, "tilt": lambda: cs.parity_scene(cs.TILT14), "wave": cs.wave_scene, "smallest": cs.smallest_scene,
+          "flat": cs.flat_board_scene}[name]()
+    prob = sc.problem(cs.FLAT_ANCHOR if name == "flat" else 0)
+    tp, fp = cs.flat_start(sc) if name == "flat" else cs.perturbed_start(sc)
     for lam in (0.0, 1e-3, 10.0):
         d = ba.step_difference(ba.schur_step(prob, tp, fp, lam), ba.dense_step(prob, tp, fp, lam))
         print("%s lambda %g: |schur - dense| / |dense| = %.3g" % (name, lam, d))
