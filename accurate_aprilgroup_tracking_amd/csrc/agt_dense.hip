@@ -53,11 +53,7 @@ __global__ __launch_bounds__(256) void dense_accum_kernel(const DenseParams P)
     if ((int)blockIdx.x > P.nblk) {
         // next frame's pyramid tile (only in launches that carry the job; independent of the done word)
         const int tile = (int)blockIdx.x - P.nblk - 1;
-        if (tile < P.n_pyr) {
-            const int by = tile / P.py0.gx, bx = tile - by * P.py0.gx;
-            agt_pyr2::pyr_down2_body(P.py0, P.py1, bx, by, P.py0.src + (long)b * P.py0.sbatch, P.py0.dst + (long)b * P.py0.dbatch,
-                                     P.py1.dst + (long)b * P.py1.dbatch, lds_raw);
-        }
+        if (tile < P.n_pyr) agt_pyr2::pyr2_tile_of_stream(P.py0, P.py1, b, tile, lds_raw);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

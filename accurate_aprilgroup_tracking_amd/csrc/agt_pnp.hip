@@ -30,9 +30,8 @@ __global__ __launch_bounds__(AGT_WAVE * COOP_WAVES) void pnp_coop_kernel(const A
     __shared__ agt_pnp::PnpShared sh;
     if ((int)blockIdx.x >= n_solve) {
         const int t = (int)blockIdx.x - n_solve;
-        const int st = t / n_pyr, tile = t - st * n_pyr;
-        const int by = tile / Y0.gx, bx = tile - by * Y0.gx;
-        agt_pyr2::pyr_down2_body(Y0, Y1, bx, by, Y0.src + (long)st * Y0.sbatch, Y0.dst + (long)st * Y0.dbatch, Y1.dst + (long)st * Y1.dbatch, tile_lds);
+        const int st = t / n_pyr;
+        agt_pyr2::pyr2_tile_of_stream(Y0, Y1, st, t - st * n_pyr, tile_lds);
         return;
     }
     const int b = blockIdx.x;

@@ -39,10 +39,8 @@ __global__ __launch_bounds__(agt_pyr::NT) void pyr_down2_kernel(const AgtPyrArgs
     const int t = agt_xcd_order((int)blockIdx.x, (int)gridDim.x, A0.xshift);
     const int per_img = A0.gx * A0.gy;
     if (t >= per_img * A0.B) return;
-    const int bz = t / per_img, r = t - bz * per_img;
-    const int by = r / A0.gx;
-    agt_pyr2::pyr_down2_body(A0, A1, r - by * A0.gx, by, A0.src + (long)bz * A0.sbatch, A0.dst + (long)bz * A0.dbatch,
-                             A1.dst + (long)bz * A1.dbatch, lds);
+    const int bz = t / per_img;
+    agt_pyr2::pyr2_tile_of_stream(A0, A1, bz, t - bz * per_img, lds);
 }
 
 // Fused upload (agt_track_host_frame): ONE gray frame read from pinned host memory (A0.src: its device address), level 0 copied to
@@ -72,16 +70,49 @@ void agt_pyr2_grid(int w2, int h2, int* gx, int* gy)
     *gy = (h2 + agt_pyr2::TH2 - 1) / agt_pyr2::TH2;
 }
 
+void agt_pyr_grid(int dw, int dh, int* gx, int* gy)
+{
+    *gx = (dw + agt_pyr::TW - 1) / agt_pyr::TW;
+    *gy = (dh + agt_pyr::TH - 1) / agt_pyr::TH;
+}
+
+// one pass's argument block from its source and destination level (the destination's size is implied: (w + 1) / 2) and B images:
+// tiled form, the grid left to the planner
+static void pyr_args(const AgtLevel& src, const AgtLevel& dst, int B, AgtPyrArgs& A)
+{
+    A.src = src.ptr; A.sw = src.w; A.sh = src.h; A.spitch = src.pitch; A.sbatch = src.bstride;
+    A.dst = const_cast<uint8_t*>(dst.ptr); A.dw = (src.w + 1) / 2; A.dh = (src.h + 1) / 2; A.dpitch = dst.pitch; A.dbatch = dst.bstride;
+    A.B = B; A.strip_rows = 0;
+    A.xshift = agt_chip_current().xshift; A.topdown = 0;
+}
+
+// "The register-rolling form can take this source and destination": 16-byte loads of whole groups, at least two of them per row,
+// 8-byte stores of level 1, buffer descriptors (32-bit sizes and offsets) over source and destination.  A: the pass (of a two-level
+// pass: its level 0 -> 1 block); src_align / dst_align: OR of every source / destination address of the launch.  What differs:
+//   min_h       8 for one level, 32 for two (neither figure has a measurement or a derivation on record: profiles/pyr_refactor.md)
+//   dst2_align  two levels: OR of the level-2 addresses, pitch and stride; 4 bytes -- a lane stores 4 level-2 pixels
+//   copy_align, cpitch  fused upload: level 0 is copied with 16-byte stores through a descriptor of sh * cpitch bytes
+static bool pyr_roll_ok(const AgtPyrArgs& A, uintptr_t src_align, uintptr_t dst_align, int min_h, uintptr_t dst2_align = 0,
+                        uintptr_t copy_align = 0, long cpitch = 0)
+{
+    return ((src_align | (uintptr_t)A.spitch | (uintptr_t)A.sbatch | (uintptr_t)A.sw | copy_align | (uintptr_t)cpitch) & 15) == 0 &&
+           ((dst_align | (uintptr_t)A.dpitch | (uintptr_t)A.dbatch) & 7) == 0 && (dst2_align & 3) == 0 &&
+           A.sw >= 32 && A.sh >= min_h && (long)A.sh * A.spitch < (1L << 31) && (long)A.sh * cpitch < (1L << 31) && (long)A.dh * A.dpitch < (1L << 31);
+}
+
+// the two-level pass in A[0], A[1] runs register-rolling with strips of `oh` level-2 rows (gx = workgroups per image, gy = 1), or
+// tiled (oh = 0: the tile grid of the pass); said in both blocks
+static void pyr2_set_form(AgtPyrArgs* A, int oh)
+{
+    if (oh) { A[0].gx = agt_pyr4::roll2_blocks(A[0].sw, A[1].dh, oh); A[0].gy = 1; }
+    else agt_pyr2_grid(A[1].dw, A[1].dh, &A[0].gx, &A[0].gy);
+    A[0].strip_rows = A[1].strip_rows = oh; A[1].gx = A[0].gx; A[1].gy = A[0].gy;
+}
+
 void agt_pyr2_args(const AgtLevel* lv, int B, AgtPyrArgs* A)
 {
-    for (int k = 0; k < 2; k++) {
-        A[k].src = lv[k].ptr; A[k].sw = lv[k].w; A[k].sh = lv[k].h; A[k].spitch = lv[k].pitch; A[k].sbatch = lv[k].bstride;
-        A[k].dst = const_cast<uint8_t*>(lv[k + 1].ptr); A[k].dw = (lv[k].w + 1) / 2; A[k].dh = (lv[k].h + 1) / 2; A[k].dpitch = lv[k + 1].pitch; A[k].dbatch = lv[k + 1].bstride;
-        A[k].B = B; A[k].strip_rows = 0;
-        A[k].xshift = agt_chip_current().xshift; A[k].topdown = 0;
-    }
-    agt_pyr2_grid(A[1].dw, A[1].dh, &A[0].gx, &A[0].gy);              // the tile grid of the pass rides in A[0]
-    A[1].gx = A[0].gx; A[1].gy = A[0].gy;
+    for (int k = 0; k < 2; k++) pyr_args(lv[k], lv[k + 1], B, A[k]);
+    pyr2_set_form(A, 0);
 }
 
 // The register-rolling form of the two-level pass where it applies: strip_rows = level-2 rows per strip, gx = workgroups per image,
@@ -90,12 +121,8 @@ void agt_pyr2_args(const AgtLevel* lv, int B, AgtPyrArgs* A)
 void agt_pyr2_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int frames, int oh_cap)
 {
     AgtPyrArgs& A0 = A[0]; AgtPyrArgs& A1 = A[1];
-    A0.strip_rows = A1.strip_rows = 0;
-    agt_pyr2_grid(A1.dw, A1.dh, &A0.gx, &A0.gy);
-    A1.gx = A0.gx; A1.gy = A0.gy;
-    const bool ok = ((src_align | (uintptr_t)A0.spitch | (uintptr_t)A0.sbatch | (uintptr_t)A0.sw) & 15) == 0 &&
-                    ((dst_align | (uintptr_t)A0.dpitch | (uintptr_t)A0.dbatch) & 7) == 0 && ((dst_align | (uintptr_t)A1.dpitch | (uintptr_t)A1.dbatch) & 3) == 0 &&
-                    A0.sw >= 32 && A0.sh >= 32 && (long)A0.sh * A0.spitch < (1L << 31) && (long)A0.dh * A0.dpitch < (1L << 31);
+    pyr2_set_form(A, 0);
+    const bool ok = pyr_roll_ok(A0, src_align, dst_align, 32, dst_align | (uintptr_t)A1.dpitch | (uintptr_t)A1.dbatch);
     // Round 4 measured this pass and did not ship it: every strip walked top-down, its 9 halo rows came from memory a second time
     // ((4 oh2 + 9) / (4 oh2) of the image: FETCH_SIZE 76.1 MB for 59.0 MB of frames at oh2 = 8) and a lane spent ~70 VALU per level-0
     // row; 64 x 720p: 24.0-25.5 us per pass against 24.9 for two single-level passes.  Round 5 ships it for launches of >= 16 images:
@@ -128,9 +155,7 @@ void agt_pyr2_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int 
     if (oh_cap < Q) oh_cap = Q;
     oh = oh < Q ? Q : (oh > oh_cap ? oh_cap : oh);
     { const long f = AGT_KNOB("AGT_PYR4_OH", 0); if (f > 0) oh = (int)(f + Q - 1) / Q * Q; }
-    A0.strip_rows = A1.strip_rows = oh;
-    A0.gx = A1.gx = agt_pyr4::roll2_blocks(A0.sw, A1.dh, oh);
-    A0.gy = A1.gy = 1;
+    pyr2_set_form(A, oh);
 }
 
 // Fused upload + two-level pyramid of ONE frame: src = device address of the caller's gray frame in pinned host memory; copy = the
@@ -143,16 +168,10 @@ hipError_t agt_launch_pyr_upload2(hipStream_t stream, const uint8_t* src, int sw
     AgtPyrArgs A[2];
     agt_pyr2_args(lv, 1, A);
     AgtPyrArgs& A0 = A[0]; AgtPyrArgs& A1 = A[1];
-    const bool ok = (((uintptr_t)src | (uintptr_t)spitch | (uintptr_t)sw | (uintptr_t)copy | (uintptr_t)cpitch) & 15) == 0 &&
-                    (((uintptr_t)dst1 | (uintptr_t)dpitch1) & 7) == 0 && (((uintptr_t)dst2 | (uintptr_t)dpitch2) & 3) == 0 &&
-                    sw >= 32 && sh >= 32 && (long)sh * spitch < (1L << 31) && (long)sh * cpitch < (1L << 31) && (long)A0.dh * dpitch1 < (1L << 31);
-    if (!ok) return hipErrorInvalidValue;
+    if (!pyr_roll_ok(A0, (uintptr_t)src, (uintptr_t)dst1, 32, (uintptr_t)dst2 | (uintptr_t)dpitch2, (uintptr_t)copy, cpitch)) return hipErrorInvalidValue;
     // two level-2 rows per strip (17 level-0 rows a lane): the most units one frame gives, measured 22.9 us from pinned host memory
     // (4: 24.7, 8: 26.2); the rows a strip reads twice come out of the L2, not over PCIe again
-    const int oh = agt_pyr4::L2_PER_TRIP;
-    A0.strip_rows = A1.strip_rows = oh;
-    A0.gx = A1.gx = agt_pyr4::roll2_blocks(sw, A1.dh, oh);
-    A0.gy = A1.gy = 1;
+    pyr2_set_form(A, agt_pyr4::L2_PER_TRIP);
     hipLaunchKernelGGL(pyr_upload2_kernel, dim3(agt_xcd_grid(A0.gx, A0.xshift)), dim3(agt_pyr::NT), 0, stream, A0, A1, copy, (int)cpitch);
     return hipGetLastError();
 }
@@ -166,12 +185,6 @@ hipError_t agt_launch_pyr_down2(hipStream_t stream, const AgtPyrArgs* A)
     return hipGetLastError();
 }
 
-void agt_pyr_grid(int dw, int dh, int* gx, int* gy)
-{
-    *gx = (dw + agt_pyr::TW - 1) / agt_pyr::TW;
-    *gy = (dh + agt_pyr::TH - 1) / agt_pyr::TH;
-}
-
 // Geometry of one pyrDown pass for A.src / A.dst (pointers, pitches, sizes and B filled in): the register-rolling form where
 // it applies (A.strip_rows = output rows per strip, A.gx = workgroups per image, A.gy = 1), else the tiled form (strip_rows = 0, tile grid).
 // `src_align` / `dst_align`: OR of every source / destination address the launch will see (frames of a group, batch strides).
@@ -181,11 +194,8 @@ void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int 
     A.strip_rows = 0;
     A.xshift = agt_chip_current().xshift; A.topdown = 0;
     agt_pyr_grid(A.dw, A.dh, &A.gx, &A.gy);
-    const bool ok = ((src_align | (uintptr_t)A.spitch | (uintptr_t)A.sbatch | (uintptr_t)A.sw) & 15) == 0 &&
-                    ((dst_align | (uintptr_t)A.dpitch | (uintptr_t)A.dbatch) & 7) == 0 &&
-                    A.sw >= 32 && A.sh >= 8 && (long)A.sh * A.spitch < (1L << 31) && (long)A.dh * A.dpitch < (1L << 31);
     if (!AGT_KNOB("AGT_PYR3", 1)) return;       // (knobs: AGT_PYR3=0 keeps the tiled kernel, AGT_PYR3_OH=n forces the strip height)
-    if (!ok) return;
+    if (!pyr_roll_ok(A, src_align, dst_align, 8)) return;
     // strip height: enough units (four per wave) to put ~3 waves on each of the chip's SIMDs (1024 on MI355X: 12,288 units) -- a wave keeps 8 KB of reads in
     // flight --, strips no longer than 16 output rows (measured on 64 x 720p, L0 -> L1: 8 rows 17.8 us, 16: 17.0, 24: 21.2,
     // 32: 22.1, 48: 27 -- the tiled kernel: 18.6), no shorter than 4 (3 halo rows per strip are re-read through the L2)
@@ -206,9 +216,7 @@ void agt_pyr_plan(AgtPyrArgs* pA, uintptr_t src_align, uintptr_t dst_align, int 
 hipError_t agt_launch_pyr_down(hipStream_t stream, const AgtLevel& src, const AgtLevel& dst, int B)
 {
     AgtPyrArgs A;
-    A.src = src.ptr; A.sw = src.w; A.sh = src.h; A.spitch = src.pitch; A.sbatch = src.bstride;
-    A.dst = const_cast<uint8_t*>(dst.ptr); A.dw = (src.w + 1) / 2; A.dh = (src.h + 1) / 2; A.dpitch = dst.pitch; A.dbatch = dst.bstride;
-    A.B = B;
+    pyr_args(src, dst, B, A);
     agt_pyr_plan(&A, (uintptr_t)A.src, (uintptr_t)A.dst, 1);
     const dim3 grid(agt_xcd_grid((long)agt_pyr_blocks(A) * B, A.xshift));
     if (agt_pyr_rolling(A)) hipLaunchKernelGGL(pyr_roll_kernel, grid, dim3(agt_pyr::NT), 0, stream, A);

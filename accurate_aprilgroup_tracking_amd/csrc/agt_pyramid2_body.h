@@ -13,7 +13,8 @@
 //      from pushing reflected L0 through the filter at the right / bottom edges)
 //   4  horizontal + vertical pass on the L1 tile -> 16 x 64 L2 pixels, 8-byte stores
 // Redundant work: the halo (73 instead of 64 + 3 source rows: 14 % more row reads, served by the XCD's L2 for
-// neighbouring tiles).  LDS: 40.9 KB per workgroup.
+// neighbouring tiles).  LDS: 40.9 KB per workgroup.  Which kernels run this form and who chooses it: the map at the head of
+// agt_pyramid_body.h.
 #pragma once
 #include "agt_pyramid_body.h"
 
@@ -51,11 +52,9 @@ __device__ __forceinline__ void pyr_down2_body(const AgtPyrArgs& A0, const AgtPy
     const bool aligned16 = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)A0.spitch) & 15) == 0;
 
     // ---- 1. fetch: thread -> (row r0 + 14 k, chunk c), 14 rows x 18 chunks per round, 6 rounds
-    // (row-interior tiles of an aligned image: the fast path of agt_pyramid_body.h -- no reflection, no 64-bit row multiply)
+    // (row-interior tiles of an aligned image: the fast path of agt_pyramid_body.h -- no reflection, no 64-bit row multiply.  Fetch and
+    // patch are pyr_down_body's with SHF rows, written out: why, and the shared forms that were tried, is said there)
     if (aligned16 && (sw & 15) == 0 && sy0 >= 0 && sy0 + SHF <= sh && A0.spitch < (1L << 23)) {
-        typedef const __attribute__((address_space(1))) uint8_t* G8;
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(1))) u32x4_t* G128;
         const int r0 = tid / NCH, c = tid - r0 * NCH;
         const int gx = sx0 + 16 * c;
         const bool lane_on = tid < 14 * NCH && gx >= 0 && gx + 16 <= sw;
@@ -113,14 +112,7 @@ __device__ __forceinline__ void pyr_down2_body(const AgtPyrArgs& A0, const AgtPy
     // ---- 2. horizontal pass of the 73 rows: 16 groups of 8 outputs (L1 columns X1 .. X1 + 127) ...
     for (int i = tid; i < SHF * (TW / 8); i += NT) {
         const int r = i / (TW / 8), q = i - r * (TW / 8);
-        const uint8_t* s = s_src + r * SW + 16 * (q + 1);
-        const uint4 d = *reinterpret_cast<const uint4*>(s);
-        uint32_t pm = 0, nx = 0;                       // neighbour dwords from the neighbour lanes (one DPP row = one image row)
-        if (q == 0) pm = *reinterpret_cast<const uint32_t*>(s - 4);
-        if (q == TW / 8 - 1) nx = *reinterpret_cast<const uint32_t*>(s + 16);
-        pm = (uint32_t)__builtin_amdgcn_update_dpp((int)pm, (int)d.w, 0x111, 0xf, 0xf, false);    // row_shr:1
-        nx = (uint32_t)__builtin_amdgcn_update_dpp((int)nx, (int)d.x, 0x101, 0xf, 0xf, false);    // row_shl:1
-        *reinterpret_cast<uint4*>(s_h1 + r * HP1 + 16 * q) = hgroup8(d, pm, nx);
+        *reinterpret_cast<uint4*>(s_h1 + r * HP1 + 16 * q) = hgroup8_of_row(s_src + r * SW, q);      // (neighbour dwords through DPP)
     }
     // ... and the three halo columns X1 - 2, X1 - 1, X1 + 128 (centres at staged bytes 12, 14, 272)
     for (int i = tid; i < SHF * 3; i += NT) {
@@ -134,17 +126,10 @@ __device__ __forceinline__ void pyr_down2_body(const AgtPyrArgs& A0, const AgtPy
     // ---- 3. vertical pass -> extended L1 tile (rows Y1 - 2 .. Y1 + 32): interior to HBM, everything to LDS
     for (int i = tid; i < R1 * (TW / 8); i += NT) {
         const int oy = i / (TW / 8), q = i - oy * (TW / 8);
-        const uint8_t* h = s_h1 + (2 * oy) * HP1 + 16 * q;
-        const uint2 px = vgroup8(*reinterpret_cast<const uint4*>(h), *reinterpret_cast<const uint4*>(h + HP1),
-                                 *reinterpret_cast<const uint4*>(h + 2 * HP1), *reinterpret_cast<const uint4*>(h + 3 * HP1),
-                                 *reinterpret_cast<const uint4*>(h + 4 * HP1));
+        const uint2 px = vgroup8_at(s_h1 + (2 * oy) * HP1 + 16 * q, HP1);
         *reinterpret_cast<uint2*>(s_l1 + oy * L1P + 16 + 8 * q) = px;
         const int gy = Y1 + oy - 2, gx = X1 + 8 * q;
-        if (oy >= 2 && oy < R1 - 1 && gy < h1 && gx < w1) {
-            uint8_t* o = out1 + (long)gy * A0.dpitch + gx;
-            if (gx + 7 < w1 && (((uintptr_t)o) & 7) == 0) *reinterpret_cast<uint2*>(o) = px;
-            else for (int k = 0; k < 8 && gx + k < w1; k++) o[k] = (uint8_t)((k < 4 ? px.x : px.y) >> (8 * (k & 3)));
-        }
+        if (oy >= 2 && oy < R1 - 1 && gy < h1 && gx < w1) store8(out1 + (long)gy * A0.dpitch + gx, px, gx, w1);
     }
     for (int i = tid; i < R1 * 3; i += NT) {
         const int oy = i / 3, e = i - oy * 3;
@@ -191,15 +176,17 @@ __device__ __forceinline__ void pyr_down2_body(const AgtPyrArgs& A0, const AgtPy
         const int oy = tid / (TW2 / 8), q = tid - oy * (TW2 / 8);
         const int gy = Y2 + oy, gx = X2 + 8 * q;
         if (gy < h2 && gx < w2) {
-            const uint8_t* h = s_h2 + (2 * oy) * HP2 + 16 * q;
-            const uint2 px = vgroup8(*reinterpret_cast<const uint4*>(h), *reinterpret_cast<const uint4*>(h + HP2),
-                                     *reinterpret_cast<const uint4*>(h + 2 * HP2), *reinterpret_cast<const uint4*>(h + 3 * HP2),
-                                     *reinterpret_cast<const uint4*>(h + 4 * HP2));
-            uint8_t* o = out2 + (long)gy * A1.dpitch + gx;
-            if (gx + 7 < w2 && (((uintptr_t)o) & 7) == 0) *reinterpret_cast<uint2*>(o) = px;
-            else for (int k = 0; k < 8 && gx + k < w2; k++) o[k] = (uint8_t)((k < 4 ? px.x : px.y) >> (8 * (k & 3)));
+            const uint2 px = vgroup8_at(s_h2 + (2 * oy) * HP2 + 16 * q, HP2);
+            store8(out2 + (long)gy * A1.dpitch + gx, px, gx, w2);
         }
     }
+}
+
+// tile `tile` (row-major in the Y0.gx x Y0.gy grid of the pass) of stream / image `st` of a batched two-level pass
+__device__ __forceinline__ void pyr2_tile_of_stream(const AgtPyrArgs& Y0, const AgtPyrArgs& Y1, int st, int tile, uint8_t* lds)
+{
+    const int by = tile / Y0.gx, bx = tile - by * Y0.gx;
+    pyr_down2_body(Y0, Y1, bx, by, Y0.src + (long)st * Y0.sbatch, Y0.dst + (long)st * Y0.dbatch, Y1.dst + (long)st * Y1.dbatch, lds);
 }
 
 }  // namespace agt_pyr2

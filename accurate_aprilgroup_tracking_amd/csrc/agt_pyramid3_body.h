@@ -16,8 +16,8 @@
 //     handles 8 source rows = 4 output rows), so a wave keeps 8 KB of reads outstanding without any other wave's help.
 // Top / bottom image edges (reflect-101 rows) and partial last strips take the EDGE form of the row loop (per-lane reflected
 // row index, one multiply-add per load); the choice is wave-uniform.  Work per output pixel: ~12 VALU, no LDS traffic.
-// Eligibility (agt_pyr3_plan): 16-byte aligned source with pitch and width multiples of 16, 8-byte aligned destination;
-// everything else (odd widths, tiny images, unaligned crops) keeps the tiled kernel.
+// Which kernels run this form and who chooses it: the map at the head of agt_pyramid_body.h (eligibility: agt_pyramid.hip
+// pyr_roll_ok; odd widths, tiny images and unaligned crops keep the tiled kernel).
 #pragma once
 #include "agt_pyramid_body.h"
 

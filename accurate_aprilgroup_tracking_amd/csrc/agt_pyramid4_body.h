@@ -16,7 +16,7 @@
 // are reflections OF LEVEL 1 (pyrDown(L1) reflects L1, which differs from filtering reflected level-0 pixels): columns by the same
 // in-register trick on the level-1 bytes, rows by picking the reflected entry of the level-1 window (all of them are in it).
 // Both exist only in the EDGE form of the row loop (wave-uniform choice).
-// Shipped uses: (round 4) the FUSED UPLOAD of agt_track_host_frame -- the pass reads a gray frame straight from pinned host memory
+// Shipped uses (the four forms side by side: the map at the head of agt_pyramid_body.h): (round 4) the FUSED UPLOAD of agt_track_host_frame -- the pass reads a gray frame straight from pinned host memory
 // (one frame: 22.9 us for both levels, PCIe-bound, against a 19 us copy-engine transfer + ~8 us of its submission + a 6 us pyramid
 // launch) and stores the frame's level 0 to HBM on the way (COPY); (round 5) the plain HBM -> HBM pyramid pass of every launch of >= 16
 // images (agt_pyramid.hip agt_pyr2_plan; pyr_roll2_kernel and the pyramid role of the split pipeline, pyr_group_kernel): with strips
@@ -50,32 +50,8 @@ constexpr int L2_PER_TRIP = RING / 4;
 static_assert(RING == 8 || RING == 16, "slot arithmetic below: the prologue consumes rows 0..8");
 
 // four horizontal [1 4 6 4 1] sums (u16) from the lane's 8 level-1 bytes (lo: pixels 0..3, hi: 4..7), the dword before (pm: its two
-// top bytes are pixels -2, -1) and the byte after (nx & 0xff: pixel 8) -> two registers
-__device__ __forceinline__ uint2 hgroup4(uint32_t lo, uint32_t hi, uint32_t pm, uint32_t nx)
-{
-    const uint32_t W4 = 0x04060401u;
-    const uint32_t e0 = __builtin_amdgcn_alignbyte(lo, pm, 2), e2 = __builtin_amdgcn_alignbyte(hi, lo, 2);
-    const uint32_t h0 = __builtin_amdgcn_udot4(e0, W4, (lo >> 16) & 0xff, false);      // centre pixel 0, fifth tap: pixel 2
-    const uint32_t h1 = __builtin_amdgcn_udot4(lo, W4, hi & 0xff, false);              // centre 2, fifth tap 4
-    const uint32_t h2 = __builtin_amdgcn_udot4(e2, W4, (hi >> 16) & 0xff, false);      // centre 4, fifth tap 6
-    const uint32_t h3 = __builtin_amdgcn_udot4(hi, W4, nx & 0xff, false);              // centre 6, fifth tap 8
-    return make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
-}
-
-// four vertical sums + (v + 128) >> 8 from five rows of four u16 -> four bytes
-__device__ __forceinline__ uint32_t vgroup4(uint2 r0, uint2 r1, uint2 r2, uint2 r3, uint2 r4)
-{
-    const uint32_t K4 = 0x00040004u, K6 = 0x00060006u, K128 = 0x00800080u;
-    auto col = [&](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint32_t a4) -> uint32_t {
-        uint32_t v = pk_mad(pk_add(a1, a3), K4, pk_add(a0, a4));
-        v = pk_mad(a2, K6, v);
-        return pk_shr8(pk_add(v, K128));
-    };
-    const uint32_t p0 = col(r0.x, r1.x, r2.x, r3.x, r4.x), p1 = col(r0.y, r1.y, r2.y, r3.y, r4.y);
-    return __builtin_amdgcn_perm(p1, p0, 0x06040200u);
-}
-
-// round 5: the chain form of agt_pyramid_body.h hgroup8b for the level-1 row of a lane (8 bytes: lo, hi), BIAS = +16 on every sum
+// top bytes are pixels -2, -1) and the byte after (nx & 0xff: pixel 8) -> two registers: the chain form of agt_pyramid_body.h hgroup8b,
+// BIAS = +16 on every sum
 template <bool BIAS>
 __device__ __forceinline__ uint2 hgroup4b(uint32_t lo, uint32_t hi, uint32_t pm, uint32_t nx)
 {

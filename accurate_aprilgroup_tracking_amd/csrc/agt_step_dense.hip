@@ -76,9 +76,8 @@ __global__ __launch_bounds__(AGT_WAVE * 4) void lk_pnp_coop_kernel(const AgtStep
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if ((int)blockIdx.x >= S.n_lk + S.n_pnp) {
         const int t = (int)blockIdx.x - S.n_lk - S.n_pnp;
-        const int st = t / n_pyr, tile = t - st * n_pyr;
-        const int by = tile / Y0.gx, bx = tile - by * Y0.gx;
-        agt_pyr2::pyr_down2_body(Y0, Y1, bx, by, Y0.src + (long)st * Y0.sbatch, Y0.dst + (long)st * Y0.dbatch, Y1.dst + (long)st * Y1.dbatch, lds);
+        const int st = t / n_pyr;
+        agt_pyr2::pyr2_tile_of_stream(Y0, Y1, st, t - st * n_pyr, lds);
         return;
     }
     if ((int)blockIdx.x >= S.n_lk) {

@@ -6,7 +6,7 @@ move a kernel.  CPU only; a development aid, not a test.
 
 Every gfx950 code object of both files is disassembled (llvm-objdump -d --no-show-raw-insn) and compared per demangled symbol.
 Printed: the difference of the symbol sets, and for every symbol whose instructions differ the two instruction counts, whether
-the opcode multisets are equal, and the first differing instruction.  Treated as equal:
+the opcode multisets are equal (if not: every opcode whose count differs), and the first differing instruction.  Treated as equal:
   * the two sources of a commutative two-source scalar instruction in either order (s_or_b64 s0, s0, vcc / s_or_b64 s0, vcc, s0);
   * the __hip_cuid_* symbol (a hash of the translation unit's text);
   * the literals of a pc-relative address (s_getpc_b64 + s_add_u32 / s_addc_u32) that resolve to the same symbol + offset.
@@ -127,8 +127,11 @@ def main():
         if a == b:
             continue
         bad += 1
-        same_ops = collections.Counter(x.split()[0] for x in a) == collections.Counter(x.split()[0] for x in b)
-        print("differs: %s\n    instructions %d -> %d, opcode multisets %s" % (s, len(a), len(b), "equal" if same_ops else "differ"))
+        ca, cb = collections.Counter(x.split()[0] for x in a), collections.Counter(x.split()[0] for x in b)
+        print("differs: %s\n    instructions %d -> %d, opcode multisets %s" % (s, len(a), len(b), "equal" if ca == cb else "differ"))
+        for op in sorted(set(ca) | set(cb)):
+            if ca[op] != cb[op]:
+                print("    %-24s %d -> %d" % (op, ca[op], cb[op]))
         k = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
         print("    first difference at instruction %d:  %s  |  %s" % (k, a[k] if k < len(a) else "(end)", b[k] if k < len(b) else "(end)"))
     print("# %s" % ("identical beyond the allowances" if not bad else "%d symbols differ" % bad))
