@@ -296,6 +296,40 @@ __device__ __forceinline__ void agt_project(const AgtCamera& cam, const double R
     }
 }
 
+// d(u, v) / d camera at one point, for a camera WITHOUT tilt: ju / jv are the rows of the 2 x 16 block in the order
+//     fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4        (entry 4 + i = cam.k[i]).
+// Formed from the intermediate values of agt_project<., true> (x, y, r2, cdist, icdist2, ... by the same expressions, so a caller that
+// inlines both shares them): u = fx xd + cx, v = fy yd + cy with
+//     xd = x cdist icdist2 + p1 a1 + p2 a2 + s1 r2 + s2 r4,    yd = y cdist icdist2 + p1 a3 + p2 a1 + s3 r2 + s4 r4.
+__device__ __forceinline__ void agt_project_dcam(const AgtCamera& cam, const double R[9], const double t[3], double X, double Y, double Z,
+                                                 double ju[16], double jv[16])
+{
+    const double* k = cam.k;
+    double x = R[0] * X + R[1] * Y + R[2] * Z + t[0];
+    double y = R[3] * X + R[4] * Y + R[5] * Z + t[1];
+    double z = R[6] * X + R[7] * Y + R[8] * Z + t[2];
+    z = z != 0.0 ? agt_rcp(z) : 1.0;
+    x *= z; y *= z;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    const double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+    const double icdist2 = 1.0 / (1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+    const double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2 + k[8] * r2 + k[9] * r4;
+    const double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1 + k[10] * r2 + k[11] * r4;
+    const double nx = cam.fx * x * icdist2, ny = cam.fy * y * icdist2;            // d / d numerator coefficient = n . r^2m
+    const double qx = -nx * cdist * icdist2, qy = -ny * cdist * icdist2;          // d / d denominator coefficient = q . r^2m
+    ju[0] = xd;  ju[1] = 0.0; ju[2] = 1.0; ju[3] = 0.0;
+    jv[0] = 0.0; jv[1] = yd;  jv[2] = 0.0; jv[3] = 1.0;
+    ju[4] = nx * r2; ju[5] = nx * r4; ju[8] = nx * r6;
+    jv[4] = ny * r2; jv[5] = ny * r4; jv[8] = ny * r6;
+    ju[6] = cam.fx * a1; ju[7] = cam.fx * a2;
+    jv[6] = cam.fy * a3; jv[7] = cam.fy * a1;
+    ju[9] = qx * r2; ju[10] = qx * r4; ju[11] = qx * r6;
+    jv[9] = qy * r2; jv[10] = qy * r4; jv[11] = qy * r6;
+    ju[12] = cam.fx * r2; ju[13] = cam.fx * r4; ju[14] = 0.0; ju[15] = 0.0;
+    jv[12] = 0.0; jv[13] = 0.0; jv[14] = cam.fy * r2; jv[15] = cam.fy * r4;
+}
+
 // Pose-driven visibility of one planar tag (agt_tracker_visibility, agt_tag_visibility; the rule: include/agt_hip.h).  p: the tag's cpt
 // object points (x y z each); R, t: the pose.  With c = the mean of the points (summed in index order) and n = facing * (p3 - p0) x (p1 - p0),
 // the tag's +z axis under the reference's corner template (transform_helper.py:41-63), both taken to the camera frame:

@@ -720,3 +720,19 @@ def buildDenseModel(frames, rvecs, tvecs, group, cameraMatrix, distCoeffs=None, 
     from . import dense_model
     poses = np.concatenate([np.asarray(rvecs, np.float64).reshape(-1, 3), np.asarray(tvecs, np.float64).reshape(-1, 3)], axis=1)
     return dense_model.build_dense_model(frames, poses, group, cameraMatrix, distCoeffs, use=use, **kwargs)
+
+
+from .camera_calib import (CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST,  # noqa: E402,F401
+                           CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
+                           CALIB_RATIONAL_MODEL, CALIB_THIN_PRISM_MODEL, CALIB_FIX_S1_S2_S3_S4, CALIB_TILTED_MODEL, CALIB_FIX_TAUX_TAUY,
+                           CALIB_USE_QR, CALIB_USE_LU, CALIB_FIX_TANGENT_DIST)
+
+
+def calibrateCamera(objectPoints, imagePoints, imageSize, cameraMatrix, distCoeffs, flags=0):
+    """cv2.calibrateCamera -> (rms, cameraMatrix (3,3), distCoeffs (1,k), rvecs, tvecs), rvecs / tvecs tuples of (3,1) as cv2 returns
+    them; k = 5, 8 with CALIB_RATIONAL_MODEL, 12 with CALIB_THIN_PRISM_MODEL.  cv2's cost, this project's Levenberg-Marquardt on the GPU
+    (camera_calib.calibrate_camera, include/agt_camcal.h): the minimum is cv2's, the iterates are not.  The tilted-sensor model,
+    CALIB_FIX_ASPECT_RATIO and the solver-choice flags raise `error` naming the flag."""
+    from . import camera_calib
+    rms, mtx, dist, rvecs, tvecs, _ = camera_calib.calibrate_camera(objectPoints, imagePoints, imageSize, cameraMatrix, distCoeffs, flags=flags)
+    return rms, mtx, dist, tuple(r.reshape(3, 1).copy() for r in rvecs), tuple(t.reshape(3, 1).copy() for t in tvecs)
