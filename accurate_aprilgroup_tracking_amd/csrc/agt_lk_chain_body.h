@@ -18,9 +18,12 @@
 //     arrival counter one frame later, both under the next frame's image-side work: the stores behind its Scharr barrier, the
 //     arrival two barriers on (stores count in vmcnt: issued at the frame's end, their acknowledgement was waited for by the
 //     hand-over's wait for the prefetched tiles);
-//   * the 2 x 2 systems of all levels are read once behind the reduction's barrier, with one crossing to the scalar unit.
+//   * the 2 x 2 systems of all levels are read once behind the reduction's barrier, with one crossing to the scalar unit;
+//   * the iteration loop is two loops -- the inner one holds the common trip and nothing else, the slow path and the codes that end
+//     a level are sorted out behind it -- and the sums' scale 2^-20 is folded into the level's 1 / det.
 // Measured on production code with fixed iteration counts: 5.8 us per frame + 0.62 us per iteration (profiles/r02_summary.md);
-// 5.45 us since the last two items (profiles/lk_frame_fixed.md).
+// 5.45 us since the two items before the last (profiles/lk_frame_fixed.md); the last one took another 0.5 us off the frame of the
+// c2 stream, about 0.04 us per iteration (profiles/pose_handover.md).
 // Only what the tracker uses is covered: flags == 0, no error output (lk_role keeps lk_body otherwise); the frames of a group
 // share their geometry, the image before the group may differ in pitch.  A one-frame group is fine: its image-(k-1) tiles are
 // loaded on demand like the first frame's of any group.
@@ -492,6 +495,15 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             const float4 lv4 = lv[level];
             const float a11 = NLEV > 3 ? lv11[level] : agt_uniform(lv4.x), a12 = NLEV > 3 ? lv12[level] : agt_uniform(lv4.y);
             const float a22 = NLEV > 3 ? lv22[level] : agt_uniform(lv4.z), D = NLEV > 3 ? lvD[level] : agt_uniform(lv4.w);
+            // OpenCV scales the two mismatch sums of every iteration (b1 *= FLT_SCALE, b2 *= FLT_SCALE) before the 2 x 2 solve; here the
+            // factor 2^-20 is folded into the level's 1 / det once.  Exact -- scaling by a power of two commutes with every rounding
+            // as long as no value leaves the normal range, and none does, with or without the fold: the sums are integers below
+            // 2^35 or 0, A11, A12, A22 are multiples of 2^-20 below 2^13 or 0 (a product is 0 or in [2^-40, 2^48) scaled, [2^-20, 2^48)
+            // unscaled), a difference of two such products is 0 or at least an ulp of the smaller one (> 2^-64), 1 / det lies in
+            // (2^-26, 2^23] (det in [FLT_EPSILON, 2^26): the level's entry test), so Ds in (2^-46, 2^3] is exact and dx, dy are 0 or
+            // in (2^-110, 2^52).  A NaN 1 / det stays a NaN.  The bit-exact LK tests hold the fold to the oracle.  (From here on D is
+            // used through Ds only.)
+            const float Ds = D * FLT_SCALE;
             int iv[C::NPX], ix[C::NPX], iy[C::NPX];
 #pragma unroll
             for (int q = 0; q < C::NPX; q++) { iv[q] = Iv[level][q]; ix[q] = Ix[level][q]; iy[q] = Iy[level][q]; }
@@ -513,12 +525,19 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
             // the tests of an iteration (converged, oscillating, FP64 tie-break needed, next window position outside the box)
             // are folded into one code that crosses to the scalar unit once.
             int slow = agt_uniform((int)!(nextx >= bx0 && nextx < bx1 && nexty >= by0 && nexty < by1));
-            for (int j = 0; j < max_count; j++) {
-                const float fx = floorf(nextx), fy = floorf(nexty);
+            // The loop is two loops: the inner one is the common trip (code 0: go on inside the box) and holds nothing else -- one
+            // exit test at its end, no test for the slow path at its head; whatever else a trip decided is sorted out behind it,
+            // once per level or per box crossing: code 3 goes round the outer loop through the slow path (one copy), codes 1 and 2
+            // end the level, and what code 2 does to the result follows both loops.  (As one loop with two breaks and the slow test
+            // at its head, the common trip ran through four taken branches, three untaken ones and a vector compare for the slow flag.)
+            int code = 0, j = 0;
+            while (j < max_count) {
                 if (slow) {
+                    const float fx = floorf(nextx), fy = floorf(nexty);
                     const int inx = agt_uniform((int)fx), iny = agt_uniform((int)fy);
                     if (inx < -WIN || inx >= LJ.w || iny < -WIN || iny >= LJ.h) {
                         if (level == 0) st = 0;
+                        code = 0;
                         break;
                     }
                     if (inx < jx0 || inx + WIN >= jx0 + JT || iny < jy0 || iny + WIN >= jy0 + JT) {
@@ -534,41 +553,45 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
                         block_sync<NW>();
                         set_box();
                     }
+                    slow = 0;
                 }
-                const int inx = (int)fx, iny = (int)fy;
-                // the six tap bytes are requested FIRST (their address needs only the integer part of the position) and the
-                // bilinear weights -- ~20 dependent float operations on the fraction -- are computed while the LDS answers
-                const uint8_t* q0 = sJ + __mul24(iny - jy0, JP) + (inx - jx0) + (jx0 - (jx0 & ~3));
-                int tap[C::NPX][4];
+                do {
+                    const float fx = floorf(nextx), fy = floorf(nexty);
+                    const int inx = (int)fx, iny = (int)fy;
+                    // the six tap bytes are requested FIRST (their address needs only the integer part of the position) and the
+                    // bilinear weights -- ~20 dependent float operations on the fraction -- are computed while the LDS answers
+                    const uint8_t* q0 = sJ + __mul24(iny - jy0, JP) + (inx - jx0) + (jx0 - (jx0 & ~3));
+                    int tap[C::NPX][4];
 #pragma unroll
-                for (int q = 0; q < C::NPX; q++) {
-                    const uint8_t* c = q0 + oW[q];
-                    tap[q][0] = c[0]; tap[q][1] = c[1]; tap[q][2] = c[JP]; tap[q][3] = c[JP + 1];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                bilinear_weights(nextx - fx, nexty - fy, iw00, iw01, iw10, iw11);
-                int bsum[2] = { 0, 0 };
+                    for (int q = 0; q < C::NPX; q++) {
+                        const uint8_t* c = q0 + oW[q];
+                        tap[q][0] = c[0]; tap[q][1] = c[1]; tap[q][2] = c[JP]; tap[q][3] = c[JP + 1];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    bilinear_weights(nextx - fx, nexty - fy, iw00, iw01, iw10, iw11);
+                    int bsum[2] = { 0, 0 };
 #pragma unroll
-                for (int q = 0; q < C::NPX; q++) {
-                    const int diff = descale(bil4(tap[q][0], tap[q][1], tap[q][2], tap[q][3], iw00, iw01, iw10, iw11), W_BITS - 5) - iv[q];
-                    bsum[0] += __mul24(diff, ix[q]); bsum[1] += __mul24(diff, iy[q]);          // ix = iy = 0 where !pv
-                }
-                float fb1, fb2;
-                iter_sum2(bsum, fb1, fb2, slots, phase, wave, lane);
-                fb1 *= FLT_SCALE; fb2 *= FLT_SCALE;
-                const float dx = (a12 * fb2 - a22 * fb1) * D;
-                const float dy = (a12 * fb1 - a11 * fb2) * D;
-                nextx += dx; nexty += dy;
-                outx = nextx + halfw; outy = nexty + halfw;
+                    for (int q = 0; q < C::NPX; q++) {
+                        const int diff = descale(bil4(tap[q][0], tap[q][1], tap[q][2], tap[q][3], iw00, iw01, iw10, iw11), W_BITS - 5) - iv[q];
+                        bsum[0] += __mul24(diff, ix[q]); bsum[1] += __mul24(diff, iy[q]);          // ix = iy = 0 where !pv
+                    }
+                    float fb1, fb2;
+                    iter_sum2(bsum, fb1, fb2, slots, phase, wave, lane);
+                    const float dx = (a12 * fb2 - a22 * fb1) * Ds;           // (FLT_SCALE is in Ds: see the level's entry)
+                    const float dy = (a12 * fb1 - a11 * fb2) * Ds;
+                    nextx += dx; nexty += dy;
+                    outx = nextx + halfw; outy = nexty + halfw;
 #ifdef AGT_STEP_STAMPS
-                if (pidx == 0 && threadIdx.x == 0 && k < 4 && level < 3) agt_chain_stamps[k * 16 + 14] += 1ull << (level * 8);
+                    if (pidx == 0 && threadIdx.x == 0 && k < 4 && level < 3) agt_chain_stamps[k * 16 + 14] += 1ull << (level * 8);
 #endif
-                const int code = lk_iter_code(dx, dy, pdx, pdy, j, nextx, nexty, bx0, bx1, by0, by1, eps2_lo, eps2_hi, [&] { return eps2; });
-                if (code == 1) break;
-                if (code == 2) { outx -= dx * 0.5f; outy -= dy * 0.5f; break; }
-                slow = code == 3;
-                pdx = dx; pdy = dy;
+                    code = lk_iter_code(dx, dy, pdx, pdy, j, nextx, nexty, bx0, bx1, by0, by1, eps2_lo, eps2_hi, [&] { return eps2; });
+                    pdx = dx; pdy = dy;         // (the next trip's oscillation test; code 2 takes half of it back)
+                    j++;
+                } while (code == 0 && j < max_count);
+                if (code != 3) break;
+                slow = 1;
             }
+            if (code == 2) { outx -= pdx * 0.5f; outy -= pdy * 0.5f; }
             jox[level] = agt_uniform(jx0); joy[level] = agt_uniform(jy0);
             CSTAMP(9 + level * 2);
         }

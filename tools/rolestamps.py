@@ -28,3 +28,10 @@ t0 = s[0, 0]
 for k in range(D):
     print("frame %2d: top %7.2f | corners +%5.2f | state +%5.2f (waited %5.2f) | done +%5.2f | period %5.2f" % (
         k, s[k, 0] - t0, s[k, 1] - s[k, 0], s[k, 2] - s[k, 0], s[k, 2] - s[k, 1], s[k, 3] - s[k, 2], (s[k, 3] - s[k - 1, 3]) if k else 0.0))
+# The columns are microseconds only if the counter really ticks every AGT_TICK_NS: 100 MHz is the documented s_memtime rate, but a
+# card has been seen counting about 22 times faster (profiles/pose_handover.md).  The median period below is one frame of the launch;
+# against the frame time tools/c2variants.py gives for the same library it tells the tick, and the columns can always be read as
+# fractions of it.
+if D > 2:
+    med = float(np.median(s[2:D, 3] - s[1:D - 1, 3]))
+    print("median period %.2f (one frame of the launch: with tools/c2variants.py's us/frame f for this library, AGT_TICK_NS = %.1f * f / %.2f)" % (med, TICK, med))
