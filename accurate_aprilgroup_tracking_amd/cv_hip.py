@@ -722,6 +722,30 @@ def buildDenseModel(frames, rvecs, tvecs, group, cameraMatrix, distCoeffs=None, 
     return dense_model.build_dense_model(frames, poses, group, cameraMatrix, distCoeffs, use=use, **kwargs)
 
 
+def decodeTags(gray, quads, family, maxHamming=2, minMargin=0.0):
+    """The decode stage of a tag detector (no cv2 counterpart; tag_decode.decode_quads, include/agt_tagcode.h): gray (H, W) u8, quads
+    (N, 4, 2) candidate quads, family a tag_decode.TagFamily -> list of formats.Detection for the quads that decode (status OK), in
+    the order given: tag_id, hamming, decision_margin (this rule's own scale, not apriltag's), corners rolled to the tag's canonical
+    order, homography and center.  Finding the quads is the caller's job."""
+    from . import tag_decode
+    _require_gpu()
+    img = np.ascontiguousarray(np.asarray(gray))
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise error("decodeTags: gray must be a 2-D uint8 image")
+    q = np.ascontiguousarray(np.asarray(quads, np.float32))
+    if q.ndim != 3 or q.shape[1:] != (4, 2):
+        raise error("decodeTags: quads must be (N, 4, 2)")
+    if q.shape[0] == 0:
+        return []
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        out = tag_decode.decode_quads(torch.from_numpy(img).to(dev)[None], torch.from_numpy(q).to(dev)[None], family,
+                                      max_hamming=maxHamming, min_margin=minMargin)
+    except tag_decode.T.TagCodeError as e:
+        raise error(str(e))
+    return tag_decode.records_to_detections(tag_decode.records_numpy(out.records)[0], q, out.homography.cpu().numpy()[0], family.name)
+
+
 from .camera_calib import (CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST,  # noqa: E402,F401
                            CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
                            CALIB_RATIONAL_MODEL, CALIB_THIN_PRISM_MODEL, CALIB_FIX_S1_S2_S3_S4, CALIB_TILTED_MODEL, CALIB_FIX_TAUX_TAUY,

@@ -8,6 +8,8 @@
 * detections             -- the swatbotics ``apriltag.Detection`` records the reference consumes at
   detect_pose.py:389-437 (``.corners`` 4x2, ``.tag_id``, ``.decision_margin`` >= 50) and a compact
   ``.npz`` recording of them so that a real session can be replayed without the detector.
+* tag family (``.npz``)  -- the code words ``tag_decode.TagFamily`` matches payloads against, exported once from the user's
+  own apriltag install.
 
 Host-side only; nothing here touches the GPU.  ``detections_to_corner_table`` produces the dense
 ``[4T, 2]`` corner table + mask that the device state machine takes (``agt_estimate_pose``).
@@ -210,3 +212,22 @@ def load_dense_model(path):
             raise ValueError("%s: dense model format %d, %d expected" % (path, int(f["format"]), _DENSE_MODEL_FORMAT))
         settings = {k[4:]: f[k][()].item() for k in f.files if k.startswith("set_")}
         return DenseModel(*[f[k] for k in DenseModel.FIELDS], settings=settings)
+
+
+# ------------------------------------------------------------------ tag family (.npz)
+def save_tag_family(path, codes, name="tag36h11", bits_per_side=6):
+    """One .npz with `codes` (u64; bit 35 - (6 r + c) = row r, column c of the payload), `bits_per_side` and `name`: the input of
+    tag_decode.TagFamily.  The real tag36h11 table is not shipped; export it once from your own apriltag install."""
+    codes = np.ascontiguousarray(np.asarray(codes, np.uint64).reshape(-1))
+    with open(path, "wb") as f:
+        np.savez(f, codes=codes, bits_per_side=np.int64(bits_per_side), name=np.asarray(name.decode() if isinstance(name, bytes) else str(name)))
+
+
+def load_tag_family(path):
+    """-> tag_decode.TagFamily"""
+    from .tag_decode import TagFamily
+    with np.load(path, allow_pickle=False) as f:
+        missing = [k for k in ("codes", "bits_per_side", "name") if k not in f.files]
+        if missing:
+            raise ValueError("%s: missing key(s) %s" % (path, ", ".join(missing)))
+        return TagFamily(f["codes"], str(f["name"][()]), int(f["bits_per_side"]))

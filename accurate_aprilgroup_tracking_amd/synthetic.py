@@ -276,3 +276,42 @@ class Sequence:
         render_frame(self.group, self.bits, self.rvecs[k], self.tvecs[k], self.K, self.dist, self.width, self.height,
                      self.bg, 1, cover_out=cov)
         return cov
+
+
+def _code_rotations(bits):
+    """the four words of a (6, 6) bit matrix turned clockwise 0..3 times (bit 35 - (6 r + c) = row r, column c)"""
+    weights = np.uint64(1) << (np.uint64(35) - np.arange(36, dtype=np.uint64))
+    return np.array([np.sum(weights[np.rot90(bits, -k).ravel() > 0], dtype=np.uint64) for k in range(4)], np.uint64)
+
+
+def _popcount(x):
+    x = np.asarray(x, np.uint64)
+    return np.unpackbits(x.view(np.uint8).reshape(x.shape + (8,)), axis=-1).sum(axis=-1)
+
+
+def make_tag_family(n, min_distance, seed=0, max_draws=2000000):
+    """(n,) u64 code words of a synthetic 6 x 6 family: random draws, a draw is kept only if it is at least min_distance bits from
+    every kept code under all four rotations and from its own three rotations.  A stand-in for a real family with the same
+    structure (tag36h11 has 587 codes at distance >= 11); seeded, so tests and renders agree on it."""
+    rng = np.random.default_rng(seed + 15485863)
+    kept = np.zeros(0, np.uint64)            # all four rotations of every kept code
+    codes = []
+    for _ in range(max_draws):
+        rot = _code_rotations(rng.integers(0, 2, size=(6, 6)))
+        if _popcount(rot[1:] ^ rot[0]).min() < min_distance:
+            continue
+        if kept.size and _popcount(kept ^ rot[0]).min() < min_distance:
+            continue
+        codes.append(rot[0])
+        kept = np.concatenate([kept, rot])
+        if len(codes) == n:
+            return np.array(codes, np.uint64)
+    raise ValueError("make_tag_family: %d codes at distance %d not found in %d draws" % (n, min_distance, max_draws))
+
+
+def family_bits(family, ids):
+    """(len(ids), 6, 6) u8 payloads of codes `ids` of a family (a tag_decode.TagFamily or an array of code words): the `bits`
+    render_frame paints, in place of tag_bits' random ones"""
+    codes = np.asarray(getattr(family, "codes", family), np.uint64).reshape(-1)[np.asarray(ids, np.int64)]
+    shifts = np.uint64(35) - np.arange(36, dtype=np.uint64)
+    return ((codes[:, None] >> shifts[None, :]) & np.uint64(1)).astype(np.uint8).reshape(-1, 6, 6)

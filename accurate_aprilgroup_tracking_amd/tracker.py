@@ -22,6 +22,17 @@ class TrackState(C.Structure):
                 ("chain_fault", C.c_int), ("pad", C.c_int)]
 
 
+class _DeviceArray:
+    """a library-owned device buffer as torch sees it (no copy, no ownership): the __cuda_array_interface__ of an address"""
+
+    def __init__(self, address, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(address), False), "version": 2}
+
+
+def _device_view(address, shape, typestr, device):
+    return torch.as_tensor(_DeviceArray(address, shape, typestr), device=device)
+
+
 class StreamTracker:
     def __init__(self, width, height, obj_points, K, dist=None, n_streams=1, max_level=2, win=21,
                  enhance_ape=True, reproject=False, min_points=8, gate_px=2.0, device=None, fb_check=0.0, view_deg=0.0, facing=1,
@@ -261,6 +272,30 @@ class StreamTracker:
         corners = torch.from_numpy(np.stack([t[0] for t in tabs])).to(self.dev)
         mask = torch.from_numpy(np.stack([t[1] for t in tabs])).to(self.dev)
         return self.estimate_pose(corners, mask, state_out)
+
+    def decode_tags(self, frames, family, tag_ids=None, max_hamming=2, min_margin=0.0):
+        """Image evidence that the tracked quads still show their tags (tag_decode, include/agt_tagcode.h): decodes the payload inside
+        every tag of the tracker's own corner buffer in `frames` (cuda u8 [B,H,W], the frames the corners belong to -- the newest ones
+        handed to step()), a tag being read only while all four of its corners have status 1.  family: a tag_decode.TagFamily; tag_ids:
+        the family index of each tag of the model in model order (default 0..T-1).
+        -> (records cuda u8 [B,T,40] -- tag_decode.records_numpy gives the fields --, corner_mask cuda u8 [B,n]): a tag's four mask
+        bytes are 1 iff it decoded to its own id, unrotated, within max_hamming and at or above min_margin.  Feed the mask to
+        step_detected(frames, corners, mask) or estimate_pose(corners, mask) to drop the tags that failed; step() is unchanged and
+        never calls this.  Joins the pipeline; enqueues only."""
+        from . import tag_decode
+        assert self.n % 4 == 0, "decode_tags needs four corners per tag"
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.shape[0] == self.B
+        assert tuple(frames.shape[1:]) == (self.ctx.height, self.ctx.width) and frames.stride(2) == 1, "frames must be [B, H, W] with unit pixel stride"
+        T = self.n // 4
+        ids = np.arange(T, dtype=np.int32) if tag_ids is None else np.ascontiguousarray(np.asarray(tag_ids, np.int32).reshape(-1))
+        assert ids.size == T, "one family index per tag of the model"
+        self.join()
+        cp, sp = self.corners()
+        quads = _device_view(cp, (self.B, T, 4, 2), "<f4", self.dev)
+        mask = _device_view(sp, (self.B, T, 4), "|u1", self.dev).amin(dim=2)
+        out = tag_decode.decode_quads(frames, quads, family, mask=mask, expected=torch.from_numpy(ids).to(self.dev),
+                                      max_hamming=max_hamming, min_margin=min_margin)
+        return out.records, out.corner_mask
 
     def new_state_buffer(self, frames=1):
         shape = (frames, self.B, H.STATE_STRIDE) if frames > 1 else (self.B, H.STATE_STRIDE)
