@@ -746,6 +746,30 @@ def decodeTags(gray, quads, family, maxHamming=2, minMargin=0.0):
     return tag_decode.records_to_detections(tag_decode.records_numpy(out.records)[0], q, out.homography.cpu().numpy()[0], family.name)
 
 
+def refineQuads(gray, quads, rangePx=2.0, iters=2, minStrength=40.0):
+    """The edge refinement stage of a tag detector (no cv2 counterpart; quad_refine.refine_quads, include/agt_quadfit.h): gray (H, W)
+    u8, quads (N, 4, 2) rough quads on the outer edge of the black border -> (quads (N, 4, 2) f32, records (N,) structured: status,
+    passes, strength, shift, resid).  A quad whose status is not 0 (OK) comes back exactly as given.  Not cornerSubPix: whole border
+    edges are fitted and intersected.  Finding the quads is the caller's job."""
+    from . import quad_refine
+    _require_gpu()
+    img = np.ascontiguousarray(np.asarray(gray))
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise error("refineQuads: gray must be a 2-D uint8 image")
+    q = np.ascontiguousarray(np.asarray(quads, np.float32))
+    if q.ndim != 3 or q.shape[1:] != (4, 2):
+        raise error("refineQuads: quads must be (N, 4, 2)")
+    if q.shape[0] == 0:
+        return q, np.zeros(0, quad_refine.Q.RECORD_DTYPE)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        out = quad_refine.refine_quads(torch.from_numpy(img).to(dev)[None], torch.from_numpy(q).to(dev)[None], range_px=rangePx, iters=iters,
+                                       min_strength=minStrength)
+    except quad_refine.Q.QuadFitError as e:
+        raise error(str(e))
+    return out.quads.cpu().numpy()[0], quad_refine.records_numpy(out.records)[0]
+
+
 from .camera_calib import (CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST,  # noqa: E402,F401
                            CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
                            CALIB_RATIONAL_MODEL, CALIB_THIN_PRISM_MODEL, CALIB_FIX_S1_S2_S3_S4, CALIB_TILTED_MODEL, CALIB_FIX_TAUX_TAUY,

@@ -297,6 +297,27 @@ class StreamTracker:
                                       max_hamming=max_hamming, min_margin=min_margin)
         return out.records, out.corner_mask
 
+    def refine_tags(self, frames, range_px=2.0, iters=2, min_strength=40.0):
+        """The tracked quads snapped back onto the image (quad_refine, include/agt_quadfit.h): fits every tag of the tracker's own
+        corner buffer to its border edges in `frames` (cuda u8 [B,H,W], the frames the corners belong to -- the newest ones handed to
+        step()), a tag being fitted only while all four of its corners have status 1.
+        -> (records cuda u8 [B,T,32] -- quad_refine.records_numpy gives the fields --, corners cuda f32 [B,n,2], corner_mask cuda u8
+        [B,n]): a tag's four mask bytes are 1 iff it was refined; the corners of any other tag are the buffer's own.  The result is
+        meant for step_detected(frames, corners, corner_mask) or estimate_pose(corners, corner_mask); tag_decode.decode_quads on
+        corners.view(B, T, 4, 2) may come first, its mask ANDed with this one.  step() is unchanged and never calls this.  Joins the
+        pipeline; enqueues only."""
+        from . import quad_refine
+        assert self.n % 4 == 0, "refine_tags needs four corners per tag"
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.shape[0] == self.B
+        assert tuple(frames.shape[1:]) == (self.ctx.height, self.ctx.width) and frames.stride(2) == 1, "frames must be [B, H, W] with unit pixel stride"
+        T = self.n // 4
+        self.join()
+        cp, sp = self.corners()
+        quads = _device_view(cp, (self.B, T, 4, 2), "<f4", self.dev)
+        mask = _device_view(sp, (self.B, T, 4), "|u1", self.dev).amin(dim=2)
+        out = quad_refine.refine_quads(frames, quads, mask=mask, range_px=range_px, iters=iters, min_strength=min_strength)
+        return out.records, out.quads.view(self.B, self.n, 2), out.corner_mask
+
     def new_state_buffer(self, frames=1):
         shape = (frames, self.B, H.STATE_STRIDE) if frames > 1 else (self.B, H.STATE_STRIDE)
         return torch.zeros(shape, dtype=torch.float64, device=self.dev)
