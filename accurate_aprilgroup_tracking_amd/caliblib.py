@@ -1,12 +1,13 @@
 """ctypes binding of the offline calibration library (include/agt_calib.h -> libagt_calib.so).
-
-Same rules as hiplib: the library is built by `make -C accurate_aprilgroup_tracking_amd/csrc` (build() of __graft_entry__),
-there is NO CPU fallback -- a missing library raises --, and torch is imported first so that one HIP runtime owns the device.
-"""
+Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _sidelib
+from ._sidelib import (Options, Report, STOP_CONVERGED, STOP_MAX_ITERS, STOP_LAMBDA, STOP_NAMES,  # noqa: F401
+                       _f64, _addr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_calib.so")
@@ -17,8 +18,6 @@ ERR_ARG, ERR_ALLOC, ERR_CAMERA, ERR_HIP, ERR_DISCONNECTED, ERR_TOO_FEW_FRAMES, E
 ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_CAMERA: "CAMERA", ERR_HIP: "HIP", ERR_DISCONNECTED: "DISCONNECTED",
           ERR_TOO_FEW_FRAMES: "TOO_FEW_FRAMES", ERR_SINGULAR: "SINGULAR"}
 MAX_TAGS, MAX_FRAMES = 64, 65536
-STOP_CONVERGED, STOP_MAX_ITERS, STOP_LAMBDA = 1, 2, 3
-STOP_NAMES = {STOP_CONVERGED: "converged", STOP_MAX_ITERS: "iteration cap", STOP_LAMBDA: "damping limit"}
 
 # every symbol include/agt_calib.h declares
 SYMBOLS = ["agt_calib_version", "agt_group_calib_create", "agt_group_calib_destroy", "agt_group_calib_eval", "agt_group_calib_step",
@@ -31,38 +30,12 @@ class Problem(C.Structure):
                 ("obs_frame", C.c_void_p), ("obs_tag", C.c_void_p), ("obs_corners", C.c_void_p)]
 
 
-class Options(C.Structure):
-    _fields_ = [("max_iters", C.c_int32), ("reserved0", C.c_int32), ("ftol", C.c_double), ("lambda0", C.c_double),
-                ("lambda_up", C.c_double), ("lambda_down", C.c_double), ("lambda_max", C.c_double)]
-
-
-class Report(C.Structure):
-    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("stop_reason", C.c_int32), ("n_residuals", C.c_int32),
-                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_rms_px", C.c_double), ("final_lambda", C.c_double)]
-
-
-class CalibError(ValueError):
+class CalibError(_sidelib.SideLibError):
     """A call of libagt_calib.so returned a negative code."""
-
-    def __init__(self, code, where):
-        self.code = code
-        super().__init__("%s failed: AGT_CALIB_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
+    PREFIX, ERRORS = "CALIB", ERRORS
 
 
-_lib = None
-
-
-def lib():
-    """Load libagt_calib.so (once).  Raises RuntimeError when it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    import torch  # noqa: F401  (its libamdhip64 first: one HIP runtime per process, see hiplib.lib)
-    L = C.CDLL(LIB_PATH)
+def _declare(L):
     vp, f64 = C.c_void_p, C.c_double
     L.agt_calib_version.restype = C.c_int
     L.agt_group_calib_create.argtypes = [C.POINTER(Problem), vp, C.POINTER(vp)]
@@ -71,28 +44,27 @@ def lib():
     L.agt_group_calib_step.argtypes = [vp, f64, vp, vp, vp, vp]
     L.agt_group_calib_default_options.argtypes = [C.POINTER(Options)]
     L.agt_group_calib_solve.argtypes = [vp, C.POINTER(Options), vp, vp, C.POINTER(Report)]
-    _lib = L
-    return L
 
 
-def check(rc, where):
-    if rc != OK:
-        raise CalibError(rc, where)
+_lib = None
 
 
-def _f64(a, shape):
-    a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
-    return a
+def lib():
+    """Load libagt_calib.so (once).  Raises RuntimeError when it is missing."""
+    global _lib
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
-def _addr(a):
-    return C.c_void_p(a.ctypes.data)
+check = CalibError.check
 
 
-class GroupCalib:
+class GroupCalib(_sidelib.Handle):
     """One agt_group_calib handle: a problem checked, sorted and uploaded once.
 
     tag_sizes (T,), anchor: tag index, n_frames: F, obs_frame / obs_tag (n,), obs_corners (n, 4, 2); poses are (., 6) rvec | tvec."""
+    DESTROY = "agt_group_calib_destroy"
 
     def __init__(self, cameraMatrix, distCoeffs, tag_sizes, anchor, n_frames, obs_frame, obs_tag, obs_corners, stream=None):
         self.L = lib()
@@ -109,17 +81,6 @@ class GroupCalib:
                     self.T, _addr(sizes), int(anchor), self.F, self.n, 0, _addr(fr), _addr(tg), _addr(co))
         self.h = C.c_void_p()
         check(self.L.agt_group_calib_create(C.byref(p), C.c_void_p(stream) if stream else None, C.byref(self.h)), "agt_group_calib_create")
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.L.agt_group_calib_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def eval(self, tag_poses, frame_poses):
         """-> (residuals (n, 8) in the caller's observation order, cost)"""

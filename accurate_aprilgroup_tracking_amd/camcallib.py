@@ -1,12 +1,13 @@
 """ctypes binding of the offline camera calibration library (include/agt_camcal.h -> libagt_camcal.so).
-
-Same rules as caliblib: the library is built by `make -C accurate_aprilgroup_tracking_amd/csrc` (build() of __graft_entry__),
-there is NO CPU fallback -- a missing library raises --, and torch is imported first so that one HIP runtime owns the device.
-"""
+Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _sidelib
+from ._sidelib import (Options, Report, STOP_CONVERGED, STOP_MAX_ITERS, STOP_LAMBDA, STOP_NAMES,  # noqa: F401
+                       _f64, _addr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_camcal.so")
@@ -17,8 +18,6 @@ ERR_ARG, ERR_ALLOC, ERR_CAMERA, ERR_HIP, ERR_TOO_FEW, ERR_SINGULAR, ERR_DEGENERA
 ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_CAMERA: "CAMERA", ERR_HIP: "HIP", ERR_TOO_FEW: "TOO_FEW", ERR_SINGULAR: "SINGULAR",
           ERR_DEGENERATE: "DEGENERATE"}
 MAX_VIEWS, MIN_VIEW_POINTS, MAX_VIEW_POINTS, NCAM = 65536, 4, 4096, 16
-STOP_CONVERGED, STOP_MAX_ITERS, STOP_LAMBDA = 1, 2, 3
-STOP_NAMES = {STOP_CONVERGED: "converged", STOP_MAX_ITERS: "iteration cap", STOP_LAMBDA: "damping limit"}
 # the camera vector c[16]
 CAMERA_NAMES = ["fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6", "s1", "s2", "s3", "s4"]
 
@@ -32,38 +31,12 @@ class Problem(C.Structure):
                 ("view_start", C.c_void_p), ("object_points", C.c_void_p), ("image_points", C.c_void_p)]
 
 
-class Options(C.Structure):
-    _fields_ = [("max_iters", C.c_int32), ("reserved0", C.c_int32), ("ftol", C.c_double), ("lambda0", C.c_double),
-                ("lambda_up", C.c_double), ("lambda_down", C.c_double), ("lambda_max", C.c_double)]
-
-
-class Report(C.Structure):
-    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("stop_reason", C.c_int32), ("n_residuals", C.c_int32),
-                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_rms_px", C.c_double), ("final_lambda", C.c_double)]
-
-
-class CamCalError(ValueError):
+class CamCalError(_sidelib.SideLibError):
     """A call of libagt_camcal.so returned a negative code (or camera_calib refused the problem with one)."""
-
-    def __init__(self, code, where):
-        self.code = code
-        super().__init__("%s failed: AGT_CAMCAL_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
+    PREFIX, ERRORS = "CAMCAL", ERRORS
 
 
-_lib = None
-
-
-def lib():
-    """Load libagt_camcal.so (once).  Raises RuntimeError when it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    import torch  # noqa: F401  (its libamdhip64 first: one HIP runtime per process, see hiplib.lib)
-    L = C.CDLL(LIB_PATH)
+def _declare(L):
     vp, f64 = C.c_void_p, C.c_double
     L.agt_camcal_version.restype = C.c_int
     L.agt_camcal_create.argtypes = [C.POINTER(Problem), vp, C.POINTER(vp)]
@@ -72,21 +45,20 @@ def lib():
     L.agt_camcal_step.argtypes = [vp, f64, vp, vp, vp, vp]
     L.agt_camcal_default_options.argtypes = [C.POINTER(Options)]
     L.agt_camcal_solve.argtypes = [vp, C.POINTER(Options), vp, vp, C.POINTER(Report)]
-    _lib = L
-    return L
 
 
-def check(rc, where):
-    if rc != OK:
-        raise CamCalError(rc, where)
+_lib = None
 
 
-def _f64(a, shape):
-    return np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
+def lib():
+    """Load libagt_camcal.so (once).  Raises RuntimeError when it is missing."""
+    global _lib
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
-def _addr(a):
-    return C.c_void_p(a.ctypes.data)
+check = CamCalError.check
 
 
 def pack_views(object_points, image_points):
@@ -102,11 +74,12 @@ def pack_views(object_points, image_points):
     return start, np.ascontiguousarray(X), np.ascontiguousarray(m)
 
 
-class CamCal:
+class CamCal(_sidelib.Handle):
     """One agt_camcal handle: a problem checked and uploaded once.
 
     object_points / image_points: lists of per-view (n_v, 3) / (n_v, 2); free_mask: bit i = entry i of the camera vector
     (CAMERA_NAMES) is estimated; ndist: 0, 4, 5, 8 or 12.  camera is (16,), view poses are (V, 6) rvec | tvec."""
+    DESTROY = "agt_camcal_destroy"
 
     def __init__(self, object_points, image_points, free_mask, ndist, stream=None):
         self.L = lib()
@@ -115,17 +88,6 @@ class CamCal:
         p = Problem(self.V, int(ndist), int(free_mask), 0, _addr(start), _addr(X), _addr(m))
         self.h = C.c_void_p()
         check(self.L.agt_camcal_create(C.byref(p), C.c_void_p(stream) if stream else None, C.byref(self.h)), "agt_camcal_create")
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.L.agt_camcal_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def eval(self, camera, view_poses):
         """-> (residuals (N, 2) in the caller's point order, cost)"""

@@ -2,6 +2,7 @@
 // library's stream pool.  The calls live in agt_api_calls.hip, the tracker in agt_api_tracker.hip, undistortion in
 // agt_api_undistort.hip.
 #include "agt_ctx.h"
+#include "agt_side_math.h"
 #include <new>
 #include <string.h>
 #include <math.h>
@@ -13,29 +14,16 @@ namespace {
 
 int g_last_hip = 0;      // last failing HIP call made without a context (agt_create)
 
-// matTilt | invMatTilt of a coefficient vector (detail::computeTiltProjectionMatrix<double>, distortion_model.hpp; Matx products
-// accumulate s = 0; s += a * b): 14 coefficients = the 12 + the tilted-sensor angles (tau_x, tau_y), which cv2.calibrateCamera returns
-// non-zero only under CALIB_TILTED_MODEL -- the reference calibrates 5 coefficients, calibrate_camera.py:178
+// matTilt | invMatTilt of a coefficient vector (the arithmetic: agt_side_math.h), the identity unless it is tilted: 14 coefficients =
+// the 12 + the tilted-sensor angles (tau_x, tau_y), which cv2.calibrateCamera returns non-zero only under CALIB_TILTED_MODEL -- the
+// reference calibrates 5 coefficients, calibrate_camera.py:178
 void tilt_matrices(const double* dist, int ndist, AgtTiltHost* t)
 {
     static const double I3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
     memcpy(t->m, I3, sizeof(I3)); memcpy(t->m + 9, I3, sizeof(I3));
     t->on = 0;
     if (ndist != 14 || !dist || (dist[12] == 0.0 && dist[13] == 0.0)) return;
-    const double cX = cos(dist[12]), sX = sin(dist[12]), cY = cos(dist[13]), sY = sin(dist[13]);
-    const double rotX[9] = { 1, 0, 0, 0, cX, sX, 0, -sX, cX }, rotY[9] = { cY, 0, -sY, 0, 1, 0, sY, 0, cY };
-    auto mul = [](const double* A, const double* B, double* C) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) { double a = 0; for (int q = 0; q < 3; q++) a += A[i * 3 + q] * B[q * 3 + j]; C[i * 3 + j] = a; }
-    };
-    double rotXY[9];
-    mul(rotY, rotX, rotXY);
-    const double projZ[9] = { rotXY[8], 0, -rotXY[2], 0, rotXY[8], -rotXY[5], 0, 0, 1 };
-    mul(projZ, rotXY, t->m);
-    const double inv = 1. / rotXY[8];
-    const double invProjZ[9] = { inv, 0, inv * rotXY[2], 0, inv, inv * rotXY[5], 0, 0, 1 };
-    const double rt[9] = { rotXY[0], rotXY[3], rotXY[6], rotXY[1], rotXY[4], rotXY[7], rotXY[2], rotXY[5], rotXY[8] };
-    mul(rt, invProjZ, t->m + 9);
+    agt_side::tilt_matrices(dist[12], dist[13], t->m);
     t->on = 1;
 }
 

@@ -20,9 +20,16 @@
 #include <new>
 #include <vector>
 #include "agt_device.h"
+#include "agt_side_buffers.h"
+#include "agt_side_device.h"
 #include "../../include/agt_calib.h"
 
 #pragma clang fp contract(fast)
+
+static_assert(AGT_CALIB_OK == agt_side::OK && AGT_CALIB_ERR_ARG == agt_side::ERR_ARG && AGT_CALIB_ERR_ALLOC == agt_side::ERR_ALLOC &&
+              AGT_CALIB_ERR_HIP == agt_side::ERR_HIP && AGT_CALIB_STOP_CONVERGED == agt_side::STOP_CONVERGED &&
+              AGT_CALIB_STOP_MAX_ITERS == agt_side::STOP_MAX_ITERS && AGT_CALIB_STOP_LAMBDA == agt_side::STOP_LAMBDA,
+              "the shared host code returns this library's codes");
 
 namespace {
 
@@ -128,53 +135,6 @@ __global__ __launch_bounds__(64) void calib_accumulate_kernel(CalibDev P, const 
     }
 }
 
-// LDL^T of a symmetric positive definite 6 x 6 (upper triangle read), factored once per frame and applied to seven right-hand sides.
-// The arithmetic of agt_solve6 with correctly rounded divisions: this is an offline solve held to a numpy reference near FP64
-// round-off, not a link of a per-frame chain, so the reciprocal estimates of the pose solver buy nothing here.
-struct CalibLdl6 { double L[6][6], iD[6]; };
-
-__device__ __forceinline__ bool calib_factor6(const double A[36], CalibLdl6& F)
-{
-    double D[6];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= F.L[j][k] * F.L[j][k] * D[k];
-        if (!(d > 0.0)) ok = false;
-        D[j] = d;
-        F.iD[j] = 1.0 / d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double v = A[j * 6 + i];
-#pragma unroll
-            for (int k = 0; k < j; k++) v -= F.L[i][k] * F.L[j][k] * D[k];
-            F.L[i][j] = v / d;
-        }
-    }
-    return ok;
-}
-
-__device__ __forceinline__ void calib_subst6(const CalibLdl6& F, const double b[6], double x[6])
-{
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) v -= F.L[i][k] * y[k];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double v = y[i] * F.iD[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) v -= F.L[k][i] * x[k];
-        x[i] = v;
-    }
-}
-
 __global__ __launch_bounds__(64) void calib_eliminate_kernel(CalibDev P, CalibSet S, double lambda, double* __restrict__ Y, double* __restrict__ xf, int* __restrict__ fail)
 {
     const int o = blockIdx.x * 64 + threadIdx.x;
@@ -189,14 +149,14 @@ __global__ __launch_bounds__(64) void calib_eliminate_kernel(CalibDev P, CalibSe
     }
 #pragma unroll
     for (int i = 0; i < 6; i++) A[i * 7] += lambda * A[i * 7];
-    CalibLdl6 F;
-    const bool ok = calib_factor6(A, F);
+    AgtLdl6 F;
+    const bool ok = agt_ldl6_factor(A, F);
 #pragma unroll 1
     for (int j = 0; j < 6; j++) {
         double b[6], x[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) b[k] = S.W[(size_t)o * 36 + k * 6 + j];
-        calib_subst6(F, b, x);
+        agt_ldl6_subst(F, b, x);
 #pragma unroll
         for (int k = 0; k < 6; k++) Y[(size_t)o * 36 + k * 6 + j] = x[k];
     }
@@ -208,7 +168,7 @@ __global__ __launch_bounds__(64) void calib_eliminate_kernel(CalibDev P, CalibSe
 #pragma unroll
             for (int k = 0; k < 6; k++) b[k] += S.gf[p * 6 + k];
         }
-        calib_subst6(F, b, x);
+        agt_ldl6_subst(F, b, x);
 #pragma unroll
         for (int k = 0; k < 6; k++) xf[f * 6 + k] = x[k];
     }
@@ -297,71 +257,18 @@ __global__ __launch_bounds__(1024) void calib_cost_kernel(CalibDev P, const doub
         for (int p = P.fstart[f]; p < P.fstart[f + 1]; p++) cf += cost_o[p];
         acc += cf;
     }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
+    agt_block_sum_1024(acc, part);
     if (threadIdx.x == 0) cost_out[0] = part[0];
-}
-
-// matTilt | invMatTilt of the 14-coefficient model (OpenCV's computeTiltProjectionMatrix; products accumulate s = 0; s += a * b)
-void tilt_matrices(double tau_x, double tau_y, double* m)
-{
-    const double cX = cos(tau_x), sX = sin(tau_x), cY = cos(tau_y), sY = sin(tau_y);
-    const double rotX[9] = { 1, 0, 0, 0, cX, sX, 0, -sX, cX }, rotY[9] = { cY, 0, -sY, 0, 1, 0, sY, 0, cY };
-    auto mul = [](const double* A, const double* B, double* C) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) { double a = 0; for (int q = 0; q < 3; q++) a += A[i * 3 + q] * B[q * 3 + j]; C[i * 3 + j] = a; }
-    };
-    double rotXY[9];
-    mul(rotY, rotX, rotXY);
-    const double projZ[9] = { rotXY[8], 0, -rotXY[2], 0, rotXY[8], -rotXY[5], 0, 0, 1 };
-    mul(projZ, rotXY, m);
-    const double inv = 1. / rotXY[8];
-    const double invProjZ[9] = { inv, 0, inv * rotXY[2], 0, inv, inv * rotXY[5], 0, 0, 1 };
-    const double rt[9] = { rotXY[0], rotXY[3], rotXY[6], rotXY[1], rotXY[4], rotXY[7], rotXY[2], rotXY[5], rotXY[8] };
-    mul(rt, invProjZ, m + 9);
-}
-
-// in-place Cholesky A = L L^T (lower triangle of the row-major n x n A), then A x = b in b; false on a non-positive pivot
-bool cholesky_solve(std::vector<double>& A, std::vector<double>& b, int n)
-{
-    for (int j = 0; j < n; j++) {
-        double d = A[(size_t)j * n + j];
-        for (int k = 0; k < j; k++) d -= A[(size_t)j * n + k] * A[(size_t)j * n + k];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        d = sqrt(d);
-        A[(size_t)j * n + j] = d;
-        for (int i = j + 1; i < n; i++) {
-            double v = A[(size_t)i * n + j];
-            for (int k = 0; k < j; k++) v -= A[(size_t)i * n + k] * A[(size_t)j * n + k];
-            A[(size_t)i * n + j] = v / d;
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        double v = b[i];
-        for (int k = 0; k < i; k++) v -= A[(size_t)i * n + k] * b[k];
-        b[i] = v / A[(size_t)i * n + i];
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double v = b[i];
-        for (int k = i + 1; k < n; k++) v -= A[(size_t)k * n + i] * b[k];
-        b[i] = v / A[(size_t)i * n + i];
-    }
-    return true;
 }
 
 }  // namespace
 
 struct agt_group_calib {
-    hipStream_t stream;
+    AgtSideBuffers dev;
     CalibDev P;
     int T, F, n, anchor, n_pairs, n_used_frames;
     std::vector<int> perm;             // sorted row -> the caller's row
     std::vector<int> pairs;            // (t1, t2), t1 <= t2, neither the anchor
-    std::vector<void*> allocs;
     CalibSet set[2];
     double *d_tag[2], *d_frame[2];
     double *d_Y, *d_xf, *d_S, *d_rhs, *d_dtag, *d_dframe, *d_cost, *d_tilt;
@@ -371,41 +278,15 @@ struct agt_group_calib {
 
 namespace {
 
-int dev_alloc(agt_group_calib* h, void** p, size_t bytes)
-{
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return AGT_CALIB_ERR_ALLOC; }
-    h->allocs.push_back(*p);
-    return AGT_CALIB_OK;
-}
-
-#define HC(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); return AGT_CALIB_ERR_HIP; } } while (0)
-#define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
-int upload(agt_group_calib* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return AGT_CALIB_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-    HC(hipStreamSynchronize(h->stream));          // (the source is the caller's or a local: it must be read before this returns)
-    return AGT_CALIB_OK;
-}
-
-int download(agt_group_calib* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return AGT_CALIB_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HC(hipStreamSynchronize(h->stream));
-    return AGT_CALIB_OK;
-}
-
 inline int blocks64(int n) { return (n + 63) / 64; }
 
 // residuals, Jacobian products and the cost of set s at (d_tag[s], d_frame[s])
 int accumulate(agt_group_calib* h, int s, double* cost)
 {
-    if (h->n) calib_accumulate_kernel<<<blocks64(h->n), 64, 0, h->stream>>>(h->P, h->d_tag[s], h->d_frame[s], h->set[s]);
-    calib_cost_kernel<<<1, 1024, 0, h->stream>>>(h->P, h->set[s].cost, h->d_cost);
+    if (h->n) calib_accumulate_kernel<<<blocks64(h->n), 64, 0, h->dev.stream>>>(h->P, h->d_tag[s], h->d_frame[s], h->set[s]);
+    calib_cost_kernel<<<1, 1024, 0, h->dev.stream>>>(h->P, h->set[s].cost, h->d_cost);
     HC(hipGetLastError());
-    return download(h, cost, h->d_cost, sizeof(double));
+    return h->dev.download(cost, h->d_cost, sizeof(double));
 }
 
 // the damped step at set s: d_tag (host, T x 6) and, on the device, d_dframe and the trial frame poses in d_frame[1 - s]
@@ -413,17 +294,17 @@ int damped_step(agt_group_calib* h, int s, double lambda, std::vector<double>& d
 {
     const int T = h->T, nr = 6 * (T - 1);
     *solved = false;
-    HC(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));
-    if (h->n) calib_eliminate_kernel<<<blocks64(h->n), 64, 0, h->stream>>>(h->P, h->set[s], lambda, h->d_Y, h->d_xf, h->d_fail);
+    HC(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->dev.stream));
+    if (h->n) calib_eliminate_kernel<<<blocks64(h->n), 64, 0, h->dev.stream>>>(h->P, h->set[s], lambda, h->d_Y, h->d_xf, h->d_fail);
     if (h->n_pairs)
-        calib_reduce_kernel<<<h->n_pairs, 64 * CALIB_SEGMENTS, 0, h->stream>>>(h->P, h->set[s], h->d_pairs, lambda, h->d_Y, h->d_xf, h->d_S, h->d_rhs);
+        calib_reduce_kernel<<<h->n_pairs, 64 * CALIB_SEGMENTS, 0, h->dev.stream>>>(h->P, h->set[s], h->d_pairs, lambda, h->d_Y, h->d_xf, h->d_S, h->d_rhs);
     HC(hipGetLastError());
     std::vector<double> blk((size_t)h->n_pairs * 36), rhs((size_t)T * 6, 0.0);
     int fail = 0;
-    HC(hipMemcpyAsync(blk.data(), h->d_S, blk.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HC(hipMemcpyAsync(rhs.data(), h->d_rhs, rhs.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HC(hipMemcpyAsync(&fail, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HC(hipStreamSynchronize(h->stream));
+    HC(hipMemcpyAsync(blk.data(), h->d_S, blk.size() * sizeof(double), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipMemcpyAsync(rhs.data(), h->d_rhs, rhs.size() * sizeof(double), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipMemcpyAsync(&fail, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipStreamSynchronize(h->dev.stream));
     if (fail) return AGT_CALIB_OK;
     std::vector<double> A((size_t)nr * nr, 0.0), b(nr, 0.0);
     auto ri = [&](int t) { return t < h->anchor ? t : t - 1; };
@@ -439,13 +320,13 @@ int damped_step(agt_group_calib* h, int s, double lambda, std::vector<double>& d
     for (int t = 0; t < T; t++)
         if (t != h->anchor)
             for (int i = 0; i < 6; i++) b[ri(t) * 6 + i] = -rhs[t * 6 + i];
-    if (nr && !cholesky_solve(A, b, nr)) return AGT_CALIB_OK;
+    if (nr && !agt_side::cholesky_solve(A, b, nr)) return AGT_CALIB_OK;
     d_tag.assign((size_t)T * 6, 0.0);
     for (int t = 0; t < T; t++)
         if (t != h->anchor)
             for (int i = 0; i < 6; i++) d_tag[t * 6 + i] = b[ri(t) * 6 + i];
-    RC(upload(h, h->d_dtag, d_tag.data(), d_tag.size() * sizeof(double)));
-    calib_backsub_kernel<<<blocks64(h->F), 64, 0, h->stream>>>(h->P, h->d_Y, h->d_xf, h->d_dtag, h->d_frame[s], h->d_dframe, h->d_frame[1 - s]);
+    RC(h->dev.upload(h->d_dtag, d_tag.data(), d_tag.size() * sizeof(double)));
+    calib_backsub_kernel<<<blocks64(h->F), 64, 0, h->dev.stream>>>(h->P, h->d_Y, h->d_xf, h->d_dtag, h->d_frame[s], h->d_dframe, h->d_frame[1 - s]);
     HC(hipGetLastError());
     *solved = true;
     return AGT_CALIB_OK;
@@ -460,15 +341,14 @@ int agt_calib_version(void) { return AGT_CALIB_VERSION; }
 int agt_group_calib_default_options(agt_calib_options* o)
 {
     if (!o) return AGT_CALIB_ERR_ARG;
-    memset(o, 0, sizeof(*o));
-    o->max_iters = 50; o->ftol = 1e-14; o->lambda0 = 1e-3; o->lambda_up = 10.0; o->lambda_down = 0.1; o->lambda_max = 1e12;
+    agt_side::lm_default_options(o);
     return AGT_CALIB_OK;
 }
 
 int agt_group_calib_destroy(agt_group_calib* h)
 {
     if (!h) return AGT_CALIB_OK;
-    for (void* p : h->allocs) (void)hipFree(p);
+    h->dev.free_all();
     delete h;
     return AGT_CALIB_OK;
 }
@@ -489,7 +369,7 @@ int agt_group_calib_create(const agt_calib_problem* pr, void* stream, agt_group_
 
     agt_group_calib* h = new (std::nothrow) agt_group_calib();
     if (!h) return AGT_CALIB_ERR_ALLOC;
-    h->stream = (hipStream_t)stream; h->T = T; h->F = F; h->n = n; h->anchor = pr->anchor; h->cur = 0;
+    h->dev.stream = (hipStream_t)stream; h->T = T; h->F = F; h->n = n; h->anchor = pr->anchor; h->cur = 0;
     // ---- host side: sort by frame (stable), the (tag, frame) table, the refusals -- before any device work
     std::vector<int> fstart(F + 1, 0), obs_of((size_t)T * F, -1), tag_s(n), frame_s(n);
     std::vector<double> corners_s((size_t)n * 8);
@@ -543,7 +423,7 @@ int agt_group_calib_create(const agt_calib_problem* pr, void* stream, agt_group_
     int *d_tag_s, *d_frame_s, *d_fstart, *d_obs_of;
     double *d_corners, *d_sizes;
     int rc = AGT_CALIB_OK;
-    auto A = [&](void** p, size_t bytes) { if (!rc) rc = dev_alloc(h, p, bytes); };
+    auto A = [&](void** p, size_t bytes) { if (!rc) rc = h->dev.alloc(p, bytes); };
     const size_t nn = (size_t)n;
     A((void**)&d_tag_s, nn * sizeof(int)); A((void**)&d_frame_s, nn * sizeof(int)); A((void**)&d_fstart, (size_t)(F + 1) * sizeof(int));
     A((void**)&d_obs_of, (size_t)T * F * sizeof(int)); A((void**)&d_corners, nn * 8 * sizeof(double)); A((void**)&d_sizes, (size_t)T * sizeof(double));
@@ -558,22 +438,18 @@ int agt_group_calib_create(const agt_calib_problem* pr, void* stream, agt_group_
     A((void**)&h->d_Y, nn * 36 * sizeof(double)); A((void**)&h->d_xf, (size_t)F * 6 * sizeof(double));
     A((void**)&h->d_S, (size_t)h->n_pairs * 36 * sizeof(double)); A((void**)&h->d_rhs, (size_t)T * 6 * sizeof(double));
     A((void**)&h->d_dtag, (size_t)T * 6 * sizeof(double)); A((void**)&h->d_dframe, (size_t)F * 6 * sizeof(double));
-    if (!rc) rc = upload(h, d_tag_s, tag_s.data(), nn * sizeof(int));
-    if (!rc) rc = upload(h, d_frame_s, frame_s.data(), nn * sizeof(int));
-    if (!rc) rc = upload(h, d_fstart, fstart.data(), (size_t)(F + 1) * sizeof(int));
-    if (!rc) rc = upload(h, d_obs_of, obs_of.data(), (size_t)T * F * sizeof(int));
-    if (!rc) rc = upload(h, d_corners, corners_s.data(), nn * 8 * sizeof(double));
-    if (!rc) rc = upload(h, d_sizes, pr->tag_sizes, (size_t)T * sizeof(double));
-    if (!rc) rc = upload(h, h->d_pairs, h->pairs.data(), h->pairs.size() * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_tag_s, tag_s.data(), nn * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_frame_s, frame_s.data(), nn * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_fstart, fstart.data(), (size_t)(F + 1) * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_obs_of, obs_of.data(), (size_t)T * F * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_corners, corners_s.data(), nn * 8 * sizeof(double));
+    if (!rc) rc = h->dev.upload(d_sizes, pr->tag_sizes, (size_t)T * sizeof(double));
+    if (!rc) rc = h->dev.upload(h->d_pairs, h->pairs.data(), h->pairs.size() * sizeof(int));
     CalibDev& P = h->P;
     memset(&P, 0, sizeof(P));
-    P.cam.fx = pr->K[0]; P.cam.fy = pr->K[4]; P.cam.cx = pr->K[2]; P.cam.cy = pr->K[5];
-    for (int i = 0; i < 12; i++) P.cam.k[i] = i < nd ? pr->dist[i] : 0.0;
-    P.cam.tilt = nullptr;
-    if (nd == 14 && (pr->dist[12] != 0.0 || pr->dist[13] != 0.0)) {
-        double m[18];
-        tilt_matrices(pr->dist[12], pr->dist[13], m);
-        if (!rc) rc = upload(h, h->d_tilt, m, sizeof(m));
+    double m[18];
+    if (agt_side::fill_camera(pr->K, pr->dist, nd, P.cam, m)) {
+        if (!rc) rc = h->dev.upload(h->d_tilt, m, sizeof(m));
         P.cam.tilt = h->d_tilt;
     }
     P.n = n; P.F = F; P.T = T;
@@ -587,14 +463,14 @@ int agt_group_calib_eval(agt_group_calib* h, const double* tag_poses, const doub
 {
     if (!h || !tag_poses || !frame_poses) return AGT_CALIB_ERR_ARG;
     const int s = h->cur;
-    RC(upload(h, h->d_tag[s], tag_poses, (size_t)h->T * 6 * sizeof(double)));
-    RC(upload(h, h->d_frame[s], frame_poses, (size_t)h->F * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_tag[s], tag_poses, (size_t)h->T * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_frame[s], frame_poses, (size_t)h->F * 6 * sizeof(double)));
     double cost = 0.0;
     RC(accumulate(h, s, &cost));
     if (cost_out) *cost_out = cost;
     if (residuals_out) {
         std::vector<double> r((size_t)h->n * 8);
-        RC(download(h, r.data(), h->set[s].res, r.size() * sizeof(double)));
+        RC(h->dev.download(r.data(), h->set[s].res, r.size() * sizeof(double)));
         for (int p = 0; p < h->n; p++) memcpy(residuals_out + (size_t)h->perm[p] * 8, &r[(size_t)p * 8], 8 * sizeof(double));
     }
     return AGT_CALIB_OK;
@@ -604,8 +480,8 @@ int agt_group_calib_step(agt_group_calib* h, double lambda, const double* tag_po
 {
     if (!h || !tag_poses || !frame_poses || !d_tags_out || !d_frames_out || !(lambda >= 0.0) || !isfinite(lambda)) return AGT_CALIB_ERR_ARG;
     const int s = h->cur;
-    RC(upload(h, h->d_tag[s], tag_poses, (size_t)h->T * 6 * sizeof(double)));
-    RC(upload(h, h->d_frame[s], frame_poses, (size_t)h->F * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_tag[s], tag_poses, (size_t)h->T * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_frame[s], frame_poses, (size_t)h->F * 6 * sizeof(double)));
     double cost = 0.0;
     RC(accumulate(h, s, &cost));
     std::vector<double> d_tag;
@@ -613,60 +489,38 @@ int agt_group_calib_step(agt_group_calib* h, double lambda, const double* tag_po
     RC(damped_step(h, s, lambda, d_tag, &solved));
     if (!solved) return AGT_CALIB_ERR_SINGULAR;
     memcpy(d_tags_out, d_tag.data(), d_tag.size() * sizeof(double));
-    return download(h, d_frames_out, h->d_dframe, (size_t)h->F * 6 * sizeof(double));
+    return h->dev.download(d_frames_out, h->d_dframe, (size_t)h->F * 6 * sizeof(double));
 }
 
 int agt_group_calib_solve(agt_group_calib* h, const agt_calib_options* options, double* tag_poses, double* frame_poses, agt_calib_report* report)
 {
     if (!h || !tag_poses || !frame_poses) return AGT_CALIB_ERR_ARG;
     agt_calib_options o;
-    agt_group_calib_default_options(&o);
-    if (options) o = *options;
-    if (o.max_iters < 0 || !(o.ftol >= 0.0) || !(o.lambda0 >= 0.0) || !(o.lambda_up > 1.0) || !(o.lambda_down > 0.0) || !(o.lambda_down <= 1.0) ||
-        !(o.lambda_max > 0.0))
-        return AGT_CALIB_ERR_ARG;
+    if (!agt_side::lm_options(options, o)) return AGT_CALIB_ERR_ARG;
     const int T = h->T, F = h->F;
     int s = h->cur;
     std::vector<double> tag(tag_poses, tag_poses + (size_t)T * 6), trial((size_t)T * 6), d_tag;
-    RC(upload(h, h->d_tag[s], tag.data(), tag.size() * sizeof(double)));
-    RC(upload(h, h->d_frame[s], frame_poses, (size_t)F * 6 * sizeof(double)));
-    double cost = 0.0, lambda = o.lambda0;
-    RC(accumulate(h, s, &cost));
-    const double cost0 = cost;
-    int iters = 0, accepted = 0, stop = AGT_CALIB_STOP_MAX_ITERS;
-    while (iters < o.max_iters) {
-        if (cost == 0.0) { stop = AGT_CALIB_STOP_CONVERGED; break; }
-        iters++;
-        bool solved = false;
-        RC(damped_step(h, s, lambda, d_tag, &solved));
-        double cost_trial = INFINITY;
-        if (solved) {
-            for (size_t i = 0; i < tag.size(); i++) trial[i] = tag[i] + d_tag[i];
-            RC(upload(h, h->d_tag[1 - s], trial.data(), trial.size() * sizeof(double)));
-            RC(accumulate(h, 1 - s, &cost_trial));
-        }
-        if (cost_trial < cost) {                        // (NaN fails)
-            const double gain = cost - cost_trial;
-            tag = trial; s = 1 - s; accepted++;
-            const bool done = gain <= o.ftol * cost;
-            cost = cost_trial;
-            lambda *= o.lambda_down;
-            if (done) { stop = AGT_CALIB_STOP_CONVERGED; break; }
-        } else {
-            lambda = lambda > 0.0 ? lambda * o.lambda_up : 1e-6;
-            if (lambda > o.lambda_max) { stop = AGT_CALIB_STOP_LAMBDA; break; }
-        }
-    }
+    RC(h->dev.upload(h->d_tag[s], tag.data(), tag.size() * sizeof(double)));
+    RC(h->dev.upload(h->d_frame[s], frame_poses, (size_t)F * 6 * sizeof(double)));
+    double cost0 = 0.0;
+    RC(accumulate(h, s, &cost0));
+    agt_calib_report rep;
+    RC(agt_side::lm_solve(o, cost0, 8 * h->n,
+        [&](double lambda, double& cost_trial) {
+            bool solved = false;
+            RC(damped_step(h, s, lambda, d_tag, &solved));
+            if (solved) {
+                for (size_t i = 0; i < tag.size(); i++) trial[i] = tag[i] + d_tag[i];
+                RC(h->dev.upload(h->d_tag[1 - s], trial.data(), trial.size() * sizeof(double)));
+                RC(accumulate(h, 1 - s, &cost_trial));
+            }
+            return AGT_CALIB_OK;
+        },
+        [&] { tag = trial; s = 1 - s; }, &rep));
     h->cur = s;
     memcpy(tag_poses, tag.data(), tag.size() * sizeof(double));
-    RC(download(h, frame_poses, h->d_frame[s], (size_t)F * 6 * sizeof(double)));
-    if (report) {
-        memset(report, 0, sizeof(*report));
-        report->iterations = iters; report->accepted = accepted; report->stop_reason = stop; report->n_residuals = 8 * h->n;
-        report->initial_cost = cost0; report->final_cost = cost;
-        report->final_rms_px = h->n ? sqrt(2.0 * cost / (8.0 * (double)h->n)) : 0.0;
-        report->final_lambda = lambda;
-    }
+    RC(h->dev.download(frame_poses, h->d_frame[s], (size_t)F * 6 * sizeof(double)));
+    if (report) *report = rep;
     return AGT_CALIB_OK;
 }
 

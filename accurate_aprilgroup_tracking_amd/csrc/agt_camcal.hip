@@ -21,9 +21,16 @@
 #include <new>
 #include <vector>
 #include "agt_device.h"
+#include "agt_side_buffers.h"
+#include "agt_side_device.h"
 #include "../../include/agt_camcal.h"
 
 #pragma clang fp contract(fast)
+
+static_assert(AGT_CAMCAL_OK == agt_side::OK && AGT_CAMCAL_ERR_ARG == agt_side::ERR_ARG && AGT_CAMCAL_ERR_ALLOC == agt_side::ERR_ALLOC &&
+              AGT_CAMCAL_ERR_HIP == agt_side::ERR_HIP && AGT_CAMCAL_STOP_CONVERGED == agt_side::STOP_CONVERGED &&
+              AGT_CAMCAL_STOP_MAX_ITERS == agt_side::STOP_MAX_ITERS && AGT_CAMCAL_STOP_LAMBDA == agt_side::STOP_LAMBDA,
+              "the shared host code returns this library's codes");
 
 namespace {
 
@@ -108,52 +115,6 @@ __global__ __launch_bounds__(64) void camcal_accumulate_kernel(CamcalDev P, AgtC
     }
 }
 
-// LDL^T of a symmetric positive definite 6 x 6 (upper triangle read) and its substitution: the arithmetic of calib_factor6 /
-// calib_subst6 (agt_calib.hip), correctly rounded divisions -- an offline solve held to a numpy reference near FP64 round-off.
-struct CamcalLdl6 { double L[6][6], iD[6]; };
-
-__device__ __forceinline__ bool camcal_factor6(const double A[36], CamcalLdl6& F)
-{
-    double D[6];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= F.L[j][k] * F.L[j][k] * D[k];
-        if (!(d > 0.0)) ok = false;
-        D[j] = d;
-        F.iD[j] = 1.0 / d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double v = A[j * 6 + i];
-#pragma unroll
-            for (int k = 0; k < j; k++) v -= F.L[i][k] * F.L[j][k] * D[k];
-            F.L[i][j] = v / d;
-        }
-    }
-    return ok;
-}
-
-__device__ __forceinline__ void camcal_subst6(const CamcalLdl6& F, const double b[6], double x[6])
-{
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) v -= F.L[i][k] * y[k];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double v = y[i] * F.iD[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) v -= F.L[k][i] * x[k];
-        x[i] = v;
-    }
-}
-
 // Y: V x 96 [pose parameter][camera entry], xv: V x 6, C: V x 256 = B_v Y_v, rv: V x 16 = B_v x_v
 __global__ __launch_bounds__(64) void camcal_eliminate_kernel(CamcalDev P, CamcalSet S, double lambda, double* __restrict__ Y, double* __restrict__ xv,
                                                               double* __restrict__ C, double* __restrict__ rv, int* __restrict__ fail)
@@ -168,13 +129,13 @@ __global__ __launch_bounds__(64) void camcal_eliminate_kernel(CamcalDev P, Camca
         for (int j = 0; j < 6; j++) A[i * 6 + j] = j >= i ? H[camcal_tri(CAMCAL_NC + i, CAMCAL_NC + j)] : 0.0;
 #pragma unroll
     for (int i = 0; i < 6; i++) A[i * 7] += lambda * A[i * 7];
-    CamcalLdl6 F;
-    const bool ok = camcal_factor6(A, F);
+    AgtLdl6 F;
+    const bool ok = agt_ldl6_factor(A, F);
     if (lane <= CAMCAL_NC) {           // lane c < 16: column c of Y_v (right-hand side: row c of B_v); lane 16: x_v (g_v)
         double b[6], x[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) b[k] = lane < CAMCAL_NC ? H[camcal_tri(lane, CAMCAL_NC + k)] : H[camcal_tri(CAMCAL_NC + k, CAMCAL_NJ)];
-        camcal_subst6(F, b, x);
+        agt_ldl6_subst(F, b, x);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             sY[lane][k] = x[k];
@@ -253,41 +214,8 @@ __global__ __launch_bounds__(1024) void camcal_cost_kernel(CamcalDev P, const do
     __shared__ double part[1024];
     double acc = 0.0;
     for (int v = threadIdx.x; v < P.V; v += 1024) acc += cost_v[v];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
+    agt_block_sum_1024(acc, part);
     if (threadIdx.x == 0) cost_out[0] = part[0];
-}
-
-// in-place Cholesky A = L L^T (lower triangle of the row-major n x n A), then A x = b in b; false on a non-positive pivot
-bool cholesky_solve(std::vector<double>& A, std::vector<double>& b, int n)
-{
-    for (int j = 0; j < n; j++) {
-        double d = A[(size_t)j * n + j];
-        for (int k = 0; k < j; k++) d -= A[(size_t)j * n + k] * A[(size_t)j * n + k];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        d = sqrt(d);
-        A[(size_t)j * n + j] = d;
-        for (int i = j + 1; i < n; i++) {
-            double v = A[(size_t)i * n + j];
-            for (int k = 0; k < j; k++) v -= A[(size_t)i * n + k] * A[(size_t)j * n + k];
-            A[(size_t)i * n + j] = v / d;
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        double v = b[i];
-        for (int k = 0; k < i; k++) v -= A[(size_t)i * n + k] * b[k];
-        b[i] = v / A[(size_t)i * n + i];
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double v = b[i];
-        for (int k = i + 1; k < n; k++) v -= A[(size_t)k * n + i] * b[k];
-        b[i] = v / A[(size_t)i * n + i];
-    }
-    return true;
 }
 
 AgtCamera make_camera(const double* c)
@@ -302,12 +230,11 @@ AgtCamera make_camera(const double* c)
 }  // namespace
 
 struct agt_camcal {
-    hipStream_t stream;
+    AgtSideBuffers dev;
     CamcalDev P;
     int V, N;
     unsigned free_mask;
     std::vector<int> free_idx;         // the estimated entries of c, ascending
-    std::vector<void*> allocs;
     CamcalSet set[2];
     double* d_pose[2];
     double *d_Y, *d_xv, *d_C, *d_rv, *d_S, *d_rhs, *d_dcam, *d_dview, *d_cost;
@@ -317,55 +244,29 @@ struct agt_camcal {
 
 namespace {
 
-int dev_alloc(agt_camcal* h, void** p, size_t bytes)
-{
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return AGT_CAMCAL_ERR_ALLOC; }
-    h->allocs.push_back(*p);
-    return AGT_CAMCAL_OK;
-}
-
-#define HC(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); return AGT_CAMCAL_ERR_HIP; } } while (0)
-#define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
-int upload(agt_camcal* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return AGT_CAMCAL_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-    HC(hipStreamSynchronize(h->stream));          // (the source is the caller's or a local: it must be read before this returns)
-    return AGT_CAMCAL_OK;
-}
-
-int download(agt_camcal* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return AGT_CAMCAL_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HC(hipStreamSynchronize(h->stream));
-    return AGT_CAMCAL_OK;
-}
-
 // residuals, the views' blocks and the cost of set s at (camera, d_pose[s])
 int accumulate(agt_camcal* h, int s, const double* camera, double* cost)
 {
-    camcal_accumulate_kernel<<<h->V, 64, 0, h->stream>>>(h->P, make_camera(camera), h->d_pose[s], h->set[s]);
-    camcal_cost_kernel<<<1, 1024, 0, h->stream>>>(h->P, h->set[s].cost, h->d_cost);
+    camcal_accumulate_kernel<<<h->V, 64, 0, h->dev.stream>>>(h->P, make_camera(camera), h->d_pose[s], h->set[s]);
+    camcal_cost_kernel<<<1, 1024, 0, h->dev.stream>>>(h->P, h->set[s].cost, h->d_cost);
     HC(hipGetLastError());
-    return download(h, cost, h->d_cost, sizeof(double));
+    return h->dev.download(cost, h->d_cost, sizeof(double));
 }
 
 // the damped step at set s: d_cam (host, 16; exactly 0 for a fixed entry) and, on the device, d_dview and the trial poses in d_pose[1 - s]
 int damped_step(agt_camcal* h, int s, double lambda, double* d_cam, bool* solved)
 {
     *solved = false;
-    HC(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));
-    camcal_eliminate_kernel<<<h->V, 64, 0, h->stream>>>(h->P, h->set[s], lambda, h->d_Y, h->d_xv, h->d_C, h->d_rv, h->d_fail);
-    camcal_reduce_kernel<<<(CAMCAL_RED + 63) / 64, 64 * CAMCAL_SEGMENTS, 0, h->stream>>>(h->P, h->set[s], lambda, h->d_C, h->d_rv, h->d_S, h->d_rhs);
+    HC(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->dev.stream));
+    camcal_eliminate_kernel<<<h->V, 64, 0, h->dev.stream>>>(h->P, h->set[s], lambda, h->d_Y, h->d_xv, h->d_C, h->d_rv, h->d_fail);
+    camcal_reduce_kernel<<<(CAMCAL_RED + 63) / 64, 64 * CAMCAL_SEGMENTS, 0, h->dev.stream>>>(h->P, h->set[s], lambda, h->d_C, h->d_rv, h->d_S, h->d_rhs);
     HC(hipGetLastError());
     double Sm[256], rhs[CAMCAL_NC];
     int fail = 0;
-    HC(hipMemcpyAsync(Sm, h->d_S, sizeof(Sm), hipMemcpyDeviceToHost, h->stream));
-    HC(hipMemcpyAsync(rhs, h->d_rhs, sizeof(rhs), hipMemcpyDeviceToHost, h->stream));
-    HC(hipMemcpyAsync(&fail, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HC(hipStreamSynchronize(h->stream));
+    HC(hipMemcpyAsync(Sm, h->d_S, sizeof(Sm), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipMemcpyAsync(rhs, h->d_rhs, sizeof(rhs), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipMemcpyAsync(&fail, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->dev.stream));
+    HC(hipStreamSynchronize(h->dev.stream));
     if (fail) return AGT_CAMCAL_OK;
     const int nf = (int)h->free_idx.size();
     std::vector<double> A((size_t)nf * nf), b(nf);
@@ -373,14 +274,14 @@ int damped_step(agt_camcal* h, int s, double lambda, double* d_cam, bool* solved
         b[i] = -rhs[h->free_idx[i]];
         for (int j = 0; j < nf; j++) A[(size_t)i * nf + j] = Sm[h->free_idx[i] * CAMCAL_NC + h->free_idx[j]];
     }
-    if (nf && !cholesky_solve(A, b, nf)) return AGT_CAMCAL_OK;
+    if (nf && !agt_side::cholesky_solve(A, b, nf)) return AGT_CAMCAL_OK;
     for (int i = 0; i < CAMCAL_NC; i++) d_cam[i] = 0.0;
     for (int i = 0; i < nf; i++) {
         if (!isfinite(b[i])) return AGT_CAMCAL_OK;
         d_cam[h->free_idx[i]] = b[i];
     }
-    RC(upload(h, h->d_dcam, d_cam, CAMCAL_NC * sizeof(double)));
-    camcal_backsub_kernel<<<(h->V + 63) / 64, 64, 0, h->stream>>>(h->P, h->d_Y, h->d_xv, h->d_dcam, h->d_pose[s], h->d_dview, h->d_pose[1 - s]);
+    RC(h->dev.upload(h->d_dcam, d_cam, CAMCAL_NC * sizeof(double)));
+    camcal_backsub_kernel<<<(h->V + 63) / 64, 64, 0, h->dev.stream>>>(h->P, h->d_Y, h->d_xv, h->d_dcam, h->d_pose[s], h->d_dview, h->d_pose[1 - s]);
     HC(hipGetLastError());
     *solved = true;
     return AGT_CAMCAL_OK;
@@ -395,15 +296,14 @@ int agt_camcal_version(void) { return AGT_CAMCAL_VERSION; }
 int agt_camcal_default_options(agt_camcal_options* o)
 {
     if (!o) return AGT_CAMCAL_ERR_ARG;
-    memset(o, 0, sizeof(*o));
-    o->max_iters = 50; o->ftol = 1e-14; o->lambda0 = 1e-3; o->lambda_up = 10.0; o->lambda_down = 0.1; o->lambda_max = 1e12;
+    agt_side::lm_default_options(o);
     return AGT_CAMCAL_OK;
 }
 
 int agt_camcal_destroy(agt_camcal* h)
 {
     if (!h) return AGT_CAMCAL_OK;
-    for (void* p : h->allocs) (void)hipFree(p);
+    h->dev.free_all();
     delete h;
     return AGT_CAMCAL_OK;
 }
@@ -429,13 +329,13 @@ int agt_camcal_create(const agt_camcal_problem* pr, void* stream, agt_camcal** o
 
     agt_camcal* h = new (std::nothrow) agt_camcal();
     if (!h) return AGT_CAMCAL_ERR_ALLOC;
-    h->stream = (hipStream_t)stream; h->V = V; h->N = N; h->free_mask = pr->free_mask; h->cur = 0;
+    h->dev.stream = (hipStream_t)stream; h->V = V; h->N = N; h->free_mask = pr->free_mask; h->cur = 0;
     for (int i = 0; i < CAMCAL_NC; i++) if ((pr->free_mask >> i) & 1) h->free_idx.push_back(i);
     // ---- device side
     int* d_vstart;
     double *d_X, *d_obs;
     int rc = AGT_CAMCAL_OK;
-    auto A = [&](void** p, size_t bytes) { if (!rc) rc = dev_alloc(h, p, bytes); };
+    auto A = [&](void** p, size_t bytes) { if (!rc) rc = h->dev.alloc(p, bytes); };
     const size_t nn = (size_t)N, vv = (size_t)V;
     A((void**)&d_vstart, (vv + 1) * sizeof(int)); A((void**)&d_X, nn * 3 * sizeof(double)); A((void**)&d_obs, nn * 2 * sizeof(double));
     A((void**)&h->d_fail, sizeof(int)); A((void**)&h->d_cost, sizeof(double));
@@ -447,9 +347,9 @@ int agt_camcal_create(const agt_camcal_problem* pr, void* stream, agt_camcal** o
     A((void**)&h->d_C, vv * 256 * sizeof(double)); A((void**)&h->d_rv, vv * CAMCAL_NC * sizeof(double));
     A((void**)&h->d_S, 256 * sizeof(double)); A((void**)&h->d_rhs, CAMCAL_NC * sizeof(double));
     A((void**)&h->d_dcam, CAMCAL_NC * sizeof(double)); A((void**)&h->d_dview, vv * 6 * sizeof(double));
-    if (!rc) rc = upload(h, d_vstart, pr->view_start, (vv + 1) * sizeof(int));
-    if (!rc) rc = upload(h, d_X, pr->object_points, nn * 3 * sizeof(double));
-    if (!rc) rc = upload(h, d_obs, pr->image_points, nn * 2 * sizeof(double));
+    if (!rc) rc = h->dev.upload(d_vstart, pr->view_start, (vv + 1) * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_X, pr->object_points, nn * 3 * sizeof(double));
+    if (!rc) rc = h->dev.upload(d_obs, pr->image_points, nn * 2 * sizeof(double));
     CamcalDev& P = h->P;
     memset(&P, 0, sizeof(P));
     P.V = V; P.vstart = d_vstart; P.X = d_X; P.obs = d_obs;
@@ -462,11 +362,11 @@ int agt_camcal_eval(agt_camcal* h, const double* camera, const double* view_pose
 {
     if (!h || !camera || !view_poses) return AGT_CAMCAL_ERR_ARG;
     const int s = h->cur;
-    RC(upload(h, h->d_pose[s], view_poses, (size_t)h->V * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_pose[s], view_poses, (size_t)h->V * 6 * sizeof(double)));
     double cost = 0.0;
     RC(accumulate(h, s, camera, &cost));
     if (cost_out) *cost_out = cost;
-    if (residuals_out) RC(download(h, residuals_out, h->set[s].res, (size_t)h->N * 2 * sizeof(double)));
+    if (residuals_out) RC(h->dev.download(residuals_out, h->set[s].res, (size_t)h->N * 2 * sizeof(double)));
     return AGT_CAMCAL_OK;
 }
 
@@ -474,67 +374,45 @@ int agt_camcal_step(agt_camcal* h, double lambda, const double* camera, const do
 {
     if (!h || !camera || !view_poses || !d_camera_out || !d_views_out || !(lambda >= 0.0) || !isfinite(lambda)) return AGT_CAMCAL_ERR_ARG;
     const int s = h->cur;
-    RC(upload(h, h->d_pose[s], view_poses, (size_t)h->V * 6 * sizeof(double)));
+    RC(h->dev.upload(h->d_pose[s], view_poses, (size_t)h->V * 6 * sizeof(double)));
     double cost = 0.0, d_cam[CAMCAL_NC];
     RC(accumulate(h, s, camera, &cost));
     bool solved = false;
     RC(damped_step(h, s, lambda, d_cam, &solved));
     if (!solved) return AGT_CAMCAL_ERR_SINGULAR;
     memcpy(d_camera_out, d_cam, sizeof(d_cam));
-    return download(h, d_views_out, h->d_dview, (size_t)h->V * 6 * sizeof(double));
+    return h->dev.download(d_views_out, h->d_dview, (size_t)h->V * 6 * sizeof(double));
 }
 
 int agt_camcal_solve(agt_camcal* h, const agt_camcal_options* options, double* camera, double* view_poses, agt_camcal_report* report)
 {
     if (!h || !camera || !view_poses) return AGT_CAMCAL_ERR_ARG;
     agt_camcal_options o;
-    agt_camcal_default_options(&o);
-    if (options) o = *options;
-    if (o.max_iters < 0 || !(o.ftol >= 0.0) || !(o.lambda0 >= 0.0) || !(o.lambda_up > 1.0) || !(o.lambda_down > 0.0) || !(o.lambda_down <= 1.0) ||
-        !(o.lambda_max > 0.0))
-        return AGT_CAMCAL_ERR_ARG;
+    if (!agt_side::lm_options(options, o)) return AGT_CAMCAL_ERR_ARG;
     const int V = h->V;
     int s = h->cur;
     double cam[CAMCAL_NC], trial[CAMCAL_NC], d_cam[CAMCAL_NC];
     memcpy(cam, camera, sizeof(cam));
-    RC(upload(h, h->d_pose[s], view_poses, (size_t)V * 6 * sizeof(double)));
-    double cost = 0.0, lambda = o.lambda0;
-    RC(accumulate(h, s, cam, &cost));
-    const double cost0 = cost;
-    int iters = 0, accepted = 0, stop = AGT_CAMCAL_STOP_MAX_ITERS;
-    while (iters < o.max_iters) {
-        if (cost == 0.0) { stop = AGT_CAMCAL_STOP_CONVERGED; break; }
-        iters++;
-        bool solved = false;
-        RC(damped_step(h, s, lambda, d_cam, &solved));
-        double cost_trial = INFINITY;
-        if (solved) {
-            memcpy(trial, cam, sizeof(cam));        // (a fixed entry is copied, not added to: it keeps its bits, -0.0 included)
-            for (int i : h->free_idx) trial[i] = cam[i] + d_cam[i];
-            RC(accumulate(h, 1 - s, trial, &cost_trial));
-        }
-        if (cost_trial < cost) {                        // (NaN fails)
-            const double gain = cost - cost_trial;
-            memcpy(cam, trial, sizeof(cam)); s = 1 - s; accepted++;
-            const bool done = gain <= o.ftol * cost;
-            cost = cost_trial;
-            lambda *= o.lambda_down;
-            if (done) { stop = AGT_CAMCAL_STOP_CONVERGED; break; }
-        } else {
-            lambda = lambda > 0.0 ? lambda * o.lambda_up : 1e-6;
-            if (lambda > o.lambda_max) { stop = AGT_CAMCAL_STOP_LAMBDA; break; }
-        }
-    }
+    RC(h->dev.upload(h->d_pose[s], view_poses, (size_t)V * 6 * sizeof(double)));
+    double cost0 = 0.0;
+    RC(accumulate(h, s, cam, &cost0));
+    agt_camcal_report rep;
+    RC(agt_side::lm_solve(o, cost0, 2 * h->N,
+        [&](double lambda, double& cost_trial) {
+            bool solved = false;
+            RC(damped_step(h, s, lambda, d_cam, &solved));
+            if (solved) {
+                memcpy(trial, cam, sizeof(cam));        // (a fixed entry is copied, not added to: it keeps its bits, -0.0 included)
+                for (int i : h->free_idx) trial[i] = cam[i] + d_cam[i];
+                RC(accumulate(h, 1 - s, trial, &cost_trial));
+            }
+            return AGT_CAMCAL_OK;
+        },
+        [&] { memcpy(cam, trial, sizeof(cam)); s = 1 - s; }, &rep));
     h->cur = s;
     memcpy(camera, cam, sizeof(cam));
-    RC(download(h, view_poses, h->d_pose[s], (size_t)V * 6 * sizeof(double)));
-    if (report) {
-        memset(report, 0, sizeof(*report));
-        report->iterations = iters; report->accepted = accepted; report->stop_reason = stop; report->n_residuals = 2 * h->N;
-        report->initial_cost = cost0; report->final_cost = cost;
-        report->final_rms_px = sqrt(2.0 * cost / (2.0 * (double)h->N));
-        report->final_lambda = lambda;
-    }
+    RC(h->dev.download(view_poses, h->d_pose[s], (size_t)V * 6 * sizeof(double)));
+    if (report) *report = rep;
     return AGT_CAMCAL_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <new>
 #include <vector>
 #include "agt_pnp_body.h"
+#include "agt_side_buffers.h"
 #include "../../include/agt_model.h"
 
 // No contraction in this file's own arithmetic: the accumulate kernel holds several inlined copies of the per-frame code (one per slot of
@@ -26,6 +27,9 @@
 // open the sums of nine one-frame calls differed from those of one nine-frame call in the last bits.  Every fused operation below is
 // written out.  (agt_project and agt_rodrigues contract inside their own definitions, agt_device.h.)
 #pragma clang fp contract(off)
+
+static_assert(AGT_MODEL_OK == agt_side::OK && AGT_MODEL_ERR_ARG == agt_side::ERR_ARG && AGT_MODEL_ERR_ALLOC == agt_side::ERR_ALLOC &&
+              AGT_MODEL_ERR_HIP == agt_side::ERR_HIP, "the shared host code returns this library's codes");
 
 namespace {
 
@@ -196,31 +200,11 @@ __global__ __launch_bounds__(MODEL_BLOCK) void model_accumulate_kernel(ModelDev 
     else model_walk<false>(P, C, B, cam);
 }
 
-// matTilt | invMatTilt of the 14-coefficient model (OpenCV's computeTiltProjectionMatrix; products accumulate s = 0; s += a * b)
-void tilt_matrices(double tau_x, double tau_y, double* m)
-{
-    const double cX = cos(tau_x), sX = sin(tau_x), cY = cos(tau_y), sY = sin(tau_y);
-    const double rotX[9] = { 1, 0, 0, 0, cX, sX, 0, -sX, cX }, rotY[9] = { cY, 0, -sY, 0, 1, 0, sY, 0, cY };
-    auto mul = [](const double* A, const double* B, double* C) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) { double a = 0; for (int q = 0; q < 3; q++) a += A[i * 3 + q] * B[q * 3 + j]; C[i * 3 + j] = a; }
-    };
-    double rotXY[9];
-    mul(rotY, rotX, rotXY);
-    const double projZ[9] = { rotXY[8], 0, -rotXY[2], 0, rotXY[8], -rotXY[5], 0, 0, 1 };
-    mul(projZ, rotXY, m);
-    const double inv = 1. / rotXY[8];
-    const double invProjZ[9] = { inv, 0, inv * rotXY[2], 0, inv, inv * rotXY[5], 0, 0, 1 };
-    const double rt[9] = { rotXY[0], rotXY[3], rotXY[6], rotXY[1], rotXY[4], rotXY[7], rotXY[2], rotXY[5], rotXY[8] };
-    mul(rt, invProjZ, m + 9);
-}
-
 }  // namespace
 
 struct agt_dense_model {
-    hipStream_t stream;
+    AgtSideBuffers dev;
     ModelDev P;
-    std::vector<void*> allocs;
     int *d_n, *d_rej, *d_nr;
     double *d_S, *d_S2, *d_Sr, *d_S2r, *d_tilt;
     // per-call tables, sized for AGT_MODEL_MAX_COUNT frames
@@ -232,36 +216,6 @@ struct agt_dense_model {
     long long frames;              // the pass's frame counter
 };
 
-namespace {
-
-#define HC(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); return AGT_MODEL_ERR_HIP; } } while (0)
-#define RC(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
-int dev_alloc(agt_dense_model* h, void** p, size_t bytes)
-{
-    if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return AGT_MODEL_ERR_ALLOC; }
-    h->allocs.push_back(*p);
-    return AGT_MODEL_OK;
-}
-
-int upload(agt_dense_model* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return AGT_MODEL_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-    HC(hipStreamSynchronize(h->stream));          // (the source is the caller's or a local: it must be read before this returns)
-    return AGT_MODEL_OK;
-}
-
-int download(agt_dense_model* h, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes || !dst) return AGT_MODEL_OK;
-    HC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HC(hipStreamSynchronize(h->stream));
-    return AGT_MODEL_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int agt_model_version(void) { return AGT_MODEL_VERSION; }
@@ -269,7 +223,7 @@ int agt_model_version(void) { return AGT_MODEL_VERSION; }
 int agt_dense_model_destroy(agt_dense_model* h)
 {
     if (!h) return AGT_MODEL_OK;
-    for (void* p : h->allocs) (void)hipFree(p);
+    h->dev.free_all();
     delete h;
     return AGT_MODEL_OK;
 }
@@ -291,11 +245,11 @@ int agt_dense_model_create(const agt_model_problem* pr, void* stream, agt_dense_
 
     agt_dense_model* h = new (std::nothrow) agt_dense_model();
     if (!h) return AGT_MODEL_ERR_ALLOC;
-    h->stream = (hipStream_t)stream; h->pass_open = false; h->calls = 0; h->frames = 0;
+    h->dev.stream = (hipStream_t)stream; h->pass_open = false; h->calls = 0; h->frames = 0;
     float *d_corners, *d_xyz;
     int* d_tag;
     int rc = AGT_MODEL_OK;
-    auto A = [&](void** p, size_t bytes) { if (!rc) rc = dev_alloc(h, p, bytes); };
+    auto A = [&](void** p, size_t bytes) { if (!rc) rc = h->dev.alloc(p, bytes); };
     const size_t mm = (size_t)M, cnt = AGT_MODEL_MAX_COUNT;
     A((void**)&d_corners, (size_t)T * 12 * sizeof(float)); A((void**)&d_xyz, mm * 3 * sizeof(float)); A((void**)&d_tag, mm * sizeof(int));
     A((void**)&h->d_n, mm * sizeof(int)); A((void**)&h->d_rej, mm * sizeof(int)); A((void**)&h->d_nr, mm * sizeof(int));
@@ -305,18 +259,14 @@ int agt_dense_model_create(const agt_model_problem* pr, void* stream, agt_dense_
     A((void**)&h->d_fidx, cnt * sizeof(int)); A((void**)&h->d_fobs, cnt * sizeof(int));
     A((void**)&h->d_pose, cnt * 6 * sizeof(double)); A((void**)&h->d_rt, cnt * 12 * sizeof(double));
     A((void**)&h->d_vis, cnt * (size_t)T);
-    if (!rc) rc = upload(h, d_corners, pr->tag_corners, (size_t)T * 12 * sizeof(float));
-    if (!rc) rc = upload(h, d_xyz, pr->model_xyz, mm * 3 * sizeof(float));
-    if (!rc) rc = upload(h, d_tag, pr->sample_tag, mm * sizeof(int));
+    if (!rc) rc = h->dev.upload(d_corners, pr->tag_corners, (size_t)T * 12 * sizeof(float));
+    if (!rc) rc = h->dev.upload(d_xyz, pr->model_xyz, mm * 3 * sizeof(float));
+    if (!rc) rc = h->dev.upload(d_tag, pr->sample_tag, mm * sizeof(int));
     ModelDev& P = h->P;
     memset(&P, 0, sizeof(P));
-    P.cam.fx = pr->K[0]; P.cam.fy = pr->K[4]; P.cam.cx = pr->K[2]; P.cam.cy = pr->K[5];
-    for (int i = 0; i < 12; i++) P.cam.k[i] = i < nd ? pr->dist[i] : 0.0;
-    P.cam.tilt = nullptr;
-    if (nd == 14 && (pr->dist[12] != 0.0 || pr->dist[13] != 0.0)) {
-        double m[18];
-        tilt_matrices(pr->dist[12], pr->dist[13], m);
-        if (!rc) rc = upload(h, h->d_tilt, m, sizeof(m));
+    double m[18];
+    if (agt_side::fill_camera(pr->K, pr->dist, nd, P.cam, m)) {
+        if (!rc) rc = h->dev.upload(h->d_tilt, m, sizeof(m));
         P.cam.tilt = h->d_tilt;
     }
     P.w = w; P.h = hgt; P.T = T; P.M = M;
@@ -336,15 +286,15 @@ int agt_dense_model_begin_pass(agt_dense_model* h, double clip_sigma, double sig
     const size_t mm = (size_t)h->P.M;
     if (clip_sigma > 0.0) {
         if (!h->pass_open || h->calls < 1) return AGT_MODEL_ERR_ORDER;
-        HC(hipMemcpyAsync(h->d_nr, h->d_n, mm * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-        HC(hipMemcpyAsync(h->d_Sr, h->d_S, mm * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        HC(hipMemcpyAsync(h->d_S2r, h->d_S2, mm * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HC(hipMemcpyAsync(h->d_nr, h->d_n, mm * sizeof(int), hipMemcpyDeviceToDevice, h->dev.stream));
+        HC(hipMemcpyAsync(h->d_Sr, h->d_S, mm * sizeof(double), hipMemcpyDeviceToDevice, h->dev.stream));
+        HC(hipMemcpyAsync(h->d_S2r, h->d_S2, mm * sizeof(double), hipMemcpyDeviceToDevice, h->dev.stream));
     }
-    HC(hipMemsetAsync(h->d_n, 0, mm * sizeof(int), h->stream));
-    HC(hipMemsetAsync(h->d_rej, 0, mm * sizeof(int), h->stream));
-    HC(hipMemsetAsync(h->d_S, 0, mm * sizeof(double), h->stream));
-    HC(hipMemsetAsync(h->d_S2, 0, mm * sizeof(double), h->stream));
-    HC(hipStreamSynchronize(h->stream));
+    HC(hipMemsetAsync(h->d_n, 0, mm * sizeof(int), h->dev.stream));
+    HC(hipMemsetAsync(h->d_rej, 0, mm * sizeof(int), h->dev.stream));
+    HC(hipMemsetAsync(h->d_S, 0, mm * sizeof(double), h->dev.stream));
+    HC(hipMemsetAsync(h->d_S2, 0, mm * sizeof(double), h->dev.stream));
+    HC(hipStreamSynchronize(h->dev.stream));
     h->P.clip_sigma = clip_sigma; h->P.sigma_floor = sigma_floor;
     h->pass_open = true; h->calls = 0; h->frames = 0;
     return AGT_MODEL_OK;
@@ -366,16 +316,16 @@ int agt_dense_model_accumulate(agt_dense_model* h, const uint8_t* d_frames, size
     const int nu = (int)fidx.size();
     std::vector<int> fobs(nu, 0);
     if (nu) {
-        RC(upload(h, h->d_fidx, fidx.data(), (size_t)nu * sizeof(int)));
-        RC(upload(h, h->d_pose, pose.data(), (size_t)nu * 6 * sizeof(double)));
+        RC(h->dev.upload(h->d_fidx, fidx.data(), (size_t)nu * sizeof(int)));
+        RC(h->dev.upload(h->d_pose, pose.data(), (size_t)nu * 6 * sizeof(double)));
         ModelCall C;
         C.frames = d_frames; C.pitch = pitch; C.frame_stride = frame_stride; C.nu = nu;
         C.fidx = h->d_fidx; C.pose = h->d_pose; C.rt = h->d_rt; C.vis = h->d_vis; C.frame_obs = h->d_fobs;
-        model_frames_kernel<<<nu, 64, 0, h->stream>>>(h->P, C);
-        model_accumulate_kernel<<<(h->P.M + MODEL_BLOCK - 1) / MODEL_BLOCK, MODEL_BLOCK, 0, h->stream>>>(h->P, C, C.rt, C.fidx, C.vis, C.frames);
+        model_frames_kernel<<<nu, 64, 0, h->dev.stream>>>(h->P, C);
+        model_accumulate_kernel<<<(h->P.M + MODEL_BLOCK - 1) / MODEL_BLOCK, MODEL_BLOCK, 0, h->dev.stream>>>(h->P, C, C.rt, C.fidx, C.vis, C.frames);
         HC(hipGetLastError());
-        HC(hipMemcpyAsync(fobs.data(), h->d_fobs, (size_t)nu * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HC(hipStreamSynchronize(h->stream));
+        HC(hipMemcpyAsync(fobs.data(), h->d_fobs, (size_t)nu * sizeof(int), hipMemcpyDeviceToHost, h->dev.stream));
+        HC(hipStreamSynchronize(h->dev.stream));
     }
     h->calls++; h->frames += count;
     if (frame_obs_out) {
@@ -390,10 +340,10 @@ int agt_dense_model_read(agt_dense_model* h, int32_t* n, double* S, double* S2, 
     if (!h) return AGT_MODEL_ERR_ARG;
     if (!h->pass_open) return AGT_MODEL_ERR_ORDER;
     const size_t mm = (size_t)h->P.M;
-    RC(download(h, n, h->d_n, mm * sizeof(int)));
-    RC(download(h, S, h->d_S, mm * sizeof(double)));
-    RC(download(h, S2, h->d_S2, mm * sizeof(double)));
-    return download(h, rejected, h->d_rej, mm * sizeof(int));
+    RC(h->dev.download(n, h->d_n, mm * sizeof(int)));
+    RC(h->dev.download(S, h->d_S, mm * sizeof(double)));
+    RC(h->dev.download(S2, h->d_S2, mm * sizeof(double)));
+    return h->dev.download(rejected, h->d_rej, mm * sizeof(int));
 }
 
 }  // extern "C"

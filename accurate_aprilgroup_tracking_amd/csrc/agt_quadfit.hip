@@ -12,7 +12,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "agt_side_device.h"
 #include "../../include/agt_quadfit.h"
+
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -33,8 +36,6 @@ __device__ __forceinline__ double row_sum(double x)
     for (int m = 8; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
     return x;
 }
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (NaN fails)
 
 // corner j of four held in registers (no indexed private array: no scratch)
 __device__ __forceinline__ double pick(const double (&v)[4], int j) { return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3]; }
@@ -63,7 +64,7 @@ __device__ __forceinline__ double sample(const uint8_t* __restrict__ img, size_t
     const double a = x - fx, b = y - fy;
     const uint8_t* p = img + (size_t)iy * pitch + (size_t)ix;
     const double i00 = p[0], i10 = p[1], i01 = p[pitch], i11 = p[pitch + 1];
-    return (1.0 - a) * (1.0 - b) * i00 + a * (1.0 - b) * i10 + (1.0 - a) * b * i01 + a * b * i11;
+    return agt_blend4(a, b, i00, i10, i01, i11);
 }
 
 __global__ __launch_bounds__(64 * QUAD_WAVES) void quad_refine_kernel(QuadCall C)
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void quad_refine_kernel(QuadCall C
         if (refused == AGT_QUAD_OK) {
             bool fin = true;
 #pragma unroll
-            for (int j = 0; j < 4; j++) fin = fin && finite_d(cx[j]) && finite_d(cy[j]);
+            for (int j = 0; j < 4; j++) fin = fin && agt_finite(cx[j]) && agt_finite(cy[j]);
             if (fin) {
 #pragma unroll
                 for (int j = 0; j < 4; j++) {

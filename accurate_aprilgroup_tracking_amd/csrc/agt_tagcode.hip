@@ -13,7 +13,10 @@
 #include <new>
 #include <vector>
 
+#include "agt_side_device.h"
 #include "../../include/agt_tagcode.h"
+
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -58,8 +61,6 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t x)
     return x;
 }
 
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }      // (NaN fails)
-
 struct Sample { double x, y; bool degenerate, outside; };
 
 __device__ __forceinline__ Sample sample_point(const double (&H)[9], double u, double v, int w, int h)
@@ -68,7 +69,7 @@ __device__ __forceinline__ Sample sample_point(const double (&H)[9], double u, d
     const double den = H[6] * u + H[7] * v + H[8];
     s.x = (H[0] * u + H[1] * v + H[2]) / den;
     s.y = (H[3] * u + H[4] * v + H[5]) / den;
-    s.degenerate = !finite_d(den) || den == 0.0 || !finite_d(s.x) || !finite_d(s.y);
+    s.degenerate = !agt_finite(den) || den == 0.0 || !agt_finite(s.x) || !agt_finite(s.y);
     const double fx = floor(s.x), fy = floor(s.y);
     s.outside = !(fx >= 0.0 && fx <= (double)(w - 2) && fy >= 0.0 && fy <= (double)(h - 2));
     return s;
@@ -81,7 +82,7 @@ __device__ __forceinline__ double bilinear(const uint8_t* __restrict__ img, size
     const double a = s.x - fx, b = s.y - fy;
     const uint8_t* p = img + (size_t)(int)fy * pitch + (size_t)(int)fx;
     const double i00 = p[0], i10 = p[1], i01 = p[pitch], i11 = p[pitch + 1];
-    return (1.0 - a) * (1.0 - b) * i00 + a * (1.0 - b) * i10 + (1.0 - a) * b * i01 + a * b * i11;
+    return agt_blend4(a, b, i00, i10, i01, i11);
 }
 
 __global__ __launch_bounds__(64 * TAG_WAVES) void tag_decode_kernel(TagCall C)

@@ -8,6 +8,8 @@ or `make -C accurate_aprilgroup_tracking_amd/csrc`.
 import ctypes as C
 import os
 
+from . import _sidelib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_hip.so")
 
@@ -62,23 +64,7 @@ class AgtError(ValueError):
         super().__init__("%s failed: AGT_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
 
 
-_lib = None
-
-
-def lib():
-    """Load libagt_hip.so (once).  Raises RuntimeError when the HIP extension is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    # PyTorch-ROCm bundles its own libamdhip64.so.7; load it FIRST so that this library's
-    # NEEDED libamdhip64.so.7 resolves to the same runtime instance (two HIP runtimes in one
-    # process cannot both own the device).
-    import torch  # noqa: F401
-    L = C.CDLL(LIB_PATH)
+def _declare(L):
     vp, i32, f64, sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
     L.agt_version.restype = i32
     L.agt_error_string.restype = C.c_char_p
@@ -140,8 +126,17 @@ def lib():
     L.agt_download.argtypes = [vp, vp, vp, sz]
     L.agt_profile_begin.argtypes = [vp, i32]
     L.agt_profile_end.argtypes = [vp, vp, C.POINTER(i32)]
-    _lib = L
-    return L
+
+
+_lib = None
+
+
+def lib():
+    """Load libagt_hip.so (once).  Raises RuntimeError when the HIP extension is missing."""
+    global _lib
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
 def check(rc, where):

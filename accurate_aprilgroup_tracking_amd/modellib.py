@@ -1,12 +1,12 @@
 """ctypes binding of the dense-model library (include/agt_model.h -> libagt_model.so).
-
-Same rules as hiplib and caliblib: the library is built by `make -C accurate_aprilgroup_tracking_amd/csrc` (build() of __graft_entry__),
-there is NO CPU fallback -- a missing library raises --, and torch is imported first so that one HIP runtime owns the device.
-"""
+Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _sidelib
+from ._sidelib import _addr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_model.so")
@@ -28,12 +28,19 @@ class Problem(C.Structure):
                 ("model_xyz", C.c_void_p), ("sample_tag", C.c_void_p), ("max_view_deg", C.c_double)]
 
 
-class ModelError(ValueError):
+class ModelError(_sidelib.SideLibError):
     """A call of libagt_model.so returned a negative code."""
+    PREFIX, ERRORS = "MODEL", ERRORS
 
-    def __init__(self, code, where):
-        self.code = code
-        super().__init__("%s failed: AGT_MODEL_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
+
+def _declare(L):
+    vp, f64, sz = C.c_void_p, C.c_double, C.c_size_t
+    L.agt_model_version.restype = C.c_int
+    L.agt_dense_model_create.argtypes = [C.POINTER(Problem), vp, C.POINTER(vp)]
+    L.agt_dense_model_destroy.argtypes = [vp]
+    L.agt_dense_model_begin_pass.argtypes = [vp, f64, f64]
+    L.agt_dense_model_accumulate.argtypes = [vp, vp, sz, sz, C.c_int, vp, vp, vp]
+    L.agt_dense_model_read.argtypes = [vp, vp, vp, vp, vp]
 
 
 _lib = None
@@ -42,36 +49,17 @@ _lib = None
 def lib():
     """Load libagt_model.so (once).  Raises RuntimeError when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    import torch  # noqa: F401  (its libamdhip64 first: one HIP runtime per process, see hiplib.lib)
-    L = C.CDLL(LIB_PATH)
-    vp, f64, sz = C.c_void_p, C.c_double, C.c_size_t
-    L.agt_model_version.restype = C.c_int
-    L.agt_dense_model_create.argtypes = [C.POINTER(Problem), vp, C.POINTER(vp)]
-    L.agt_dense_model_destroy.argtypes = [vp]
-    L.agt_dense_model_begin_pass.argtypes = [vp, f64, f64]
-    L.agt_dense_model_accumulate.argtypes = [vp, vp, sz, sz, C.c_int, vp, vp, vp]
-    L.agt_dense_model_read.argtypes = [vp, vp, vp, vp, vp]
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
-def check(rc, where):
-    if rc != OK:
-        raise ModelError(rc, where)
+check = ModelError.check
 
 
-def _addr(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-class DenseModelHandle:
+class DenseModelHandle(_sidelib.Handle):
     """One agt_dense_model handle: a problem checked and uploaded once.  tag_corners (T, 4, 3) f32, model_xyz (M, 3) f32, sample_tag (M,) i32."""
+    DESTROY = "agt_dense_model_destroy"
 
     def __init__(self, cameraMatrix, distCoeffs, width, height, tag_corners, model_xyz, sample_tag, max_view_deg=60.0, facing=1, stream=None):
         self.L = lib()
@@ -87,17 +75,6 @@ class DenseModelHandle:
                     self.width, self.height, self.T, _addr(tc), self.M, int(facing), _addr(xyz), _addr(tag), float(max_view_deg))
         self.h = C.c_void_p()
         check(self.L.agt_dense_model_create(C.byref(p), C.c_void_p(stream) if stream else None, C.byref(self.h)), "agt_dense_model_create")
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.L.agt_dense_model_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def begin_pass(self, clip_sigma=0.0, sigma_floor=0.0):
         check(self.L.agt_dense_model_begin_pass(self.h, float(clip_sigma), float(sigma_floor)), "agt_dense_model_begin_pass")

@@ -1,12 +1,11 @@
 """ctypes binding of the quad edge refinement (include/agt_quadfit.h -> libagt_quadfit.so).
-
-Same rules as tagcodelib: the library is built by `make -C accurate_aprilgroup_tracking_amd/csrc` (build() of __graft_entry__),
-there is NO CPU fallback -- a missing library raises --, and torch is imported first so that one HIP runtime owns the device.
-"""
+Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _sidelib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_quadfit.so")
@@ -26,12 +25,15 @@ assert RECORD_DTYPE.itemsize == 32
 SYMBOLS = ["agt_quadfit_version", "agt_quad_refine"]
 
 
-class QuadFitError(ValueError):
+class QuadFitError(_sidelib.SideLibError):
     """A call of libagt_quadfit.so returned a negative code."""
+    PREFIX, ERRORS = "QUADFIT", ERRORS
 
-    def __init__(self, code, where):
-        self.code = code
-        super().__init__("%s failed: AGT_QUADFIT_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
+
+def _declare(L):
+    vp, i32, sz, f64 = C.c_void_p, C.c_int, C.c_size_t, C.c_double
+    L.agt_quadfit_version.restype = C.c_int
+    L.agt_quad_refine.argtypes = [vp, vp, sz, sz, i32, i32, i32, vp, vp, i32, f64, i32, f64, vp, vp, vp, vp, vp]
 
 
 _lib = None
@@ -40,24 +42,12 @@ _lib = None
 def lib():
     """Load libagt_quadfit.so (once).  Raises RuntimeError when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    import torch  # noqa: F401  (its libamdhip64 first: one HIP runtime per process, see hiplib.lib)
-    L = C.CDLL(LIB_PATH)
-    vp, i32, sz, f64 = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-    L.agt_quadfit_version.restype = C.c_int
-    L.agt_quad_refine.argtypes = [vp, vp, sz, sz, i32, i32, i32, vp, vp, i32, f64, i32, f64, vp, vp, vp, vp, vp]
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
-def check(rc, where):
-    if rc != OK:
-        raise QuadFitError(rc, where)
+check = QuadFitError.check
 
 
 def refine(stream, frames_ptr, pitch, frame_stride, width, height, B, quads_ptr, mask_ptr, Q, range_px, iters, min_strength,

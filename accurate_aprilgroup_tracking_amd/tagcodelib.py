@@ -1,12 +1,11 @@
 """ctypes binding of the tag payload decoder (include/agt_tagcode.h -> libagt_tagcode.so).
-
-Same rules as camcallib: the library is built by `make -C accurate_aprilgroup_tracking_amd/csrc` (build() of __graft_entry__),
-there is NO CPU fallback -- a missing library raises --, and torch is imported first so that one HIP runtime owns the device.
-"""
+Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _sidelib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_tagcode.so")
@@ -27,12 +26,17 @@ assert RECORD_DTYPE.itemsize == 40
 SYMBOLS = ["agt_tagcode_version", "agt_tag_family_create", "agt_tag_family_destroy", "agt_tag_decode"]
 
 
-class TagCodeError(ValueError):
+class TagCodeError(_sidelib.SideLibError):
     """A call of libagt_tagcode.so returned a negative code."""
+    PREFIX, ERRORS = "TAGCODE", ERRORS
 
-    def __init__(self, code, where):
-        self.code = code
-        super().__init__("%s failed: AGT_TAGCODE_ERR_%s (%d)" % (where, ERRORS.get(code, "?"), code))
+
+def _declare(L):
+    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
+    L.agt_tagcode_version.restype = C.c_int
+    L.agt_tag_family_create.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
+    L.agt_tag_family_destroy.argtypes = [vp]
+    L.agt_tag_decode.argtypes = [vp, vp, sz, sz, i32, i32, i32, vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
 
 
 _lib = None
@@ -41,30 +45,17 @@ _lib = None
 def lib():
     """Load libagt_tagcode.so (once).  Raises RuntimeError when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "HIP extension %s is missing: build it (python -c 'import __graft_entry__ as g; g.build()'). "
-            "There is no CPU fallback." % LIB_PATH)
-    import torch  # noqa: F401  (its libamdhip64 first: one HIP runtime per process, see hiplib.lib)
-    L = C.CDLL(LIB_PATH)
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    L.agt_tagcode_version.restype = C.c_int
-    L.agt_tag_family_create.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
-    L.agt_tag_family_destroy.argtypes = [vp]
-    L.agt_tag_decode.argtypes = [vp, vp, sz, sz, i32, i32, i32, vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _sidelib.load(LIB_PATH, _declare)
+    return _lib
 
 
-def check(rc, where):
-    if rc != OK:
-        raise TagCodeError(rc, where)
+check = TagCodeError.check
 
 
-class Family:
+class Family(_sidelib.Handle):
     """One agt_tag_family handle: the codes' four rotations, uploaded once; decodes are enqueued on `stream`."""
+    DESTROY = "agt_tag_family_destroy"
 
     def __init__(self, codes, bits_per_side=6, stream=None):
         self.L = lib()
@@ -73,17 +64,6 @@ class Family:
         self.h = C.c_void_p()
         check(self.L.agt_tag_family_create(C.c_void_p(codes.ctypes.data), self.n, int(bits_per_side), C.c_void_p(stream) if stream else None,
                                            C.byref(self.h)), "agt_tag_family_create")
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h.value:
-            self.L.agt_tag_family_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def decode(self, frames_ptr, pitch, frame_stride, width, height, B, quads_ptr, mask_ptr, Q, expected_ptr, max_hamming, min_margin,
                records_ptr, ok_ptr, corner_mask_ptr, homography_ptr):

@@ -6,7 +6,6 @@ the end-to-end GPU test."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -24,12 +23,6 @@ KERNELS = ["camcal_accumulate_kernel", "camcal_backsub_kernel", "camcal_cost_ker
 LAMBDAS = (0.0, 1e-3, 10.0)
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "agt_camcal.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agt_[a-z0-9_]+)\s*\(", text)))
-
-
 def numpy_start(sc):
     """cv2's start without a guess, on the host: centre, closed-form focal lengths, no distortion; poses by the planar solvePnP statement"""
     from accurate_aprilgroup_tracking_amd import camera_calib as cc
@@ -45,15 +38,9 @@ def numpy_poses(sc, c):
 
 
 def test_camcal_library_builds_exports_and_resources():
-    import __graft_entry__ as g
-    g.build()
+    import side_library
     from accurate_aprilgroup_tracking_amd import camcallib
-    import kernel_resources
-    assert os.path.exists(camcallib.LIB_PATH), "make all does not build libagt_camcal.so"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", camcallib.LIB_PATH], text=True)
-    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
-    assert exported == set(declared_symbols()) == set(camcallib.SYMBOLS)
-    rows = kernel_resources.kernel_rows(camcallib.LIB_PATH)
+    rows = side_library.built(camcallib, "camcal")
     assert [re.search(r"(camcal_\w+)\(", r["name"]).group(1) for r in rows] == KERNELS
     bad = [(r["name"], r["scratch"], r["vgpr"], r["vspill"]) for r in rows if r["scratch"] != 0 or r["vgpr"] > 512 or r["vspill"] != 0]
     assert not bad, bad

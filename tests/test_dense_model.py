@@ -5,7 +5,6 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -26,22 +25,10 @@ KERNELS = ["model_accumulate_kernel", "model_frames_kernel"]
 CAMERAS = {"none": None, "mild": synthetic.MILD_DIST.reshape(-1), "tilt14": calib_scenes.TILT14}
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "agt_model.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agt_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_model_library_builds_exports_and_resources():
-    import __graft_entry__ as g
-    g.build()
+    import side_library
     from accurate_aprilgroup_tracking_amd import modellib
-    import kernel_resources
-    assert os.path.exists(modellib.LIB_PATH), "make all does not build libagt_model.so"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", modellib.LIB_PATH], text=True)
-    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
-    assert exported == set(declared_symbols()) == set(modellib.SYMBOLS)
-    rows = kernel_resources.kernel_rows(modellib.LIB_PATH)
+    rows = side_library.built(modellib, "model")
     assert sorted(re.search(r"(model_\w+)\(", r["name"]).group(1) for r in rows) == KERNELS
     bad = [(r["name"], r["scratch"], r["vgpr"], r["vspill"]) for r in rows if r["scratch"] != 0 or r["vgpr"] > 512 or r["vspill"] != 0]
     assert not bad, bad

@@ -4,7 +4,6 @@ of scratch; the numpy / scipy statement of the bundle adjustment (tests/group_ba
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -22,22 +21,10 @@ KERNELS = ["calib_accumulate_kernel", "calib_backsub_kernel", "calib_cost_kernel
 E2E_PERTURB_DEG = cs.E2E_PERTURB_DEG
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "agt_calib.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agt_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_calib_library_builds_exports_and_resources():
-    import __graft_entry__ as g
-    g.build()
+    import side_library
     from accurate_aprilgroup_tracking_amd import caliblib
-    import kernel_resources
-    assert os.path.exists(caliblib.LIB_PATH), "make all does not build libagt_calib.so"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", caliblib.LIB_PATH], text=True)
-    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
-    assert exported == set(declared_symbols()) == set(caliblib.SYMBOLS)
-    rows = kernel_resources.kernel_rows(caliblib.LIB_PATH)
+    rows = side_library.built(caliblib, "calib")
     assert [re.search(r"(calib_\w+)\(", r["name"]).group(1) for r in rows] == KERNELS
     bad = [(r["name"], r["scratch"], r["vgpr"], r["vspill"]) for r in rows if r["scratch"] != 0 or r["vgpr"] > 512 or r["vspill"] != 0]
     assert not bad, bad

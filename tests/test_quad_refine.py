@@ -4,7 +4,6 @@ that the GPU tests compare with finds the rendered corners, tells a tag's border
 promises."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -20,22 +19,10 @@ import tag_decode_scenes as ts     # noqa: E402
 NOISE, SEED = 1.0, 3
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "agt_quadfit.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agt_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_quadfit_library_builds_exports_and_resources():
-    import __graft_entry__ as g
-    g.build()
+    import side_library
     from accurate_aprilgroup_tracking_amd import quadfitlib
-    import kernel_resources
-    assert os.path.exists(quadfitlib.LIB_PATH), "make all does not build libagt_quadfit.so"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", quadfitlib.LIB_PATH], text=True)
-    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
-    assert exported == set(declared_symbols()) == set(quadfitlib.SYMBOLS)
-    rows = kernel_resources.kernel_rows(quadfitlib.LIB_PATH)
+    rows = side_library.built(quadfitlib, "quadfit")
     assert [re.search(r"(quad_\w+)\(", r["name"]).group(1) for r in rows] == ["quad_refine_kernel"]
     print(rows[0])
     # no private segment, no LDS, and room for four waves per SIMD

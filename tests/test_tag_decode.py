@@ -5,7 +5,6 @@ generator, family file)."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -30,22 +29,10 @@ def cand():
     return tn.candidates(ts.family_codes())
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "agt_tagcode.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agt_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_tagcode_library_builds_exports_and_resources():
-    import __graft_entry__ as g
-    g.build()
+    import side_library
     from accurate_aprilgroup_tracking_amd import tagcodelib
-    import kernel_resources
-    assert os.path.exists(tagcodelib.LIB_PATH), "make all does not build libagt_tagcode.so"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", tagcodelib.LIB_PATH], text=True)
-    exported = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
-    assert exported == set(declared_symbols()) == set(tagcodelib.SYMBOLS)
-    rows = kernel_resources.kernel_rows(tagcodelib.LIB_PATH)
+    rows = side_library.built(tagcodelib, "tagcode")
     assert [re.search(r"(tag_\w+)\(", r["name"]).group(1) for r in rows] == ["tag_decode_kernel"]
     # no private segment, and room for four waves per SIMD
     bad = [(r["name"], r["scratch"], r["vgpr"], r["vspill"]) for r in rows if r["scratch"] != 0 or r["vgpr"] > 128 or r["vspill"] != 0]
