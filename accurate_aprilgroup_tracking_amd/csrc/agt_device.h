@@ -145,13 +145,19 @@ __device__ __forceinline__ void agt_rodrigues(const double r_in[3], double R[9],
     double rx = r_in[0], ry = r_in[1], rz = r_in[2];
     const double t2 = rx * rx + ry * ry + rz * rz;
     const double theta = agt_sqrtp(t2);
-    // theta < DBL_EPSILON: R = I (and G = I: dR/dr_j = [e_j]x at r = 0).  Written as selects on the results, not as an early
-    // return: with two exits the optimiser kept R[0] and G[0] in memory behind a pointer phi -- 32 B of scratch per lane in every
-    // kernel that calls this (1.5 MB of scratch writes per dense launch, a scratch round trip in each LM evaluation).
+    // theta < DBL_EPSILON: R = I (and G = I: dR/dr_j = [e_j]x at r = 0).  Not an early return: with two exits the optimiser kept
+    // R[0] and G[0] in memory behind a pointer phi -- 32 B of scratch per lane in every kernel that calls this (1.5 MB of scratch
+    // writes per dense launch, a scratch round trip in each LM evaluation).  And not selects on the 18 results (36 v_cndmask_b32 in
+    // every LM evaluation, for a case a tracked body never takes): ONE input is selected, the unit axis below (three doubles).
+    //   R: below DBL_EPSILON agt_sincos returns c = 1 exactly (so c1 = 0) and a finite s; with the axis forced to +0 every entry is
+    //      c [k on the diagonal] + 0 * 0 + s * (+-0) = 1 or +0: the identity, bit for bit what the selects wrote.
+    //   G: theta < 1e-2 takes the series, and t2 < 5e-32 leaves a = 1/2, bq = 1/6, d = 1 exactly: the diagonal is 1 + O(t2) = 1, the
+    //      off-diagonal entries are +-r / 2 + O(t2) -- the true derivative's, |.| < 1.2e-16, where the selects wrote 0 (equal at r = 0).
+    // itheta: 1 / 0 = inf at theta = 0, and the NaN of 0 * inf ends in the axis select.  At theta >= DBL_EPSILON no bit changes.
     const bool tiny = theta < DBL_EPSILON;
     double s, c;
     agt_sincos(theta, s, c);
-    const double c1 = 1.0 - c, itheta = agt_rcp(tiny ? 1.0 : theta);
+    const double c1 = 1.0 - c, itheta = agt_rcp(theta);
     if (JAC) {
         // a = (1 - cos t)/t^2, b = (t - sin t)/t^3; series below t = 1e-2 (cancellation), relative error < 1e-16 there
         double a, bq;
@@ -168,16 +174,13 @@ __device__ __forceinline__ void agt_rodrigues(const double r_in[3], double R[9],
                               bq * rx * ry + a * rz, d + bq * ry * ry, bq * ry * rz - a * rx,
                               bq * rx * rz - a * ry, bq * ry * rz + a * rx, d + bq * rz * rz };
 #pragma unroll
-        for (int i = 0; i < 9; i++) G[i] = tiny ? ((i % 4 == 0) ? 1.0 : 0.0) : g[i];
+        for (int i = 0; i < 9; i++) G[i] = g[i];
     }
-    rx *= itheta; ry *= itheta; rz *= itheta;
+    rx = tiny ? 0.0 : rx * itheta; ry = tiny ? 0.0 : ry * itheta; rz = tiny ? 0.0 : rz * itheta;
     const double rrt[9] = { rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz };
     const double r_x[9] = { 0, -rz, ry, rz, 0, -rx, -ry, rx, 0 };
 #pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double v = c * ((k % 4 == 0) ? 1.0 : 0.0) + c1 * rrt[k] + s * r_x[k];
-        R[k] = tiny ? ((k % 4 == 0) ? 1.0 : 0.0) : v;
-    }
+    for (int k = 0; k < 9; k++) R[k] = c * ((k % 4 == 0) ? 1.0 : 0.0) + c1 * rrt[k] + s * r_x[k];
 }
 
 struct AgtCamera {

@@ -103,6 +103,10 @@ __device__ __forceinline__ void wave_reduce_slab(double (&vals)[K], PnpShared& s
 // quad_perm[3,2,1,0] (each pairs lanes that differ in the stage's bit and agree on the higher ones); the last
 // stage adds the xor-1 neighbour.  Afterwards lane l holds the total of value l >> 1.
 // ~125 VALU instructions in 6 short dependent stages, against 28 LDS stores + 32 dependent LDS load/adds.
+// The swaps are tied two-operand instructions and run on the accumulators where the per-point code left them: the listings show no
+// register copy in front of or between them (the 64-bit copies near an evaluation belong to the Horner chains of agt_sincos), and
+// tests/test_pnp_eval_budget.py holds the butterfly part to that (profiles/pose_eval_diet.md).  The four padding values (28..31) cost
+// two v_mov_b32 each: a swap destroys its zero.
 __device__ __forceinline__ double dswap32(double a, double b, double& b_out)
 {
     const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
@@ -1042,20 +1046,31 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
     // mode 0: residuals only.  mode 1: + J^T J / J^T e into the registers.  mode 2: + J^T J / J^T e left in
     // sh.tot as a CANDIDATE (CvLevMarq asks for J at exactly these parameters next, unless the step
     // is rejected or the solve terminates; evaluating it now saves a second projection pass).
+    // Per-lane sums (the 28 of a Jacobian pass, |e|^2 of mode 0, the epilogue's error sum) START from a lane's first point: sum = term,
+    // not sum = 0.0 + term -- without no-signed-zeros the compiler has to keep both the zeroing move and the add, 28 + 28 instructions
+    // of the ~370 a one-point-per-lane Jacobian pass issues.  0.0 + x differs from x for x = -0.0 alone (+0.0 against -0.0), and in the
+    // wave sum a -0.0 partial is absorbed by any partial that is not -0.0 itself, a lane without a point (+0.0) included: a total can
+    // differ, by the sign of a zero, only if all 64 lanes hold a point and every one of them contributes -0.0 to that sum.
     double Rlast[9];
     auto evaluate_t = [&](int mode, auto DIST) -> double {
         constexpr bool D = decltype(DIST)::value;
         const bool needJ = mode != 0;
-        double R[9], G[9];
+        double R[9], G[9], acc[NACC];
         if (mode == 2) PSTAMPM(48);
-        if (needJ) agt_rodrigues<true>(param, R, G); else agt_rodrigues<false>(param, R, G);
+        if (needJ) {
+            // one point per lane: a lane WITHOUT a point hands these zeros to the butterfly.  They are written here, in front of the
+            // wave-uniform Rodrigues section (a dependent chain with free issue slots), and made opaque, so that the per-point path below
+            // neither starts with 28 moves nor adds 28 times to a known zero
+            if constexpr (PPL == 1) {
+#pragma unroll
+                for (int i = 0; i < NACC; i++) { acc[i] = 0.0; asm volatile("" : "+v"(acc[i])); }
+            }
+            agt_rodrigues<true>(param, R, G);
+        } else agt_rodrigues<false>(param, R, G);
 #pragma unroll
         for (int i = 0; i < 9; i++) Rlast[i] = R[i];
         if (mode == 2) PSTAMPM(49);
         if (needJ) {
-            double acc[NACC];
-#pragma unroll
-            for (int i = 0; i < NACC; i++) acc[i] = 0.0;
             // More than one point per lane (N > 64): the points are evaluated WITHOUT a branch around each one -- an unused slot
             // holds the origin and its terms are multiplied by an exact 0 -- so that the compiler may interleave the independent
             // FP64 chains of a lane's points (behind `if (use[q])` each point was its own basic block: 4 x 0.39 us per evaluation
@@ -1069,14 +1084,16 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
                 rex[q] = ex; rey[q] = ey;
                 const double Jx[6] = { jr[0] * m, jr[1] * m, jr[2] * m, jt[0] * m, jt[1] * m, jt[2] * m };
                 const double Jy[6] = { jr[3] * m, jr[4] * m, jr[5] * m, jt[3] * m, jt[4] * m, jt[5] * m };
+                // a lane's first point is assigned, not added to a zero (sum(): the header comment of evaluate_t)
+                auto sum = [&](double& s_, double t_) { if (q == 0) s_ = t_; else s_ += t_; };
                 int idx = 0;
 #pragma unroll
                 for (int a = 0; a < 6; a++) {
 #pragma unroll
-                    for (int c = a; c < 6; c++) acc[idx++] += Jx[a] * Jx[c] + Jy[a] * Jy[c];
-                    acc[21 + a] += Jx[a] * ex + Jy[a] * ey;
+                    for (int c = a; c < 6; c++) sum(acc[idx++], Jx[a] * Jx[c] + Jy[a] * Jy[c]);
+                    sum(acc[21 + a], Jx[a] * ex + Jy[a] * ey);
                 }
-                acc[27] += ex * ex + ey * ey;
+                sum(acc[27], ex * ex + ey * ey);
             }
             if (mode == 2) PSTAMPM(50);
             if constexpr (COOP == 1) wave_reduce_bfly<NACC>(acc, tot, lane);
@@ -1111,7 +1128,7 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
             const double m = (PPL > 1 && !use[q]) ? 0.0 : 1.0;
             const double ex = (u - mu_[q]) * m, ey = (v - mv_[q]) * m;
             rex[q] = ex; rey[q] = ey;
-            e2 += ex * ex + ey * ey;
+            if (q == 0) e2 = ex * ex + ey * ey; else e2 += ex * ex + ey * ey;
         }
         return coop_sum(wave_sum_f64(e2));
     };
@@ -1205,7 +1222,10 @@ __device__ __forceinline__ void pnp_body(const AgtPnpParams& P, int b, PnpShared
     {
         if (tvec_f32) { if (has_dist) residuals_same_rotation(std::true_type{}); else residuals_same_rotation(std::false_type{}); }
 #pragma unroll
-        for (int q = 0; q < PPL; q++) if (use[q]) esum += sqrt(rex[q] * rex[q] + rey[q] * rey[q]);
+        for (int q = 0; q < PPL; q++) if (use[q]) {
+            const double d = sqrt(rex[q] * rex[q] + rey[q] * rey[q]);
+            if (q == 0) esum = d; else esum += d;
+        }
         esum = coop_sum(wave_sum_f64(esum)) / n_used;
     }
     PSTAMP(4);

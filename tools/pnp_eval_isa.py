@@ -151,9 +151,18 @@ def region_stats(lines):
     return n, valu, counts, longest
 
 
-def main():
-    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "accurate_aprilgroup_tracking_amd", "libagt_hip_dbg.so")
-    want = "pnp_kernel<float, 1>"
+DBG_LIB = os.path.join(ROOT, "accurate_aprilgroup_tracking_amd", "libagt_hip_dbg.so")
+PARTS = ("rodrigues", "projection", "butterfly")
+
+
+def evaluation_regions(lib=DBG_LIB, want="pnp_kernel<float, 1>"):
+    """the inlined mode-2 evaluations of kernel `want`: one dict per complete 48 .. 51 run, part name -> the hot-path ISA lines between
+    two stamps (tests/test_pnp_eval_budget.py counts in these)"""
+    body, runs = kernel_runs(lib, want)
+    return [{nm: hot_path(body[lo + 1:hi]) for nm, (lo, hi) in zip(PARTS, ((a, b), (b, c), (c, d)))} for a, b, c, d in runs]
+
+
+def kernel_runs(lib, want):
     body = None
     with tempfile.TemporaryDirectory() as tmp:
         for co in code_objects(lib, tmp):
@@ -187,6 +196,12 @@ def main():
         if m0:
             break
     hot_path.base = int(m0.group(1), 16) if m0 else 0
+    return body, runs
+
+
+def main():
+    lib = sys.argv[1] if len(sys.argv) > 1 else DBG_LIB
+    body, runs = kernel_runs(lib, "pnp_kernel<float, 1>")
     print("# One Levenberg-Marquardt evaluation of the pose solver, instruction by instruction (`pnp_kernel<float, 1>`, diagnostic library)\n")
     print("`tools/pnp_eval_isa.py`: the code between the in-kernel stamps 48 | 49 | 50 | 51 of `agt_pnp_body.h evaluate_t` (mode 2: the")
     print("evaluation that also leaves J^T J / J^T e for the next iteration).  One point per lane, 48 of 64 lanes active, one wave per problem.")
