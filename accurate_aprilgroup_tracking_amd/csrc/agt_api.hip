@@ -1,6 +1,6 @@
 // agt_api.hip -- C ABI (include/agt_hip.h) over the gfx950 kernels: error strings, context lifecycle, the device table and the
-// library's stream pool.  The calls live in agt_api_calls.hip, the tracker in agt_api_tracker.hip, undistortion in
-// agt_api_undistort.hip.
+// library's stream pool.  The calls live in agt_api_calls.hip, the tracker in agt_api_tracker.hip (its launch forms:
+// agt_tracker_frames.hip), undistortion in agt_api_undistort.hip.
 #include "agt_ctx.h"
 #include "agt_side_math.h"
 #include <new>
@@ -298,7 +298,7 @@ int agt_create(const agt_config* cfg, void* hip_stream, agt_ctx** out)
     if (!ok) { hip_fail(nullptr, hipGetLastError()); agt_destroy(c); return AGT_ERR_ALLOC; }
     c->split.reset_history();
     c->pipeline = agt_step_supported(cfg->win) ? 1 : 0;
-    c->reproject = 0; c->min_points = 8; c->gate_px = 2.0;
+    c->opt.reproject = 0; c->opt.min_points = 8; c->opt.gate_px = 2.0;
     // knobs: fixed iteration counts (AGT_LK_MAX_COUNT=n AGT_LK_EPS=0) separate the per-iteration cost of the LK role from its per-frame cost
     c->lk_max_count = AGT_KNOB("AGT_LK_MAX_COUNT", 30); c->lk_eps = AGT_KNOB_F("AGT_LK_EPS", 0.01); c->lk_min_eig = 1e-4;
     c->lk_cap_cu = -1;                               // (the library's choice: agt_lk_occupancy_cu)

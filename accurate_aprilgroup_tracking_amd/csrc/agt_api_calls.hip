@@ -78,10 +78,10 @@ int agt_pyramid_build_pair(agt_ctx* c, const uint8_t* d_prev, const uint8_t* d_n
     hipError_t e = agt_launch_step(c->stream, S, T, c->cfg.win, AGT_STEP_PYR);
     if (e != hipSuccess) return hip_fail(c, e);
     for (int k = 0; k < 2; k++) {
-        c->l0_ptr[k] = src[k]; c->l0_pitch[k] = (long)pitch; c->l0_bstride[k] = (long)batch_stride;
+        RingFrame& f = c->frame[k]; f.ptr = src[k]; f.pitch = (long)pitch; f.bstride = (long)batch_stride;      // (as pyramid_build_on: state_out stays)
         rc = pyramid_levels_on(c, c->stream, k, 3, B);
         if (rc) return rc;
-        c->built_B[k] = B;
+        f.B = B;
     }
     return AGT_OK;
 }
@@ -92,12 +92,12 @@ int agt_pyramid_level(const agt_ctx* c, int slot, int level, const uint8_t** d_p
                       int* w, int* h, size_t* pitch, size_t* batch_stride)
 {
     if (!c || slot < 0 || slot >= c->ring || level < 0 || level > c->eff_max_level) return AGT_ERR_ARG;
-    if (c->built_B[slot] <= 0) return AGT_ERR_STATE;
-    if (d_ptr) *d_ptr = level == 0 ? c->l0_ptr[slot] : c->lmem[slot][level];
+    if (c->frame[slot].B <= 0) return AGT_ERR_STATE;
+    if (d_ptr) *d_ptr = level == 0 ? c->frame[slot].ptr : c->lmem[slot][level];
     if (w) *w = c->lw[level];
     if (h) *h = c->lh[level];
-    if (pitch) *pitch = (size_t)(level == 0 ? c->l0_pitch[slot] : c->lpitch[level]);
-    if (batch_stride) *batch_stride = (size_t)(level == 0 ? c->l0_bstride[slot] : level_bstride(c, level));
+    if (pitch) *pitch = (size_t)(level == 0 ? c->frame[slot].pitch : c->lpitch[level]);
+    if (batch_stride) *batch_stride = (size_t)(level == 0 ? c->frame[slot].bstride : level_bstride(c, level));
     return AGT_OK;
 }
 
@@ -112,7 +112,7 @@ int agt_lk_track(agt_ctx* c, int prev_slot, int next_slot,
 }
 
 // agt_lk_track with the forward-backward check: the forward launch as agt_lk_track issues it, then the same kernels back from next_slot
-// to prev_slot in verdict mode (agt_api_tracker.hip lk_verdict_on), on the same stream
+// to prev_slot in verdict mode (agt_tracker_frames.hip lk_verdict_on), on the same stream
 int agt_lk_track_fb(agt_ctx* c, int prev_slot, int next_slot, const float* d_prev_pts, float* d_next_pts,
                     uint8_t* d_status, float* d_err, float* d_fb_dist, int n, int B,
                     int crit_type, int crit_max_count, double crit_eps, int flags, double min_eig_threshold, double fb_max_px)
@@ -235,7 +235,7 @@ int consensus_on(agt_ctx* c, hipStream_t stream, const void* d_obj, long obj_bst
     memset(&h, 0, sizeof(h));
     h.cam = cam; h.obj = d_obj; h.obj_bstride = obj_bstride; h.img = d_img; h.mask = d_mask; h.dtype = dtype;
     h.n = cpt; h.use_guess = use_guess ? 1 : 0; h.pose = s->hyp_pose; h.info = s->hyp_info; h.gate_px = 2.0;
-    h.hyp_T = T; h.hyp_pose = use_guess ? d_start : nullptr; h.hyp_track = track; h.enhance_ape = c->enhance_ape;
+    h.hyp_T = T; h.hyp_pose = use_guess ? d_start : nullptr; h.hyp_track = track; h.enhance_ape = c->opt.enhance_ape;
     e = agt_launch_pnp(stream, h, B * T);
     if (e != hipSuccess) return hip_fail(c, e);
     AgtProjParams v;
@@ -359,7 +359,7 @@ int agt_project_points_host(agt_ctx* c, const void* h_obj, int dtype, int n, con
     return AGT_OK;
 }
 
-// residency cap of the one-wave LK launches: what it does and the library's choice at lk_lds_min (agt_api_tracker.hip)
+// residency cap of the one-wave LK launches: what it does and the library's choice at lk_lds_min (agt_tracker_frames.hip)
 int agt_lk_lds_request(int workgroups_per_cu) { return lk_lds_min(workgroups_per_cu); }
 
 int agt_lk_occupancy_cu(agt_ctx* c, int workgroups_per_cu)

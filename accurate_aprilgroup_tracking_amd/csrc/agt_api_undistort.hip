@@ -1,5 +1,5 @@
 // agt_api_undistort.hip -- frame pre-processing: detect_pose.py:147-183 undistort_frame, :602 cvtColor.
-// agt_preprocess_bgr, which the live camera loop calls every frame, sits beside that loop in agt_api_tracker.hip.
+// agt_preprocess_bgr, which the live camera loop calls every frame, sits beside that loop in agt_api_live.hip.
 #include "agt_ctx.h"
 #include <math.h>
 #include <float.h>

@@ -1,5 +1,7 @@
 // agt_ctx.h -- the context of the C ABI and the host internals its sources share (agt_api.hip: context lifecycle and the device
-// table; agt_api_calls.hip: the stateless calls; agt_api_tracker.hip: the tracker; agt_api_undistort.hip: undistortion).
+// table; agt_api_calls.hip: the stateless calls; agt_api_tracker.hip: the tracker's entry points; agt_api_live.hip: the live camera
+// loop; agt_api_undistort.hip: undistortion; agt_tracker_frames.hip: what a tracked frame is issued with and its launch forms, whose
+// own declarations are in agt_tracker.h).
 // The entry points take their C linkage from include/agt_hip.h; nothing declared here leaves the library (agt_hip.map).
 #pragma once
 #include "agt_kernels.h"
@@ -16,7 +18,7 @@
 #define AGT_TILT_SLOTS 8          // device table of tilted-sensor matrices: slot 0 the tracker's camera, 1.. the stateless calls'
 #define AGT_SPLIT_SLACK 2        // split mode: groups of extra ring entries (pyramid launches run that far ahead of LK)
 
-// Event state of the split pipeline (agt_api_tracker.hip issue_split).  A role's n-th launch records slot n % AGT_EV_SLOTS of its row, and
+// Event state of the split pipeline (agt_tracker_frames.hip issue_split).  A role's n-th launch records slot n % AGT_EV_SLOTS of its row, and
 // the histories name the slots of its most recent launches: the events later launches of the OTHER roles wait for (-1 = none: nothing
 // of that role is in flight).  Plain data: valid when zero-filled except for the histories, which reset_history() sets.
 struct SplitEvents {
@@ -35,6 +37,47 @@ struct SplitEvents {
     void pushed_pose(int slot) { pose_hist[1] = pose_hist[0]; pose_hist[0] = slot; n[POSE]++; }
 };
 
+// What a ring entry knows about the frame it holds: level 0 is the caller's buffer (B streams of it; 0 = no pyramid built), levels >= 1
+// are the entry's own (agt_ctx::lmem).  state_out: where the frame's record goes -- meaningful only for frames the pipelined form
+// registered (agt_tracker_frames.hip), moved along with the entry, read by that form's pose role alone.
+struct RingFrame { const uint8_t* ptr; long pitch, bstride; int B; double* state_out; };
+// frames of one group launch / of a chained pair share pitch and stream stride of level 0
+inline bool same_geometry(const RingFrame& a, const RingFrame& b) { return a.pitch == b.pitch && a.bstride == b.bstride; }
+
+// The tracker's options (agt_tracker_options, _tag_gate, _fb_check, _visibility, _consensus, _predict; enhance_ape: agt_tracker_reset)
+// and the rules that follow from them -- THE place that says which option forces which launch form, and why:
+//   fb_check   the backward pass is a launch of its own behind the stand-alone LK launch;
+//   consensus  the hypothesis and vote launches sit between the LK and the pose launch;
+//   predict    the seeds are an initial flow, which the chain body of the LK role does not take;
+//     -> needs_lk_launch(): the frame's LK is the stand-alone launch -- not the LK role of the step, nor the chained or deferring
+//        forms of the serial step that build on it (agt_tracker_frames.hip serial_form);
+//   reproject  the refresh of a frame's corners comes out of its pose solve and feeds the next frame's LK, which the pipelined
+//              forms run before that solve;
+//     -> stage_by_stage(): with any of the four on, frames take the serial step whatever the pipeline depth.
+//   visibility acts inside the reproject refresh only and changes no form.
+// The dense forms (agt_track_frame(s)_dense) carry none of fb_check, visibility, consensus, predict: dense_refusal().
+// Plain data, valid when zero-filled (everything off) but for min_points / gate_px, which agt_create sets.
+struct TrackOptions {
+    int reproject, min_points, tag_gate, enhance_ape;
+    double gate_px, fb_max_px;               // fb_max_px: forward-backward threshold of the tracker's LK, px (0 = off)
+    double vis_deg, vis_cos_max; int vis_cpt, vis_facing;      // the reproject refresh revives visible tags only (vis_deg = 0: off)
+    double cons_px; int cons_cpt, cons_min;  // per-frame tag consensus in front of the pose step (cons_px = 0: off)
+    double pred_px;                          // motion-predicted initial flow of the LK step (0 = off; its buffers: agt_ctx::pred_*)
+    bool needs_lk_launch() const { return fb_max_px > 0.0 || cons_px > 0.0 || pred_px > 0.0; }
+    bool stage_by_stage() const { return reproject || needs_lk_launch(); }
+    // the dense stage's launch forms carry no backward pass, its re-seed no visibility rule, they leave no room for the consensus
+    // launches and their LK role takes no initial flow
+    int dense_refusal() const { return (fb_max_px > 0.0 || vis_deg > 0.0 || cons_px > 0.0 || pred_px > 0.0) ? AGT_ERR_UNSUPPORTED : AGT_OK; }
+    // Whole tags: n corners are corners 4t .. 4t + 3 under the tag gate, whole tags under the visibility rule, whole tags and at most
+    // 64 of them under consensus.  The codes differ by option (ABI).  agt_tracker_reset asks for its n; a setter asks for the options
+    // as they would be with the tracker's n -- the options in force always fit it, so only the new value can object.
+    int fits_corners(int n) const
+    {
+        if (tag_gate && n % tag_gate) return AGT_ERR_NPOINTS;
+        return ((vis_deg > 0.0 && n % vis_cpt) || (cons_px > 0.0 && (n % cons_cpt || n / cons_cpt > 64))) ? AGT_ERR_ARG : AGT_OK;
+    }
+};
+
 struct agt_ctx {
     agt_config cfg;
     AgtChip chip;                            // the device the context was created on (CU / XCD counts: launch rules and block orders)
@@ -47,15 +90,12 @@ struct agt_ctx {
     char* hcall_host; char* hcall_dev; unsigned long long hcall_n;      // host-mapped staging of the synchronous host-array calls (agt_solve_pnp_host)
     double* d_tilt; double tilt_host[AGT_TILT_SLOTS][18]; int tilt_valid[AGT_TILT_SLOTS]; int tilt_next;   // tilted-sensor matrices (camera_on)
     uint8_t* lmem[AGT_RING_MAX][AGT_MAX_LEVELS];
-    const uint8_t* l0_ptr[AGT_RING_MAX];
-    long l0_pitch[AGT_RING_MAX], l0_bstride[AGT_RING_MAX];
-    int built_B[AGT_RING_MAX];
+    RingFrame frame[AGT_RING_MAX];           // the frame each entry holds
     // tracker: rings (frame t lives in entry t % ring) so that one fused launch can work on pyramid
     // stage s of frames t-sF.., LK of frames t-LF.. and PnP of frames t-(L+1)F.. at once (F = group)
     int ring;                                // allocated ring entries: >= (L + 2) * group
     float* corners[AGT_RING_MAX];            // [B][n][2]
     uint8_t* status[AGT_RING_MAX];           // [B][n]
-    double* so_ring[AGT_RING_MAX];           // caller's state_out of the frames in flight
     int pipeline;                            // 1 = software-pipelined fused step (agt_step.hip)
     int group;                               // frames per fused launch (1..AGT_MAX_GROUP)
     int ramp;                                // split pipeline: frames per group while the pipeline fills (launch_group: split_ramp)
@@ -86,18 +126,11 @@ struct agt_ctx {
     double* pose;                            // [B][6]
     AgtTrackState* tstate;                   // [B]
     AgtCameraHost cam;
-    int trk_n, trk_B, enhance_ape, trk_ready;
-    int reproject, min_points, tag_gate;
-    double gate_px;
-    double fb_max_px;                        // agt_tracker_fb_check: forward-backward threshold of the tracker's LK, px (0 = off; on: stage-by-stage frames)
-    // agt_tracker_visibility: the reproject refresh revives visible tags only (vis_deg = 0: off)
-    double vis_deg, vis_cos_max; int vis_cpt, vis_facing;
-    // agt_tracker_consensus: per-frame tag consensus in front of the pose step (cons_px = 0: off; on: stage-by-stage frames)
-    double cons_px; int cons_cpt, cons_min;
-    // agt_tracker_predict: motion-predicted initial flow of the tracker's LK step (pred_px = 0: off; on: stage-by-stage frames).  One
-    // allocation made when the option is first switched on: the per-stream pose history (AGT_PRED_* of agt_kernels.h), the frame's flows and
-    // the start points of the backward pass of the forward-backward check
-    double pred_px; double* pred_hist; float* pred_flow; float* pred_back;
+    int trk_n, trk_B, trk_ready;
+    TrackOptions opt;
+    // agt_tracker_predict: one allocation made when the option is first switched on: the per-stream pose history (AGT_PRED_* of
+    // agt_kernels.h), the frame's flows and the start points of the backward pass of the forward-backward check
+    double* pred_hist; float* pred_flow; float* pred_back;
     char* cons_buf; size_t cons_cap;         // scratch of the consensus calls (cons_scratch): hypotheses, and the tracker's inlier bytes / votes
     int* fault_host; int* fault_dev;         // host-mapped word a chained launch sets when a wait gave up (agt_synchronize reports it)
     // agt_track_host_frame: the frame's record and a sequence word in host-mapped memory (same allocation as the fault word: +64 the
@@ -128,9 +161,9 @@ int camera_on(agt_ctx* c, const double* K, const double* dist, int ndist, AgtCam
 int ensure_ring(agt_ctx* c, int want);
 int ms_pool_acquire(int device, hipStream_t out[3]);
 
-// agt_api_tracker.hip
+// agt_tracker_frames.hip
+int join_pipeline(agt_ctx* c);            // enqueues the remaining stages of every frame supplied so far
 int dense_scratch(agt_ctx* c, size_t need, int B);
-int join_pipeline(agt_ctx* c);
 int pyramid_build_on(agt_ctx* c, hipStream_t stream, int slot, const uint8_t* d_frames, size_t pitch, size_t batch_stride, int B);
 void fill_levels(const agt_ctx* c, int slot, AgtLevel* L);          // levels 0 .. eff_max_level of ring entry `slot` (level 0: as registered)
 int pyramid_levels_on(agt_ctx* c, hipStream_t stream, int slot, int l0, int B);      // builds levels l0 .. eff_max_level, each from the level below
@@ -144,6 +177,7 @@ int lk_verdict_on(agt_ctx* c, hipStream_t stream, int prev_slot, int next_slot,
                   int n, int B, int crit_type, int crit_max_count, double crit_eps,
                   int flags, double min_eig_threshold, double fb_max_px, const float* d_back_seed = nullptr);
 int lk_lds_min(int per_cu);
+// agt_api_calls.hip
 // Scratch of one consensus call over B streams of T tags (agt_api_calls.hip): grown when too small, never shrunk
 struct ConsScratch { double* hyp_pose; int32_t* hyp_info; double* win; uint8_t* inl; int32_t* votes; };
 int cons_scratch(agt_ctx* c, int B, int T, int n, ConsScratch* s);
@@ -152,7 +186,7 @@ int cons_scratch(agt_ctx* c, int B, int T, int n, ConsScratch* s);
 int consensus_on(agt_ctx* c, hipStream_t stream, const void* d_obj, long obj_bstride, const void* d_img, int dtype, const uint8_t* d_mask,
                  int n, int B, const AgtCameraHost& cam, const double* d_start, int use_guess, const AgtTrackState* track,
                  int cpt, double inlier_px, int min_inliers, uint8_t* d_inl, int32_t* d_votes, double* d_win, ConsScratch* s);
-// arguments of the visibility rule (agt_tracker_visibility, agt_tag_visibility): max_view_deg finite in [0, 90], facing +1 / -1, cpt >= 4
+// agt_api_tracker.hip: arguments of the visibility rule (agt_tracker_visibility, agt_tag_visibility): max_view_deg finite in [0, 90], facing +1 / -1, cpt >= 4
 bool visibility_args_ok(int corners_per_tag, double max_view_deg, int facing);
 double visibility_cos_max(double max_view_deg);                     // cos(max_view_deg), exactly 0 at 90
 

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(AGT_WAVE * NW) __attribute__((amdgpu_waves_per_eu(O
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     // issue priority 1 for every tracker wave of a context that has DECLARED co-tenancy (agt_lk_occupancy_cu with a count: its launches share
-    // the device with other contexts' pyramid passes, agt_api_tracker.hip lk_track_on sets the internal flag): cold pairs 44.4-44.6 -> 43.3-43.4 us per
+    // the device with other contexts' pyramid passes, agt_tracker_frames.hip lk_launch_on sets the internal flag): cold pairs 44.4-44.6 -> 43.3-43.4 us per
     // step (priority 2: the same).  Not for the split pipeline's own launches: c3 37.3-37.6 -> 37.8-38.1 (profiles/r06_experiments.md 17)
     const bool cotenant = NW == 1 && (P.flags & AGT_LK_FLAG_COTENANT) != 0;
     if (cotenant) __builtin_amdgcn_s_setprio(1);

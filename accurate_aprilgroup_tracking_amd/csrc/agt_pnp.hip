@@ -19,7 +19,7 @@ __global__ __launch_bounds__(AGT_WAVE) void pnp_kernel(const AgtPnpParams P)
 // n > 64: four waves.  A solve that starts from a guess is shared by all of them (agt_pnp_body.h, COOP); one without (first
 // frame of a tracker, after a gate rejection, cv2-shaped calls without useExtrinsicGuess) is wave 0's, four points per lane.
 constexpr int COOP_WAVES = agt_pnp::MAX_PPL;
-// Clip submission of the serial step (agt_api_tracker.hip step_serial): the two-level pyramid pass of the NEXT frame rides in this launch
+// Clip submission of the serial step (agt_tracker_frames.hip step_serial): the two-level pyramid pass of the NEXT frame rides in this launch
 // as extra workgroups (blockIdx.x >= n_solve; tile t of stream s at n_solve + s * n_pyr + t) -- the solve is one workgroup per
 // stream, the rest of the chip idles beside it, and alone the pass was a 6.5 us launch at the head of the next frame's chain.
 template <typename T>

@@ -148,7 +148,7 @@ void agt_pyr2_plan(AgtPyrArgs* A, uintptr_t src_align, uintptr_t dst_align, int 
     constexpr int Q = agt_pyr4::L2_PER_TRIP;
     int oh = (int)((A1.dh + strips - 1) / strips + Q - 1) / Q * Q;
     // oh_cap (round 6): 16 for a launch of its own (agt_pyramid_build, agt_pyramid_build_pair: the pass IS the step's long pole there and
-    // every strip pays 9 halo rows of loads and arithmetic); AGT_SPLIT_PYR_OH = 6 (agt_api_tracker.hip) for the pyramid role of the split pipeline,
+    // every strip pays 9 halo rows of loads and arithmetic); AGT_SPLIT_PYR_OH = 6 (agt_tracker_frames.hip) for the pyramid role of the split pipeline,
     // whose launch of up to 1,024 images runs for hundreds of microseconds BESIDE the per-frame LK launches: 64 streams x 16 frames, us per
     // step over four boxes 16: 36.7-37.6, 10: 36.0-36.2, 8: 35.7-36.3, 6: 35.1-35.9, 4: 35.4-36.3, 2: 40.6 (profiles/r06_experiments.md 17)
     // -- short-lived pyramid waves give their slots back sooner

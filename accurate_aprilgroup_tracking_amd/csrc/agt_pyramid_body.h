@@ -23,7 +23,7 @@
 // hgroup8_of_row / vgroup8_at, and store8 (both tiled bodies); hgroup8b / vgroup8b / vcol_b (both rolling bodies;
 // agt_pyramid4_body.h adds the half-width hgroup4b / vgroup4b).  The tile fetch is written out in both tiled bodies (pyr_down_body says why).
 // Who chooses (agt_pyramid.hip): agt_pyr_plan -- one level: rolling where pyr_roll_ok holds, else tiled; agt_pyr2_plan -- two
-// levels: rolling for launches of >= 16 images where it holds, else tiled; the callers (agt_api_calls.hip, agt_api_tracker.hip) take
+// levels: rolling for launches of >= 16 images where it holds, else tiled; the callers (agt_api_calls.hip, agt_tracker_frames.hip) take
 // the tiled two-level pass only for B <= AGT_PYR2_MAX_B streams (agt_ctx.h) and two one-level passes beyond that; the riding
 // tiles are always the tiled two-level pass; agt_launch_pyr_upload2 is always rolling (or refuses).
 #pragma once

@@ -175,7 +175,7 @@ __device__ __forceinline__ void lk_role(const AgtStepParams& S, const AgtStepTab
 // workgroup (decides which XCD a workgroup sits on).  Everything is read from the kernel-argument segment (scalar loads):
 // a reference to the by-value argument would make the compiler copy the whole structure to scratch.
 // ROLL2: the register-rolling two-level pass may be planned (split pipeline: pyr_group_kernel); the fused step kernel is planned with
-// the tiled two-level pass only (agt_api_tracker.hip launch_group) and does not carry the rolling body -- it sits on the edge of its registers
+// the tiled two-level pass only (agt_tracker_frames.hip launch_group) and does not carry the rolling body -- it sits on the edge of its registers
 template <bool ROLL2>
 __device__ __forceinline__ void pyr_role(KParams KS, KTables KT, int blk, int base, uint8_t* lds)
 {
@@ -511,7 +511,7 @@ bool agt_step_fits(int n, int B)
 // roles: AGT_STEP_ALL = one fused launch; AGT_STEP_PYR / AGT_STEP_LK = that role alone, from the kernel compiled without
 // the FP64 PnP role (each launch sizes its own LDS); AGT_STEP_PNP = the PnP role alone.
 // The LK role tracks every corner with four waves.  Its one-wave forms lost: as a group launch of the split pipeline 54.2 against
-// 42.1 us per step at 64 streams (per-frame launches instead, agt_api_tracker.hip launch_group; round 4, profiles/r04_experiments.md),
+// 42.1 us per step at 64 streams (per-frame launches instead, agt_tracker_frames.hip launch_group; round 4, profiles/r04_experiments.md),
 // and the fused launch never holds more than the 1024 corners up to which agt_lk_wide picks four waves.
 hipError_t agt_launch_step(hipStream_t stream, const AgtStepParams& S, const AgtStepTables& T, int win, int roles)
 {

@@ -879,7 +879,7 @@ def test_poisoned_table_entry_is_fail_stop(torch_cuda, seq640, role, streams):
     rec = np.array(f["rec"])
     assert f["codes"][1] == -8, "agt_synchronize reports AGT_ERR_CHAIN (codes %s)" % f["codes"]
     differs = np.nonzero((rec != clean).any(axis=(1, 2)))[0]
-    # (the fused step runs groups of four frames from the start; the split pipeline fills in groups of two, then four: agt_api_tracker.hip split_ramp)
+    # (the fused step runs groups of four frames from the start; the split pipeline fills in groups of two, then four: agt_tracker_frames.hip split_ramp)
     first_ok = 4 if streams == 1 else 2
     assert len(differs) and differs[0] >= first_ok, "the poisoned entry belongs to the second multi-frame launch: the frames of the first one are clean"
     if role == "PNP" or streams == 1:
