@@ -184,7 +184,12 @@ int agt_lk_track_fb(agt_ctx* ctx, int prev_slot, int next_slot, const float* d_p
  * applied wherever cv2 applies it: projectPoints and its Jacobian, undistortPoints, the undistortion maps, getOptimalNewCameraMatrix.
  * d_pose: [B][6] f64 (rvec, tvec): read when use_guess, always written on success
  * (cv2 overwrites the guess arrays in place too, detect_pose.py:487-490).
- * d_info: [B][4] i32 (AGT_INFO_*), d_err: [B] f64 mean reprojection error; either may be NULL. */
+ * d_info: [B][4] i32 (AGT_INFO_*), d_err: [B] f64 mean reprojection error; either may be NULL.
+ * Inputs the solve cannot use are reported, not repaired.  A used image coordinate that is NaN or infinite, or a NaN in the guess, ends
+ * as AGT_INFO_OK = 1, AGT_INFO_ITERS = 20, AGT_INFO_FLAGS = AGT_PNP_SINGULAR (| AGT_PNP_PLANAR without a guess on planar points) with a
+ * d_err that is not finite and a pose that is not finite (all six numbers; with a NaN guess at least the NaN ones): test d_err or the
+ * flag, not AGT_INFO_OK.  A system whose pivot is exactly 0 (e.g. every object point at the origin) ends after one iteration with the
+ * guess unchanged, AGT_PNP_SINGULAR and the guess's error.  Problems of one batch do not see each other's numbers. */
 int agt_solve_pnp(agt_ctx* ctx, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
                   const uint8_t* d_mask, int n, int B,
                   const double* K, const double* dist, int ndist,

@@ -147,18 +147,69 @@ def test_host_rule_is_the_numpy_statement_and_recovers_the_clean_corners(oracle,
         assert plain.last_error < 0.2
 
 
-@pytest.mark.parametrize("kind", S.BATCHES)
+@pytest.mark.parametrize("kind", S.BATCHES + S.EDGE_BATCHES)
 def test_every_gpu_batch_meets_the_margin_condition(oracle, kind):
+    """(e_flag is exempt from nothing either: with its reference told what the zero tag reports, it meets the condition too)"""
     bt = S.make_batch(kind, oracle)
     for b in range(bt.B):
-        for guess in (None, bt.guess[b]):
-            res = S.oracle_rule(oracle, bt.obj, bt.img[b], bt.K, bt.dist, usable=bt.usable(b), guess=guess)
+        for guess in (False, True):
+            res = bt.reference(oracle, b, guess)
             S.check_margins(res, bt.usable(b))
             assert np.array_equal(res["inliers"], bt.expected[b]), "%s stream %d" % (kind, b)
             if kind == "b2_allbad" and b == 1:
                 assert res["winner"] == -1 and res["n_hyp"] == 12 and max(res["counts"].values()) == 4
             if kind.endswith("masked"):
                 assert res["n_cand"] == 11 and res["count"] == int(bt.expected[b].sum()) and res["count"] % 4 == 3
+
+
+# what the oracle's rule gives for every edge batch: (n_cand, n_hyp without a guess, n_hyp with one, winner per stream, count)
+EDGE_TABLE = {"e_nonfinite": (12, 10, 10, (8,), 34), "e_noncoplanar": (12, 11, 12, (8,), 36), "e_tie": (12, 12, 12, (5,), 8),
+              "e_behind": (10, 10, 10, (1,), 32), "e_t64": (64, 64, 64, (S.E_T64_WINNER,), 176), "e_t64_last": (64, 64, 64, (63,), 176),
+              "e_t1": (1, 1, 1, (0,), 4), "e_cpt8": (6, 6, 6, (4,), 40), "e_cpt80": (3, 3, 3, (1, 0), 160), "e_cpt128": (1, 1, 1, (0,), 255),
+              "e_flag": (12, 11, 11, (8,), 44)}
+
+
+@pytest.mark.parametrize("kind", S.EDGE_BATCHES)
+def test_edge_batches_reach_their_clause(oracle, kind):
+    """The edge batches of the GPU tests, by the oracle alone: candidates, accepted hypotheses, winner and count are the table's, and each
+    scene's outcome hangs on the clause it was built for."""
+    bt = S.make_batch(kind, oracle)
+    n_cand, hyp_plain, hyp_guess, winners, count = EDGE_TABLE[kind]
+    for b in range(bt.B):
+        for guess in (False, True):
+            res = bt.reference(oracle, b, guess)
+            where = "%s stream %d %s" % (kind, b, "guess" if guess else "no guess")
+            assert (res["n_cand"], res["n_hyp"]) == (n_cand, hyp_guess if guess else hyp_plain), where
+            assert (res["winner"], res["count"]) == (winners[b], count) and count == int(bt.expected[b].sum()), where
+            assert np.array_equal(res["inliers"], bt.expected[b]), where
+            if kind == "e_nonfinite":
+                bad = np.flatnonzero(~np.isfinite(bt.img[b]).all(axis=1))
+                assert bad.size == 2 and bt.usable(b)[bad].all() and not res["inliers"][bad].any(), where
+                assert sorted(set(range(12)) - set(res["counts"])) == sorted(bad // 4), where + ": the two tags are no hypotheses"
+            if kind == "e_tie":
+                assert res["counts"] == {t: (8 if t in (5, 9) else 4) for t in range(12)}, where
+                assert res["ssq"][5] == res["ssq"][9] and np.array_equal(res["sets"][5], res["sets"][9]), where + ": an exact tie"
+                assert count == bt.min_inliers, where + ": the count sits on min_inliers"
+                none = S.oracle_rule(oracle, bt.obj, bt.img[b], bt.K, bt.dist, guess=bt.guess[b] if guess else None, min_inliers=9)
+                assert none["winner"] == -1 and not none["inliers"].any(), where
+            if kind == "e_behind":
+                twins = np.flatnonzero(bt.mask[b] == 0) // 4
+                tw = np.concatenate([np.arange(4 * d + 1, 4 * d + 4) for d in twins])
+                d = np.sqrt(res["d2"][res["winner"]][tw])
+                print("%s: the twins' usable corners lie %.2f .. %.2f px from their image points under the winner" % (where, d.min(), d.max()))
+                assert twins.size == 2 and d.max() < S.TAU - 0.05 and not res["inliers"][tw].any(), where
+                # ... and nothing but the depth clause keeps them out
+                wo = bt.reference(oracle, b, guess, depth_clause=False)
+                assert wo["count"] == count + 6 and wo["inliers"][tw].all() and np.array_equal(wo["inliers"][bt.expected[b]], res["inliers"][bt.expected[b]]), where
+            if kind == "e_flag":
+                t = S.E_FLAG_TAG
+                assert t not in res["counts"], where
+                if guess:
+                    # without the flag clause the zero tag's hypothesis, the guess itself, beats every tag's
+                    wo = bt.reference(oracle, b, guess, flag_clause=False)
+                    assert wo["winner"] == t and wo["n_hyp"] == 12 and wo["count"] == count, where
+            if kind.startswith("e_cpt"):
+                assert set(res["counts"].values()) <= {bt.cpt, count}, where
 
 
 def test_option_off_is_the_detector_without_the_keyword(oracle, tmp_path):
