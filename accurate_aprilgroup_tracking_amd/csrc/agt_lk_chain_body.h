@@ -13,7 +13,8 @@
 //     flow, so it is evaluated for every level at once, as straight-line code: the partial sums are transposed through LDS
 //     and wave w finishes level w -- three barriers per frame instead of nine;
 //   * the level loop is unrolled (per-level quantities are plain registers), the iteration makes one vector -> scalar decision,
-//     its sums cross the waves as int32 hi / lo pairs;
+//     its sums cross the waves as int32 hi / lo pairs -- one 64-bit LDS add of lo | hi << 32 per row leader into three rotating
+//     slots; thread 0 clears the slot of the trip after next once its wave has this trip's totals (rule of the slots: iter_sum2);
 //   * the result is stored (device-scope stores when the PnP role of the same launch waits for it) and counted into the
 //     arrival counter one frame later, both under the next frame's image-side work: the stores behind its Scharr barrier, the
 //     arrival two barriers on (stores count in vmcnt: issued at the frame's end, their acknowledgement was waited for by the
@@ -23,7 +24,8 @@
 //     a level are sorted out behind it -- and the sums' scale 2^-20 is folded into the level's 1 / det.
 // Measured on production code with fixed iteration counts: 5.8 us per frame + 0.62 us per iteration (profiles/r02_summary.md);
 // 5.45 us since the two items before the last (profiles/lk_frame_fixed.md); the last one took another 0.5 us off the frame of the
-// c2 stream, about 0.04 us per iteration (profiles/pose_handover.md).
+// c2 stream, about 0.04 us per iteration (profiles/pose_handover.md); the 64-bit add and the one-test loop condition another
+// 0.03 us per iteration (profiles/lk_trip_bookkeeping.md).
 // Only what the tracker uses is covered: flags == 0, no error output (lk_role keeps lk_body otherwise); the frames of a group
 // share their geometry, the image before the group may differ in pitch.  A one-frame group is fine: its image-(k-1) tiles are
 // loaded on demand like the first frame's of any group.
@@ -90,6 +92,20 @@ __device__ __forceinline__ void wave_sum2_i32(int v0, int v1, int& t0, int& t1) 
 // sum lo < 2^20 over the workgroup), and fmaf(hi, 65536, lo) rounds the exact total once -- the same float as
 // (float)(double)(int64 total) in block_sum_exact's caller.  v_permlane32_swap puts both sums in one DPP chain (value 0 in
 // the lower half-wave, value 1 in the upper one).
+//
+// chain_accumulate: the first lane of each 16-lane row adds its row's sum, split lo / hi, into the workgroup's accumulator
+// { lo0, hi0, lo1, hi1 } at acc -- as ONE 64-bit LDS atomic of lo | hi << 32 per row leader (agt_lk_body.h pair_accumulate, which
+// the other four-wave bodies keep, sends two 32-bit ones).  No carry: the lo parts are non-negative and their total over the
+// workgroup stays below 2^20, so the low word never carries into the high one, and the high word wraps mod 2^32 exactly as the
+// separate int32 add of hi did: the same two sums (integer adds: order-free, exact).
+__device__ __forceinline__ void chain_accumulate(int* acc, int lane, int xl, int xh)
+{
+    if ((lane & 15) == 0) {
+        typedef __attribute__((address_space(3))) unsigned long long* L64;
+        const L64 q = (L64)(acc + ((lane >> 5) << 1));                // (8-byte aligned: the slots are 16-byte words)
+        __hip_atomic_fetch_add(q, (unsigned long long)(unsigned)xl | ((unsigned long long)(unsigned)xh << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
 __device__ __forceinline__ void iter_sum2(const int (&v)[2], float& f0, float& f1, int* slots, int& phase, int wave, int lane)
 {
     // |v| < 2^26 per thread: the pair sum across the half-waves (2^27) and three DPP steps (x 8: < 2^30) still fit int32, so the
@@ -99,19 +115,39 @@ __device__ __forceinline__ void iter_sum2(const int (&v)[2], float& f0, float& f
     const int x = row_steps<0, 3>(pair_fold(v[0], v[1]));
     int xl = x & 0xffff, xh = x >> 16;
     xl = row_steps<3, 4>(xl); xh = row_steps<3, 4>(xh);
-    // The row sums go straight into the workgroup's accumulator (pair_accumulate), three rotating slots -- the slot of iteration i + 2
-    // is cleared by thread 0 right after the barrier of iteration i, when its last readers (iteration i - 1) are past it.  No
-    // read-lanes, no scalar adds, and after the barrier every wave reads ONE 16-byte word instead of four.
+    // The row sums go straight into the workgroup's accumulator (chain_accumulate), three rotating slots.  No read-lanes, no
+    // scalar adds, and after the barrier every wave reads ONE 16-byte word instead of four.
     // (round 2: read-lanes + ds_write_b128 per wave + four ds_read_b128 and twelve adds after the barrier; finishing the sums
     // with row_bcast DPP steps and a store from lanes 31 / 63 had measured 11 % slower than that)
+    // RULE OF THE SLOTS.  Count the trips of a workgroup 0, 1, 2, .. over the whole call (the rotation never restarts at a level or
+    // a frame): trip i uses slot i mod 3 and holds exactly one barrier, barrier i, below.  Thread 0 clears the slot of trip i + 2
+    // behind barrier i, AFTER its wave has the totals of trip i: the store is not part of the wait for the totals.
+    //   * nobody still reads it: slot (i + 2) mod 3 = (i - 1) mod 3 was read behind barrier i - 1, and a wave waits for that read
+    //     before it uses the totals, hence before it arrives at barrier i; thread 0 is past barrier i;
+    //   * nobody adds into it yet: the adds of trip i + 2 are issued behind barrier i + 1, which needs thread 0's wave, and
+    //     lds_barrier() waits for the wave's own LDS operations -- the clear among them -- before the wave arrives;
+    //   * it is zero when trip i + 2 adds, and so are the slots of trips 0 and 1 (all three are zeroed at the call's entry).
+    // The argument uses only the ORDER of the trips and the barrier inside each, so what lies between two trips cannot break it:
+    // codes 1 / 2 and max_count end a level behind a complete trip, and the next trip is the next usable level's or the next frame's
+    // first, with the frame's barriers in between (more ordering, never less); code 3 goes round the outer loop, whose slow path
+    // adds block_sync()s every wave takes; a lost corner's `continue`, io.bad's return and a level that is not usable run no trip at
+    // all -- a slot cleared for a trip that comes much later, or never, stays clear: nothing but a trip adds into a slot.  Every
+    // branch that decides whether a trip runs is uniform over the workgroup, so the four waves count the same trips.  Two slots
+    // would race: the slot cleared behind barrier i would be the one the faster waves already add trip i + 1's sums into.
+    // (Clearing the NEXT trip's slot at the head of the trip instead -- before, beside or behind the tap reads, by thread 0 or by
+    // the row leaders -- measured 0.3 to 0.9 us per frame SLOWER than this, and `phase` as a scalar no faster:
+    // profiles/lk_trip_bookkeeping.md.)
     int* s = slots + phase * 4;
-    pair_accumulate(s, lane, xl, xh);
+    chain_accumulate(s, lane, xl, xh);
     lds_barrier();
     const int4 t = *reinterpret_cast<const int4*>(s);
     const int nz = phase == 0 ? 2 : phase - 1;                     // (phase + 2) % 3
-    if (threadIdx.x == 0) *reinterpret_cast<int4*>(slots + nz * 4) = make_int4(0, 0, 0, 0);
     f0 = fmaf((float)t.y, 65536.f, (float)t.x);
     f1 = fmaf((float)t.w, 65536.f, (float)t.z);
+    // (the totals are in registers here -- the empty statement pins that: left to itself the compiler issues the store between the
+    // totals' read and its wait, and LDS operations of a wave complete in order)
+    asm volatile("" : "+v"(f0), "+v"(f1) :: "memory");
+    if (threadIdx.x == 0) *reinterpret_cast<int4*>(slots + nz * 4) = make_int4(0, 0, 0, 0);
     phase = phase == 2 ? 0 : phase + 1;
 }
 
@@ -587,7 +623,9 @@ __device__ __forceinline__ void lk_frames_w4(PP P, int pt, int b, uint8_t* lds, 
                     code = lk_iter_code(dx, dy, pdx, pdy, j, nextx, nexty, bx0, bx1, by0, by1, eps2_lo, eps2_hi, [&] { return eps2; });
                     pdx = dx; pdy = dy;         // (the next trip's oscillation test; code 2 takes half of it back)
                     j++;
-                } while (code == 0 && j < max_count);
+                    // (one integer test: written `code == 0 && j < max_count` the back edge was eleven scalar instructions -- two
+                    // conditions made into masks, a third for the code behind the loop -- and measured 0.4 us per frame slower)
+                } while ((code | (int)(j >= max_count)) == 0);
                 if (code != 3) break;
                 slow = 1;
             }
