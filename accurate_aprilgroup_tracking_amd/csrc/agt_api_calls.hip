@@ -126,6 +126,18 @@ int agt_lk_track_fb(agt_ctx* c, int prev_slot, int next_slot, const float* d_pre
                          crit_type, crit_max_count, crit_eps, flags, min_eig_threshold, fb_max_px);
 }
 
+// the plain solve (no tracker state) on B streams of n points; the caller fills in the camera
+static AgtPnpParams plain_solve(const void* obj, long obj_bstride, const void* img, const uint8_t* mask, int dtype, int n,
+                                int use_guess, double* pose, int32_t* info, double* err)
+{
+    AgtPnpParams p;
+    memset(&p, 0, sizeof(p));
+    p.obj = obj; p.obj_bstride = obj_bstride; p.img = img; p.mask = mask; p.dtype = dtype;
+    p.n = n; p.use_guess = use_guess ? 1 : 0; p.pose = pose; p.info = info; p.err = err;
+    p.gate_px = 2.0;
+    return p;
+}
+
 int agt_solve_pnp(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, const void* d_img, int dtype,
                   const uint8_t* d_mask, int n, int B,
                   const double* K, const double* dist, int ndist,
@@ -135,13 +147,9 @@ int agt_solve_pnp(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, const 
     if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
     if (n < 3 || n > 256) return AGT_ERR_NPOINTS;
     if (!use_guess && n < 4) return AGT_ERR_NPOINTS;
-    AgtPnpParams p;
-    memset(&p, 0, sizeof(p));
+    AgtPnpParams p = plain_solve(d_obj, (long)obj_batch_stride, d_img, d_mask, dtype, n, use_guess, d_pose, d_info, d_err);
     int rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
-    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.img = d_img; p.mask = d_mask; p.dtype = dtype;
-    p.n = n; p.use_guess = use_guess ? 1 : 0; p.pose = d_pose; p.info = d_info; p.err = d_err;
-    p.gate_px = 2.0;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
@@ -152,17 +160,15 @@ int agt_project_points(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, i
 {
     if (!c || !d_obj || !d_pose || !d_img_out || n <= 0 || B <= 0) return AGT_ERR_ARG;
     if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
-    AgtProjParams p;
-    memset(&p, 0, sizeof(p));
+    AgtPointsParams p = { d_obj, (long)obj_batch_stride, dtype, n, d_pose };
     int rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
-    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n; p.pose = d_pose;
     p.img_out = d_img_out; p.jac = d_jac;
-    hipError_t e = agt_launch_project(c->stream, p, B);
+    hipError_t e = agt_launch_points(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
-// the visibility rule of agt_tracker_visibility for B poses: project_kernel in its visibility mode (agt_pnp.hip), one thread per tag
+// the visibility rule of agt_tracker_visibility for B poses: visible_kernel (agt_project.hip), one thread per tag
 int agt_tag_visibility(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
                        const double* d_pose, int corners_per_tag, double max_view_deg, int facing,
                        uint8_t* d_visible, double* d_cos)
@@ -170,15 +176,13 @@ int agt_tag_visibility(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, i
     if (!c || !d_obj || !d_pose || !d_visible || n <= 0 || B <= 0) return AGT_ERR_ARG;
     if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
     if (!visibility_args_ok(corners_per_tag, max_view_deg, facing) || !(max_view_deg > 0.0) || n % corners_per_tag) return AGT_ERR_ARG;
-    AgtProjParams p;
-    memset(&p, 0, sizeof(p));
-    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n; p.pose = d_pose;
+    AgtVisibleParams p = { d_obj, (long)obj_batch_stride, dtype, n, d_pose };
     p.vis_out = d_visible; p.vis_cos = d_cos; p.vis_cos_max = visibility_cos_max(max_view_deg); p.vis_cpt = corners_per_tag; p.vis_facing = facing;
-    hipError_t e = agt_launch_project(c->stream, p, B);
+    hipError_t e = agt_launch_visible(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
-// the seed rule of agt_tracker_predict for B pairs of poses: project_kernel in its flow mode (agt_pnp.hip), one workgroup per stream
+// the seed rule of agt_tracker_predict for B pairs of poses: flow_kernel (agt_project.hip), one workgroup per stream
 int agt_predict_flow(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int dtype, int n, int B,
                      const double* d_pose_older, const double* d_pose_newer, const double* K, const double* dist, int ndist,
                      const float* d_prev_pts, const uint8_t* d_mask, double max_flow_px,
@@ -188,20 +192,18 @@ int agt_predict_flow(agt_ctx* c, const void* d_obj, size_t obj_batch_stride, int
     if (dtype != AGT_F32 && dtype != AGT_F64) return AGT_ERR_ARG;
     if (!(max_flow_px > 0.0) || !(max_flow_px <= 1.7976931348623157e308)) return AGT_ERR_ARG;       // (NaN fails both)
     if (n > 256) return AGT_ERR_NPOINTS;
-    AgtProjParams p;
-    memset(&p, 0, sizeof(p));
+    AgtFlowParams p = { d_obj, (long)obj_batch_stride, dtype, n };
     int rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
-    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.dtype = dtype; p.n = n;
     p.flow_older = d_pose_older; p.flow_newer = d_pose_newer; p.flow_pstride = 6; p.flow_prev = d_prev_pts; p.flow_mask = d_mask;
     p.flow_seed = d_seed_pts; p.flow_out = d_flow; p.flow_max = d_flow_max; p.flow_pred = d_pose_pred; p.flow_cap = (float)max_flow_px;
-    hipError_t e = agt_launch_project(c->stream, p, B);
+    hipError_t e = agt_launch_flow(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
 // ---- tag consensus (the rule: include/agt_hip.h agt_solve_pnp_consensus).  Three launches on one stream, nothing in between:
 //   1. the solver kernels over B * T problems of cpt points (hypothesis launch, agt_kernels.h AgtPnpParams::hyp_T)
-//   2. project_kernel in vote mode, one workgroup per stream: inlier bytes, votes, the winner's pose
+//   2. vote_kernel (agt_project.hip), one workgroup per stream: inlier bytes, votes, the winner's pose
 //   3. (stateless call) the ordinary masked solve from the winner's pose; (tracker) the unchanged pose step on the smaller mask
 int cons_scratch(agt_ctx* c, int B, int T, int n, ConsScratch* s)
 {
@@ -238,13 +240,11 @@ int consensus_on(agt_ctx* c, hipStream_t stream, const void* d_obj, long obj_bst
     h.hyp_T = T; h.hyp_pose = use_guess ? d_start : nullptr; h.hyp_track = track; h.enhance_ape = c->opt.enhance_ape;
     e = agt_launch_pnp(stream, h, B * T);
     if (e != hipSuccess) return hip_fail(c, e);
-    AgtProjParams v;
-    memset(&v, 0, sizeof(v));
-    v.cam = cam; v.obj = d_obj; v.obj_bstride = obj_bstride; v.dtype = dtype; v.n = n;
+    AgtVoteParams v = { d_obj, obj_bstride, dtype, n, cam };
     v.vote_img = d_img; v.vote_mask = d_mask; v.vote_pose = s->hyp_pose; v.vote_info = s->hyp_info;
     v.vote_inl = d_inl ? d_inl : s->inl; v.vote_votes = d_votes ? d_votes : s->votes; v.vote_win = d_win ? d_win : s->win;
     v.vote_tau2 = inlier_px * inlier_px; v.vote_cpt = cpt; v.vote_min = min_inliers;
-    e = agt_launch_project(stream, v, B);
+    e = agt_launch_vote(stream, v, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
@@ -258,8 +258,8 @@ int agt_solve_pnp_consensus(agt_ctx* c, const void* d_obj, size_t obj_batch_stri
     if (!(inlier_px > 0.0) || !(inlier_px <= 1.0e150)) return AGT_ERR_ARG;             // (NaN fails both; the square stays finite)
     if (corners_per_tag < 4 || n % corners_per_tag || min_inliers < corners_per_tag) return AGT_ERR_ARG;
     if (n > 256 || n / corners_per_tag > 64) return AGT_ERR_NPOINTS;
-    AgtPnpParams p;
-    memset(&p, 0, sizeof(p));
+    // the refit: agt_solve_pnp(mask = inliers, use_guess = 1).  A stream without consensus has an all-zero mask: pose untouched, info TOO_FEW
+    AgtPnpParams p = plain_solve(d_obj, (long)obj_batch_stride, d_img, d_inliers, dtype, n, 1, d_pose, d_info, d_err);
     int rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
     ConsScratch s;
@@ -267,10 +267,6 @@ int agt_solve_pnp_consensus(agt_ctx* c, const void* d_obj, size_t obj_batch_stri
     rc = consensus_on(c, c->stream, d_obj, (long)obj_batch_stride, d_img, dtype, d_mask, n, B, p.cam, d_pose, use_guess, nullptr,
                       corners_per_tag, inlier_px, min_inliers, d_inliers, d_votes, d_pose, &s);
     if (rc) return rc;
-    // the refit: agt_solve_pnp(mask = inliers, use_guess = 1).  A stream without consensus has an all-zero mask: pose untouched, info TOO_FEW
-    p.obj = d_obj; p.obj_bstride = (long)obj_batch_stride; p.img = d_img; p.mask = d_inliers; p.dtype = dtype;
-    p.n = n; p.use_guess = 1; p.pose = d_pose; p.info = d_info; p.err = d_err;
-    p.gate_px = 2.0;
     hipError_t e = agt_launch_pnp(c->stream, p, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
@@ -294,6 +290,17 @@ int hcall_ready(agt_ctx* c)
     c->hcall_n = 0;
     return AGT_OK;
 }
+
+// one host call (after hcall_ready): the call's number goes into the parameters, whose kernel stores it behind its outputs; launch, poll
+template <class P, class Launch>
+int hcall_run(agt_ctx* c, P& p, Launch launch)
+{
+    const unsigned long long want = ++c->hcall_n;
+    p.host_seq = (unsigned long long*)(c->hcall_dev + HC_SEQ); p.host_seq_base = want;
+    hipError_t e = launch(c->stream, p, 1);
+    if (e != hipSuccess) return hip_fail(c, e);
+    return poll_seq(c, (const volatile unsigned long long*)(c->hcall_host + HC_SEQ), want);
+}
 }  // namespace
 
 int agt_solve_pnp_host(agt_ctx* c, const void* h_obj, const void* h_img, int dtype, int n,
@@ -306,8 +313,8 @@ int agt_solve_pnp_host(agt_ctx* c, const void* h_obj, const void* h_img, int dty
     if (!use_guess && n < 4) return AGT_ERR_NPOINTS;
     int rc = hcall_ready(c);
     if (rc) return rc;
-    AgtPnpParams p;
-    memset(&p, 0, sizeof(p));
+    AgtPnpParams p = plain_solve(c->hcall_dev + HC_OBJ, 0, c->hcall_dev + HC_IMG, nullptr, dtype, n, use_guess, (double*)(c->hcall_dev + HC_POSE),
+                                 (int32_t*)(c->hcall_dev + HC_INFO), (double*)(c->hcall_dev + HC_ERR));
     rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
     const size_t es = dtype == AGT_F32 ? 4 : 8;
@@ -315,15 +322,7 @@ int agt_solve_pnp_host(agt_ctx* c, const void* h_obj, const void* h_img, int dty
     memcpy(c->hcall_host + HC_IMG, h_img, (size_t)n * 2 * es);
     double* pose = (double*)(c->hcall_host + HC_POSE);
     if (use_guess) memcpy(pose, h_pose, 6 * sizeof(double)); else memset(pose, 0, 6 * sizeof(double));
-    p.obj = c->hcall_dev + HC_OBJ; p.obj_bstride = 0; p.img = c->hcall_dev + HC_IMG; p.mask = nullptr; p.dtype = dtype;
-    p.n = n; p.use_guess = use_guess ? 1 : 0; p.pose = (double*)(c->hcall_dev + HC_POSE);
-    p.info = (int32_t*)(c->hcall_dev + HC_INFO); p.err = (double*)(c->hcall_dev + HC_ERR);
-    p.gate_px = 2.0;
-    const unsigned long long want = ++c->hcall_n;
-    p.host_seq = (unsigned long long*)(c->hcall_dev + HC_SEQ); p.host_seq_base = want;
-    hipError_t e = agt_launch_pnp(c->stream, p, 1);
-    if (e != hipSuccess) return hip_fail(c, e);
-    rc = poll_seq(c, (const volatile unsigned long long*)(c->hcall_host + HC_SEQ), want);
+    rc = hcall_run(c, p, [](hipStream_t s, const AgtPnpParams& q, int B) { return agt_launch_pnp(s, q, B); });
     if (rc) return rc;
     memcpy(h_pose, pose, 6 * sizeof(double));
     if (h_info) memcpy(h_info, c->hcall_host + HC_INFO, 4 * sizeof(int32_t));
@@ -339,20 +338,14 @@ int agt_project_points_host(agt_ctx* c, const void* h_obj, int dtype, int n, con
     if (n <= 0 || n > 256) return AGT_ERR_NPOINTS;          // (one workgroup: the reference projects its 48 .. 240 model corners)
     int rc = hcall_ready(c);
     if (rc) return rc;
-    AgtProjParams p;
-    memset(&p, 0, sizeof(p));
+    AgtPointsParams p = { c->hcall_dev + HC_OBJ, 0, dtype, n, (const double*)(c->hcall_dev + HC_POSE) };
     rc = camera_on(c, K, dist, ndist, &p.cam);
     if (rc) return rc;
     const size_t es = dtype == AGT_F32 ? 4 : 8;
     memcpy(c->hcall_host + HC_OBJ, h_obj, (size_t)n * 3 * es);
     memcpy(c->hcall_host + HC_POSE, h_pose, 6 * sizeof(double));
-    p.obj = c->hcall_dev + HC_OBJ; p.obj_bstride = 0; p.dtype = dtype; p.n = n; p.pose = (const double*)(c->hcall_dev + HC_POSE);
     p.img_out = c->hcall_dev + HC_IMG; p.jac = h_jac ? (double*)(c->hcall_dev + HC_JAC) : nullptr;
-    const unsigned long long want = ++c->hcall_n;
-    p.host_seq = (unsigned long long*)(c->hcall_dev + HC_SEQ); p.host_seq_base = want;
-    hipError_t e = agt_launch_project(c->stream, p, 1);
-    if (e != hipSuccess) return hip_fail(c, e);
-    rc = poll_seq(c, (const volatile unsigned long long*)(c->hcall_host + HC_SEQ), want);
+    rc = hcall_run(c, p, agt_launch_points);
     if (rc) return rc;
     memcpy(h_img_out, c->hcall_host + HC_IMG, (size_t)n * 2 * es);
     if (h_jac) memcpy(h_jac, c->hcall_host + HC_JAC, (size_t)n * 12 * sizeof(double));

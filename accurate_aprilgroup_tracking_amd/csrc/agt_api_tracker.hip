@@ -122,8 +122,8 @@ int agt_tracker_consensus(agt_ctx* c, int corners_per_tag, double inlier_px, int
     return set_options(c, [=](TrackOptions& o) { o.cons_px = inlier_px; o.cons_cpt = corners_per_tag; o.cons_min = min_inliers; });
 }
 
-// ---- agt_tracker_predict (semantics: include/agt_hip.h; device side: agt_pnp.hip flow_stream, the history block: agt_kernels.h AGT_PRED_*).
-// Every record-producing pose launch is preceded by ONE launch of project_kernel in flow mode, which predicts from the stream's two
+// ---- agt_tracker_predict (semantics: include/agt_hip.h; device side: agt_project.hip flow_stream, the history block: agt_kernels.h AGT_PRED_*).
+// Every record-producing pose launch is preceded by ONE launch of flow_kernel (agt_project.hip), which predicts from the stream's two
 // newest records, advances the history and leaves the frame's flow word for the pose launch.  (The launch form it forces: agt_ctx.h TrackOptions.)
 int agt_tracker_predict(agt_ctx* c, double max_flow_px)
 {

@@ -162,7 +162,7 @@ struct AgtPnpParams {
     double* pred_hist;                       // [B][AGT_PRED_STRIDE]
 };
 // Pose history of agt_tracker_predict, per stream: the record the pose step wrote last (pose, accepted), the flow word of the frame (the seed
-// launch's flow_max, handed to the pose launch), and the record before that one.  The seed launch of project_kernel (flow mode) predicts
+// launch's flow_max, handed to the pose launch), and the record before that one.  The seed launch (flow_kernel, agt_project.hip) predicts
 // from the two entries while both are accepted, then moves `last` to `before` and clears `last`.
 #define AGT_PRED_STRIDE 16
 #define AGT_PRED_LAST   0     // 0..5 pose, 6 accepted (1.0 / 0.0)
@@ -233,7 +233,10 @@ struct AgtStepTables {
     AgtPnpTables pnp;
 };
 
-struct AgtProjParams {
+// ---- the projection family (agt_project.hip): one argument block and one launcher per job.  obj / obj_bstride / dtype / n are the object
+// points as in AgtPnpParams (n per stream, obj_bstride elements between streams, 0 = shared).
+// cv::projectPoints: thread i of stream b's blocks projects point i under pose[b]
+struct AgtPointsParams {
     const void* obj; long obj_bstride; int dtype; int n;
     const double* pose;       // [B][6]
     AgtCameraHost cam;
@@ -242,16 +245,23 @@ struct AgtProjParams {
     // agt_project_points_host (one block, B = 1): host-mapped sequence word stored behind the outputs (see AgtPnpParams::host_seq); null: off
     unsigned long long* host_seq;
     unsigned long long host_seq_base;
-    // visibility mode (agt_tag_visibility; vis_out != null): no projection -- thread i of stream b's blocks judges tag i (object points
-    // vis_cpt * i ..) under pose[b] with agt_tag_visible; img_out, jac and the camera are not read
+};
+// agt_tag_visibility: thread i of stream b's blocks judges tag i (object points vis_cpt * i ..) under pose[b] with agt_tag_visible
+struct AgtVisibleParams {
+    const void* obj; long obj_bstride; int dtype; int n;
+    const double* pose;       // [B][6]
     uint8_t* vis_out;         // [B][n / vis_cpt]
     double* vis_cos;          // [B][n / vis_cpt] or null
     double vis_cos_max;
     int vis_cpt, vis_facing;
-    // vote mode (agt_solve_pnp_consensus; vote_inl != null): ONE workgroup per stream, thread i owns corner i (n <= 256).  Every usable
-    // corner is projected under every accepted hypothesis (vote_pose / vote_info: the hypothesis launch's results, [B][T][6] / [B][T][4],
-    // T = n / vote_cpt); the workgroup elects the hypothesis with the most inliers and writes the stream's inlier bytes, its votes row and,
-    // when there is a consensus, the winner's pose to vote_win[b].  img_out, jac and pose are not read.
+};
+// agt_solve_pnp_consensus: ONE workgroup per stream, thread i owns corner i (n <= 256, n / vote_cpt <= 64).  Every usable corner is
+// projected under every accepted hypothesis (vote_pose / vote_info: the hypothesis launch's results, [B][T][6] / [B][T][4],
+// T = n / vote_cpt); the workgroup elects the hypothesis with the most inliers and writes the stream's inlier bytes, its votes row and,
+// when there is a consensus, the winner's pose to vote_win[b].
+struct AgtVoteParams {
+    const void* obj; long obj_bstride; int dtype; int n;
+    AgtCameraHost cam;
     const void* vote_img;     // [B][n][2], dtype as obj
     const uint8_t* vote_mask; // [B][n] or null
     const double* vote_pose;
@@ -261,13 +271,16 @@ struct AgtProjParams {
     double* vote_win;         // [B][6]
     double vote_tau2;         // inlier_px^2
     int vote_cpt, vote_min;
-    // flow mode (agt_predict_flow, agt_tracker_predict; flow_seed or flow_hist != null): ONE workgroup per stream, thread i owns corner i
-    // (n <= 256).  The constant-velocity extrapolation of the poses flow_older[b] -> flow_newer[b] (stride flow_pstride doubles) is computed
-    // once per workgroup, every usable corner is projected under the newer and the predicted pose, the workgroup decides whether the
-    // prediction is trusted and writes seeds, flows, flow_max and the predicted pose (the rule: include/agt_hip.h).  flow_hist != null: the
-    // tracker's form -- the poses are the two entries of the stream's history block (AGT_PRED_*), a stream whose entries are not both
-    // accepted has no prediction (seeds = flow_prev, flow_max 0), and the block is advanced for the frame's pose step.  n = 0 with
-    // flow_seed null: only that.  img_out, jac and pose are not read.
+};
+// agt_predict_flow, agt_tracker_predict: ONE workgroup per stream, thread i owns corner i (n <= 256).  The constant-velocity
+// extrapolation of the poses flow_older[b] -> flow_newer[b] (stride flow_pstride doubles) is computed once per workgroup, every usable
+// corner is projected under the newer and the predicted pose, the workgroup decides whether the prediction is trusted and writes seeds,
+// flows, flow_max and the predicted pose (the rule: include/agt_hip.h).  flow_hist != null: the tracker's form -- the poses are the two
+// entries of the stream's history block (AGT_PRED_*; flow_older / flow_newer are not read), a stream whose entries are not both accepted
+// has no prediction (seeds = flow_prev, flow_max 0), and the block is advanced for the frame's pose step.  n = 0 with flow_hist: only that.
+struct AgtFlowParams {
+    const void* obj; long obj_bstride; int dtype; int n;
+    AgtCameraHost cam;
     const double* flow_older; // [B][6]
     const double* flow_newer;
     long flow_pstride;
@@ -278,11 +291,15 @@ struct AgtProjParams {
     float* flow_max;          // [B] or null
     double* flow_pred;        // [B][6] or null
     double* flow_hist;        // [B][AGT_PRED_STRIDE] or null
-    // back-seed mode (flow_back != null; the tracker's forward-backward check under agt_tracker_predict): thread i of stream b's blocks
-    // writes flow_back[b][i] = flow_prev[b][i] - flow_out[b][i] (float32), where the backward LK pass starts; nothing else is read
-    float* flow_back;         // [B][n][2]
     float flow_cap;           // (float)max_flow_px
-    int flow_pad_;
+};
+// the tracker's forward-backward check under agt_tracker_predict: thread i of stream b's blocks writes
+// flow_back[b][i] = flow_prev[b][i] - flow_out[b][i] (float32), where the backward LK pass starts
+struct AgtFlowBackParams {
+    int n;
+    const float* flow_prev;   // [B][n][2]
+    const float* flow_out;    // [B][n][2]
+    float* flow_back;         // [B][n][2]
 };
 
 // The dense stage's parameter block (agt_dense.hip: specification, mapping; agt_dense_body.h: the update).  The caller fills frame, model,
@@ -346,7 +363,12 @@ hipError_t agt_launch_lk(hipStream_t stream, const AgtLkParams& p, int win, int 
 // launch; only where agt_pnp_can_ride(n) (the four-wave kernel of n > 64)
 hipError_t agt_launch_pnp(hipStream_t stream, const AgtPnpParams& p, int B, const AgtPyrArgs* ride = nullptr);
 bool agt_pnp_can_ride(int n);
-hipError_t agt_launch_project(hipStream_t stream, const AgtProjParams& p, int B);
+// each refuses what its kernel cannot do (vote: n > 256, vote_cpt <= 0, more than 64 tags; flow: n > 256, n > 0 without seeds)
+hipError_t agt_launch_points(hipStream_t stream, const AgtPointsParams& p, int B);
+hipError_t agt_launch_visible(hipStream_t stream, const AgtVisibleParams& p, int B);
+hipError_t agt_launch_vote(hipStream_t stream, const AgtVoteParams& p, int B);
+hipError_t agt_launch_flow(hipStream_t stream, const AgtFlowParams& p, int B);
+hipError_t agt_launch_flow_back(hipStream_t stream, const AgtFlowBackParams& p, int B);
 hipError_t agt_launch_undistort_map(hipStream_t stream, const double* K, const AgtCameraHost& cam, const AgtTiltHost& tilt, const double* ir,
                                     int w, int h, short2* map1, unsigned short* map2);
 hipError_t agt_launch_preprocess(hipStream_t stream, const AgtRemapArgs& A, int gray);

@@ -183,14 +183,13 @@ static int track_lk_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, 
 // flows into the context's scratch.  prev_slot < 0: a frame without an LK step -- the history moves on, the flow word is 0.
 static int track_seed_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, int B)
 {
-    AgtProjParams q;
-    memset(&q, 0, sizeof(q));
-    q.flow_hist = c->pred_hist; q.flow_cap = (float)c->opt.pred_px;
+    AgtFlowParams q = {};
+    q.dtype = AGT_F32; q.flow_hist = c->pred_hist; q.flow_cap = (float)c->opt.pred_px;
     if (prev_slot >= 0) {
-        q.obj = c->obj; q.obj_bstride = 0; q.dtype = AGT_F32; q.n = c->trk_n; q.cam = c->cam;
+        q.obj = c->obj; q.n = c->trk_n; q.cam = c->cam;
         q.flow_prev = c->corners[prev_slot]; q.flow_mask = c->status[prev_slot]; q.flow_seed = c->corners[slot]; q.flow_out = c->pred_flow;
     }
-    hipError_t e = agt_launch_project(stream, q, B);
+    hipError_t e = agt_launch_flow(stream, q, B);
     return e == hipSuccess ? AGT_OK : hip_fail(c, e);
 }
 
@@ -738,10 +737,8 @@ static int track_fb_on(agt_ctx* c, hipStream_t stream, int prev_slot, int slot, 
 {
     const float* back = nullptr;
     if (c->opt.pred_px > 0.0) {
-        AgtProjParams q;
-        memset(&q, 0, sizeof(q));
-        q.n = c->trk_n; q.flow_prev = c->corners[slot]; q.flow_out = c->pred_flow; q.flow_back = c->pred_back;
-        hipError_t e = agt_launch_project(stream, q, B);
+        const AgtFlowBackParams q = { c->trk_n, c->corners[slot], c->pred_flow, c->pred_back };
+        hipError_t e = agt_launch_flow_back(stream, q, B);
         if (e != hipSuccess) return hip_fail(c, e);
         back = c->pred_back;
     }

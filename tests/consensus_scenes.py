@@ -6,7 +6,7 @@ TAGS (all four corners by one vector of 6 - 25 px) -- what a tag that slid onto 
 so that the same statement serves the CPU oracle and the device's own stateless calls.  `check_margins()` is the condition every scene
 of these tests has to meet under the oracle alone: no residual near the threshold, no near-tie between the two best hypotheses.
 
-The edge batches (EDGE_BATCHES, make_edge_batch) each reach one clause of the rule or one bound of the vote kernel (csrc/agt_pnp.hip
+The edge batches (EDGE_BATCHES, make_edge_batch) each reach one clause of the rule or one bound of the vote kernel (csrc/agt_project.hip
 vote_stream) that the scenes above stay clear of:
   e_nonfinite    step 2: two candidate tags with a used image coordinate NaN / image point (inf, inf) are no hypotheses; their other
                  corners still vote
