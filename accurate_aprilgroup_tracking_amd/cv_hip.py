@@ -770,6 +770,28 @@ def refineQuads(gray, quads, rangePx=2.0, iters=2, minStrength=40.0):
     return out.quads.cpu().numpy()[0], quad_refine.records_numpy(out.records)[0]
 
 
+def detectQuads(gray, **options):
+    """The first stage of a tag detector (no cv2 counterpart; quad_detect.QuadDetector, include/agt_quadfind.h): gray (H, W) u8 ->
+    (quads (N, 4, 2) f32, records (N,) structured: label, area, x0, y0, x1, y1, s2), the candidate quads of the frame in ascending
+    label order, corners on the outer edge of the dark region, clockwise on the screen, within a few pixels: refineQuads gives the
+    accuracy, decodeTags refuses what is no tag.  options: min_contrast, min_area, max_area, min_fill_pct as QuadDetector.detect
+    takes them, max_components (4096) and max_quads (512)."""
+    from . import quad_detect
+    _require_gpu()
+    img = np.ascontiguousarray(np.asarray(gray))
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise error("detectQuads: gray must be a 2-D uint8 image")
+    sizes = {k: options.pop(k) for k in ("max_components", "max_quads") if k in options}
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        det = quad_detect.QuadDetector(img.shape[1], img.shape[0], 1, **sizes)
+        out = det.detect(torch.from_numpy(img).to(dev)[None], **options)
+    except (quad_detect.Q.QuadFindError, TypeError) as e:
+        raise error(str(e))
+    n = min(int(out.counts[0, 2]), det.max_quads)
+    return out.quads.cpu().numpy()[0, :n], quad_detect.records_numpy(out.records)[0, :n]
+
+
 from .camera_calib import (CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST,  # noqa: E402,F401
                            CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
                            CALIB_RATIONAL_MODEL, CALIB_THIN_PRISM_MODEL, CALIB_FIX_S1_S2_S3_S4, CALIB_TILTED_MODEL, CALIB_FIX_TAUX_TAUY,

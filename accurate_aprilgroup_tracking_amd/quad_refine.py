@@ -3,8 +3,8 @@ tag's border, or refused.
 
 The stage of a tag detector between "a quad is roughly here" and "decode it": a line is fitted to the black-to-white step along each
 of the four border edges and the lines are intersected.  The seeds come from something else: the tracker's own corner buffer
-(StreamTracker.refine_tags), re-projected corners, or an outside detector's candidates (cv_hip.refineQuads).  Finding quads without a
-seed stays the outside detector's job.  The strength of a record is the mean step height along the weakest edge in gray levels: above
+(StreamTracker.refine_tags), re-projected corners, the quad finder's candidates (tag_detect.detect_tags) or an outside detector's
+(cv_hip.refineQuads).  Finding quads without a seed is quad_detect's job.  The strength of a record is the mean step height along the weakest edge in gray levels: above
 100 on a tag's border, around 10 on background texture.
 """
 import collections

@@ -1,8 +1,8 @@
 """Tag payload decoding on the device (include/agt_tagcode.h -> libagt_tagcode.so): which tag does a quad show, how sure, or none.
 
 The decode stage of a tag detector, applied to quads that something else found: the tracker's own corner buffer
-(StreamTracker.decode_tags) or an outside detector's candidates (cv_hip.decodeTags).  Finding quads in an image stays the outside
-detector's job.  The margin is this rule's own scale (for a clean tag: half the local black / white contrast in gray levels), not
+(StreamTracker.decode_tags), the quad finder's candidates (tag_detect.detect_tags) or an outside detector's (cv_hip.decodeTags).
+Finding quads in an image is quad_detect's job.  The margin is this rule's own scale (for a clean tag: half the local black / white contrast in gray levels), not
 the decision_margin of any apriltag release.
 
 A family is a list of 36-bit code words (bit 35 - (6 r + c) = row r, column c of the payload).  The real tag36h11 table is not

@@ -65,6 +65,7 @@ class StreamTracker:
         if predict_px:
             self.predict(predict_px)
         self._alive = []            # frames aliased by pyramid level 0 of the ring entries in flight
+        self._quad_detector = None  # detect_tags' workspace, made on first use
         self._keep_frames = max((max_level + 6) + 2, 12)
 
     def _dist_ptr(self):
@@ -317,6 +318,28 @@ class StreamTracker:
         mask = _device_view(sp, (self.B, T, 4), "|u1", self.dev).amin(dim=2)
         out = quad_refine.refine_quads(frames, quads, mask=mask, range_px=range_px, iters=iters, min_strength=min_strength)
         return out.records, out.quads.view(self.B, self.n, 2), out.corner_mask
+
+    def detect_tags(self, frames, family, tag_ids=None, max_hamming=2, min_margin=0.0):
+        """The model's tags found in `frames` (cuda u8 [B,H,W]) with no corner to start from (tag_detect: find -> refine -> decode,
+        include/agt_quadfind.h, agt_quadfit.h, agt_tagcode.h): how a tracker that has no body yet, or lost it, (re-)acquires on the
+        device.  family: a tag_decode.TagFamily; tag_ids: the family index of each tag of the model in model order (default 0..T-1).
+        -> (corners cuda f32 [B,n,2], corner_mask cuda u8 [B,n], records cuda u8 [B,Q,40] -- tag_decode.records_numpy gives the fields,
+        one per candidate slot of the finder): every candidate that decoded to a tag of the model is written into that tag's rows,
+        its corners rolled by the decoded rotation into model order; of two candidates with one id the larger margin wins, on a tie
+        the lower candidate index; every other tag's mask bytes are 0.  The result is what step_detected(frames, corners,
+        corner_mask) takes.  The tracker's own corner buffer is neither read nor written; step() is unchanged and never calls this.
+        Enqueues only."""
+        from . import quad_detect, tag_detect
+        assert self.n % 4 == 0, "detect_tags needs four corners per tag"
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.shape[0] == self.B
+        assert tuple(frames.shape[1:]) == (self.ctx.height, self.ctx.width) and frames.stride(2) == 1, "frames must be [B, H, W] with unit pixel stride"
+        T = self.n // 4
+        lut = tag_detect.family_lut(family, tag_ids, T, self.dev)
+        if self._quad_detector is None:
+            self._quad_detector = quad_detect.QuadDetector(self.ctx.width, self.ctx.height, max_batch=self.B)
+        tags = tag_detect.detect_tags(frames, family, detector=self._quad_detector, max_hamming=max_hamming, min_margin=min_margin)
+        corners, mask = tag_detect.corner_table(tags, lut, T)
+        return corners, mask, tags.decoded.records
 
     def new_state_buffer(self, frames=1):
         shape = (frames, self.B, H.STATE_STRIDE) if frames > 1 else (self.B, H.STATE_STRIDE)

@@ -2,7 +2,7 @@
  * agt_quadfit.h -- C ABI of libagt_quadfit.so: the edge refinement stage of a tag detector on the MI355X (gfx950).  Given quads that
  * are roughly right (the tracker's corner buffer, re-projected corners, an outside detector's candidates) it fits a line to the
  * black-to-white step along each of the four border edges and intersects the lines: the quad snapped onto the tag's border, with a
- * strength that tells a tag's border from background.  Finding quads without a seed is NOT done here.  No window around a corner is
+ * strength that tells a tag's border from background.  Finding quads without a seed is NOT done here (agt_quadfind.h).  No window around a corner is
  * iterated (a tag corner is an L-corner, not a saddle): whole edges are fitted and a corner comes out only as the intersection of two
  * fitted lines.
  *

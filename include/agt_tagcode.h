@@ -2,7 +2,7 @@
  * agt_tagcode.h -- C ABI of libagt_tagcode.so: the decode stage of a tag detector on the MI355X (gfx950).  Given quads (four image
  * points each, from the tracker's corner buffer or an outside detector) it reads the 6 x 6 payload printed inside each one, matches
  * it against a tag family and says which tag it is, how sure and whether the quad shows a tag at all.  Finding quads in an image is
- * NOT done here: that stays the outside detector's job.
+ * NOT done here: that is agt_quadfind.h's job.
  *
  * The rule (fixed; tests/tag_decode_numpy.py states it independently).  Everything is FP64, f32 inputs are promoted exactly.
  *   quad       four image points q0..q3 (f32 pixels, integer coordinates at pixel centres) in the model's corner order, sitting at
