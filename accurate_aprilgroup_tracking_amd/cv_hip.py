@@ -792,6 +792,48 @@ def detectQuads(gray, **options):
     return out.quads.cpu().numpy()[0, :n], quad_detect.records_numpy(out.records)[0, :n]
 
 
+FILLED, LINE_AA = -1, 16
+
+
+def _draw_one(what, img, kind, pt1, pt2, size, color):
+    """one primitive of include/agt_draw.h painted into the host array img, in place: upload, raster, copy back"""
+    from . import drawlib, overlay
+    _require_gpu()
+    if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3):
+        raise error("%s: img must be an 8-bit (H, W) or (H, W, 3) numpy array (it is changed in place)" % what)
+    try:
+        xy = [int(v) for v in (pt1[0], pt1[1], pt2[0], pt2[1])]
+        rec = drawlib.prims([(kind, xy[0], xy[1], xy[2], xy[3], int(size), [drawlib.pack_color(color) >> s & 255 for s in (0, 8, 16)])])
+    except (TypeError, ValueError, IndexError, OverflowError) as e:
+        raise error("%s: %s" % (what, e))
+    if any(abs(v) > drawlib.MAX_COORD for v in xy) or not 0 <= int(size) <= drawlib.MAX_SIZE:
+        raise error("%s: coordinates up to %d in magnitude and sizes 0..%d are drawn" % (what, drawlib.MAX_COORD, drawlib.MAX_SIZE))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = torch.from_numpy(np.ascontiguousarray(img)).to(dev)[None]
+    try:
+        overlay.draw_primitives(t, overlay.prims_tensor(rec, dev))
+    except drawlib.DrawError as e:
+        raise error(str(e))
+    np.copyto(img, t[0].cpu().numpy())
+    return img
+
+
+def circle(img, center, radius, color, thickness=-1):
+    """cv2.circle for FILLED circles (thickness < 0), in place on an 8-bit (H, W) or (H, W, 3) array: the disc of include/agt_draw.h,
+    dx^2 + dy^2 <= r^2 + r -- binary, not cv2's raster pixel for pixel.  An outlined circle raises `error`."""
+    if thickness >= 0:
+        raise error("circle: only filled circles (thickness=-1) are built")
+    return _draw_one("circle", img, 1, center, center, radius, color)
+
+
+def line(img, pt1, pt2, color, thickness=1, lineType=None):
+    """cv2.line in place on an 8-bit (H, W) or (H, W, 3) array: the segment of include/agt_draw.h, the pixels within thickness / 2 of
+    it with round caps (an even thickness paints thickness + 1 rows).  lineType is accepted and ignored: drawing is binary."""
+    if thickness < 1:
+        raise error("line: thickness must be at least 1")
+    return _draw_one("line", img, 2, pt1, pt2, thickness, color)
+
+
 from .camera_calib import (CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST,  # noqa: E402,F401
                            CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
                            CALIB_RATIONAL_MODEL, CALIB_THIN_PRISM_MODEL, CALIB_FIX_S1_S2_S3_S4, CALIB_TILTED_MODEL, CALIB_FIX_TAUX_TAUY,

@@ -6,9 +6,10 @@ north-star LK corner tracking that fills the hole at :573-574.
 
 Every cv2 call goes through `self.cv`, by default the HIP-backed `cv_hip` module, so the
 numbers come from the gfx950 kernels; without the HIP library or a GPU construction fails
-loudly.  Camera capture, drawing and the AprilTag detector itself are out of scope
-(SURVEY.md section 2 rows 4-6): a detector is injected as a callable, drawing is a no-op that
-records the projected points.
+loudly.  Camera capture and the AprilTag detector itself are out of scope
+(SURVEY.md section 2 rows 4-6): a detector is injected as a callable.  Drawing is opt-in
+(`draw=True`: the dots of the pose overlay and the tag outlines of the drawing frame, include/agt_draw.h);
+without it `_project_draw_points` only records the projected points.
 
 Two backends:
 
@@ -47,7 +48,7 @@ class PoseDetector(TransformHelper):
     CONSENSUS_MIN = 8       # inliers a tag hypothesis needs to be elected (pnp_consensus_px): more than one tag's own four
 
     def __init__(self, logger, mtx, dist, enhance_ape, cv=None, detector=None, backend="cv", lk_fb_px=None, pnp_consensus_px=None,
-                 lk_predict_px=None):
+                 lk_predict_px=None, draw=False):
         """`detector(gray) -> iterable of objects with .tag_id, .corners (4,2), .decision_margin`
         stands in for apriltag.Detector(...).detect (detect_pose.py:368-371).
         lk_fb_px: forward-backward check of the LK step (None / 0 = off): a tracked corner whose track back into the previous
@@ -62,7 +63,16 @@ class PoseDetector(TransformHelper):
         both gave an accepted pose, the constant-velocity extrapolation of those poses moves the start of every corner's search
         (predict_flow below; the rule: include/agt_hip.h agt_predict_flow); a prediction with a flow beyond this many pixels is not
         trusted and the frame is tracked as ever.  Backend "stream" hands it to its StreamTracker (predict_px); backend "cv" seeds
-        calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW."""
+        calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW.
+        draw: the reference's two images of every frame (detect_pose.py:441-465; the rule: include/agt_draw.h): a red dot on every
+        projected model corner of an accepted pose, and the tag outlines on a black `self.draw_frame` that is fresh every frame.
+        Backend "cv" draws on the host through the `Draw` mirror and the cv module's circle / line, the dots into `self.img` (which
+        `self.overlay` then names as well; for a gray frame `self.img` becomes its (g, g, g) copy, so the dots never land in the
+        array LK tracks from and the poses are those of draw=False).  Backend "stream" keeps both images on the device: `self.overlay` (the processed colour
+        frame with the dots; (g, g, g) for a gray camera) and `self.draw_frame` are cuda u8 (H, W, 3) tensors of the processed frame's
+        size, rewritten by every frame on the tracker's stream without a synchronisation of their own, and `self.img` stays the raw
+        frame; `_estimate_pose` called with correspondences alone has no frame and draws nothing there.  False (the default): nothing
+        is drawn, nothing more is launched and `draw_frame` stays None."""
         TransformHelper.__init__(self, logger, mtx, dist, cv=cv)
         if backend not in ("cv", "stream"):
             raise ValueError("backend must be 'cv' or 'stream'")
@@ -83,6 +93,9 @@ class PoseDetector(TransformHelper):
         self._dev = None                # stream backend: _DeviceStream, created at the first frame (its size fixes the context)
         self.img = None
         self.draw_frame = None
+        self.overlay = None
+        self.draw = bool(draw)
+        self._drawer = None             # backend "cv", draw=True: the Draw mirror on self.cv
         self.prev_transform = (None, None)
         self.extrinsic_guess = (None, None)
         self.rot_velocities = []
@@ -141,7 +154,7 @@ class PoseDetector(TransformHelper):
 
     @classmethod
     def from_files(cls, logger, camera_params, enhance_ape=True, cv=None, detector=None, april_group=None, backend="cv", lk_fb_px=None,
-                   pnp_consensus_px=None, lk_predict_px=None):
+                   pnp_consensus_px=None, lk_predict_px=None, draw=False):
         """Build from the reference's on-disk files: `CameraParams.npz` (calibrate_camera.py:107-123) and,
         optionally, an `april_group.json` somewhere else than DIRPATH/JSON_FILE (detect_pose.py:54-55).
         `detector` may be a recorded-detections .npz (formats.ReplayDetector) to replay a session."""
@@ -152,11 +165,11 @@ class PoseDetector(TransformHelper):
             detector = formats.ReplayDetector(detector)
         if april_group is None:
             return cls(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
-                       pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px)
+                       pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px, draw=draw)
         folder, name = os.path.split(os.fspath(april_group))
         sub = type(cls.__name__, (cls,), {"DIRPATH": folder or ".", "JSON_FILE": name})
         return sub(logger, mtx, dist, enhance_ape, cv=cv, detector=detector, backend=backend, lk_fb_px=lk_fb_px,
-                   pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px)
+                   pnp_consensus_px=pnp_consensus_px, lk_predict_px=lk_predict_px, draw=draw)
 
     # ------------------------------------------------------------------ model (detect_pose.py:105-227)
     def get_extrinsics(self):
@@ -232,9 +245,15 @@ class PoseDetector(TransformHelper):
         return img_list, obj_list, ids
 
     def _project_draw_points(self, transformation):
-        """detect_pose.py:441-465 minus the drawing: keeps the projected model corners."""
+        """detect_pose.py:441-465: keeps the projected model corners and, with draw=True, draws them into self.img and
+        self.draw_frame (backend "cv"; backend "stream" draws on the device, _DeviceStream._draw)."""
         self.projected_points, _ = self.cv.projectPoints(self.all_objpts, transformation[0], transformation[1],
                                                          self.mtx, self.dist)
+        if self.draw and self.img is not None and self.draw_frame is not None:
+            if self._drawer is None:
+                from .draw import Draw
+                self._drawer = Draw(self.logger, cv=self.cv)
+            self._drawer.draw_squares_and_3d_pts(self.img, self.draw_frame, self.projected_points)
 
     # ------------------------------------------------------------------ ★ the state machine (:467-574)
     def _estimate_pose(self, imgpoints_arr, objpoints_arr):
@@ -385,6 +404,13 @@ class PoseDetector(TransformHelper):
             return self._stream().frame(self, frame, raw=False)
         self.img = frame
         gray = self._to_gray(frame)
+        if self.draw:
+            # the dots go into a COLOUR image that is never the LK source: a BGR frame is its own overlay (gray is a cvtColor copy of
+            # it, as in the reference); a gray frame IS `gray`, which becomes _prev_gray, so it gets a (g, g, g) copy as on the device
+            if frame.ndim == 2:
+                self.img = np.repeat(frame[:, :, None], 3, axis=2)
+            self.overlay = self.img
+            self.draw_frame = np.zeros(frame.shape[:2] + (3,), np.uint8)
         img_list, obj_list, ids = ([], [], [])
         if self.detector is not None:
             img_list, obj_list, ids = self._obtain_detections(gray)
@@ -508,6 +534,9 @@ class _DeviceStream:
         self._pin = {}                  # frame_buffer(): pinned arrays handed to the caller (the capture writes into them)
         self._stage = {}                # pinned staging of frames that live anywhere else (never the caller's buffers)
         self.roi = None
+        self.draw = det.draw
+        self.ov_raw = None              # draw=True: the uploaded colour frame, the overlay (a view of it, or of its undistorted copy)
+        self.ov, self.draw_t = None, None       # and the drawing frame, all made at the first frame
 
     # ---- set-up at the first frame
     def _setup(self, det, shape, raw):
@@ -578,6 +607,45 @@ class _DeviceStream:
         np.copyto(t.numpy(), frame[:, :, None])
         return t
 
+    def _overlay_source(self, det, pin, staged):
+        """draw=True: where this frame's colour image for det.overlay comes from.  staged: the frame's own upload puts it into
+        self.bgr (every BGR or (g, g, g) frame of _ingest; the one-call path when it undistorts, which copies first): nothing more is
+        uploaded and _draw reads self.bgr.  Otherwise -- a gray frame that is not undistorted, a BGR frame the one-call path reads
+        from pinned memory directly -- `pin` is uploaded once more into ov_raw ((g, g, g) for a gray one), BEFORE the frame is tracked:
+        the copy has left `pin` when the frame's record arrives."""
+        torch = self.torch
+        if self.ov_raw is None:
+            h, w = self.src_hw
+            dev = self.trk.dev
+            self.ov_raw = torch.zeros((1, h, w, 3), dtype=torch.uint8, device=dev)
+            self.ov_gray = torch.zeros((h, w), dtype=torch.uint8, device=dev)
+            self.draw_t = torch.zeros((1, self.gh, self.gw, 3), dtype=torch.uint8, device=dev)
+            obj = np.asarray(det.all_objpts)
+            self.obj_draw = torch.from_numpy(np.ascontiguousarray(obj.reshape(-1, 3), dtype=np.float32 if obj.dtype == np.float32 else np.float64)).to(dev)
+        self.ov_staged = staged
+        if staged:
+            return
+        if pin.dim() == 2:
+            self.ov_gray.copy_(pin, non_blocking=True)
+            self.ov_raw[0].copy_(self.ov_gray.unsqueeze(2).expand(-1, -1, 3))
+        else:
+            self.ov_raw[0].copy_(pin, non_blocking=True)
+
+    def _draw(self, det):
+        """draw=True: the overlay -- a tensor of its own, never the staging buffer: the undistorted copy of the colour frame cropped to
+        the ROI as a view, or ov_raw (a device-to-device copy of self.bgr when the frame was staged there) -- then dots into it and
+        outlines onto the cleared drawing frame, at the pose of the record in rec_dev and only if it was accepted; enqueued behind the
+        frame's own work, nothing is read back"""
+        if self.undistort:
+            x, y, w, h = self.roi
+            self.ov = self.trk.ctx.undistort_bgr(self.bgr if self.ov_staged else self.ov_raw)[:, y:y + h, x:x + w]
+        else:
+            if self.ov_staged:
+                self.ov_raw.copy_(self.bgr)
+            self.ov = self.ov_raw
+        self.trk.draw_overlay(self.ov, self.draw_t, self.rec_dev, obj=self.obj_draw)
+        det.overlay, det.draw_frame = self.ov[0], self.draw_t[0]
+
     def _upload(self, dst, src_t, nbytes):
         ctx = self.trk.ctx
         self.H.check(ctx.L.agt_upload(ctx.h, self.C.c_void_p(dst.data_ptr()), self.C.c_void_p(src_t.data_ptr()), nbytes), "agt_upload")
@@ -599,12 +667,16 @@ class _DeviceStream:
         if frame.ndim == 2 and not self.undistort:
             assert frame.shape == (self.gh, self.gw)
             pin = self._pinned(frame)
+            if self.draw:
+                self._overlay_source(det, pin, staged=False)
             if self.gpitch == self.gw:
                 self._upload(g, pin, frame.size)
             else:       # pitch-padded rows: 2-D copy through torch (rare: widths that are not a multiple of 16)
                 g[0, :, :self.gw].copy_(pin, non_blocking=True)
             return g[:, :, :self.gw]
         pin = self._gray_as_bgr(frame) if frame.ndim == 2 else self._pinned(frame)
+        if self.draw:
+            self._overlay_source(det, pin, staged=True)
         if self.bgr is None:
             self.bgr = torch.zeros((1,) + tuple(pin.shape), dtype=torch.uint8, device=self.trk.dev)
         self._upload(self.bgr, pin, pin.numel())
@@ -627,10 +699,14 @@ class _DeviceStream:
             mask = self.table_dev[self.n * 8:].view(1, self.n)
             self.trk.step_detected(g, pts, mask, self.rec_dev)
             self.has_prev = self.has_prev or bool(ids)      # (the mirror's `if ids:`: a frame without any tag is no tracking source)
+            if self.draw:
+                self._draw(det)
             self._finish(det)
         else:
             self.trk.step(g, self.rec_dev)        # LK from the previous frame's corners: fills detect_pose.py:573-574
             self.trk.join()
+            if self.draw:
+                self._draw(det)
             self._finish(det, tracked=True)
 
     def _frame_tracked_one_call(self, det, frame, raw):
@@ -647,11 +723,16 @@ class _DeviceStream:
         pin = self._gray_as_bgr(frame) if (color and frame.ndim == 2) else self._pinned(frame)
         if color and self.bgr is None:
             self.bgr = self.torch.zeros((1,) + tuple(pin.shape), dtype=self.torch.uint8, device=self.trk.dev)
+        if self.draw:
+            self._overlay_source(det, pin, staged=bool(color and self.undistort))
         self.H.check(ctx.L.agt_track_host_frame(ctx.h, C.c_void_p(pin.data_ptr()), 3 if color else 1, self.src_hw[1], self.src_hw[0],
                                                 C.c_void_p(self.bgr.data_ptr()) if color else None, int(self.undistort and color),
                                                 self.roi[0] if color else 0, self.roi[1] if color else 0, C.c_void_p(g.data_ptr()), self.gpitch,
-                                                None,      # (no device copy of the record: it arrives in host memory, polled)
+                                                # (no device copy of the record, it arrives in host memory, polled -- unless the drawing reads it)
+                                                C.c_void_p(self.rec_dev.data_ptr()) if self.draw else None,
                                                 C.c_void_p(self.rec_host.data_ptr())), "agt_track_host_frame")
+        if self.draw:
+            self._draw(det)
         self.trk._alive.append(g)
         if len(self.trk._alive) > self.trk._keep_frames:
             del self.trk._alive[0]

@@ -341,6 +341,23 @@ class StreamTracker:
         corners, mask = tag_detect.corner_table(tags, lut, T)
         return corners, mask, tags.decoded.records
 
+    def draw_overlay(self, frames_bgr, draw_frames, state, radius=5, thickness=5, obj=None):
+        """The reference's two images of a frame (detect_pose.py:441-465; overlay.draw_pose, include/agt_draw.h) without the pose leaving
+        the device: the model is projected at the poses of `state` -- a record block cuda f64 [B, STATE_STRIDE] that step() (or
+        step_detected / estimate_pose) filled; with the pipeline on, join() first --, a dot is painted on every projected corner into
+        frames_bgr (cuda u8 [B,H,W,3] or [B,H,W], in place) and the tag outlines on draw_frames (same layout), which are cleared first.
+        A stream whose record is not accepted (ST_OK is not 1) keeps its frame untouched and gets a black drawing frame.  obj: the model
+        points to project, cuda f32 or f64 [n,3] (default: the tracker's own f32 copy).  -> the projected points cuda [B,n,2].
+        Enqueues on the tracker's stream; nothing is read back and nothing synchronises.  step() never calls this."""
+        from . import overlay
+        assert state.is_cuda and state.dtype == torch.float64 and tuple(state.shape) == (self.B, H.STATE_STRIDE) and state.stride(1) == 1
+        assert self.n % 4 == 0, "draw_overlay needs four corners per tag"
+        self.ctx.use_current_stream()
+        pose = state[:, :6].contiguous()
+        points, _ = self.ctx.project_points(self.obj if obj is None else obj, pose, self.K, self.dist if self.ndist else None)
+        overlay.draw_pose(frames_bgr, draw_frames, points, ok=state[:, H.ST_OK], radius=radius, thickness=thickness)
+        return points
+
     def new_state_buffer(self, frames=1):
         shape = (frames, self.B, H.STATE_STRIDE) if frames > 1 else (self.B, H.STATE_STRIDE)
         return torch.zeros(shape, dtype=torch.float64, device=self.dev)
