@@ -7,8 +7,9 @@ image centre, no distortion, focal lengths by the closed form over per-view homo
 of the absolute conic, as cvInitIntrinsicParams2D poses them; host numpy, normalised DLT).  The view poses come from ONE call of the
 batched masked solvePnP of the per-frame library, which takes its planar-homography branch.
 
-:func:`target_points_from_detections` turns a detection recording of a flat tag board into the per-view point lists: there is no
-chessboard finder here; corner lists from elsewhere go into calibrate_camera directly.
+:func:`target_points_from_detections` turns a detection recording of a flat tag board into the per-view point lists,
+:func:`target_points_from_chessboards` photographs of a printed chessboard (chessboard.find_chessboard finds the corners); corner
+lists from elsewhere go into calibrate_camera directly.
 """
 import numpy as np
 
@@ -263,6 +264,38 @@ def target_points_from_detections(frames, board, decision_margin=formats.DECISIO
     for f in sorted(set(fr.tolist())):
         rows = np.nonzero(fr == f)[0]
         obj.append(pts[tg[rows]].reshape(-1, 3)); img.append(co[rows].reshape(-1, 2)); used.append(int(f))
+    return obj, img, used
+
+
+def chessboard_object_points(pattern_size, square_size):
+    """(nx ny, 3): (i square, j square, 0) row by row, i = 0..nx-1 along a row -- the reference's objp (calibrate_camera.py:93-98)"""
+    nx, ny = int(pattern_size[0]), int(pattern_size[1])
+    if nx < 2 or ny < 2 or not float(square_size) > 0.0:
+        raise ValueError("chessboard_object_points: a pattern of at least 2 x 2 inner corners and a square size > 0 are needed")
+    i, j = np.meshgrid(np.arange(nx, dtype=np.float64), np.arange(ny, dtype=np.float64))
+    return np.stack([i.ravel() * float(square_size), j.ravel() * float(square_size), np.zeros(nx * ny)], axis=1)
+
+
+def target_points_from_chessboards(images, pattern_size, square_size, find=None, **options):
+    """Photographs of a chessboard -> (object_points, image_points, image_index), in the shapes target_points_from_detections returns:
+    per image in which the whole board was found the (nx ny, 3) object points (i square, j square, 0) and the (nx ny, 2) corners, and
+    the image's index.  images: host u8 frames, gray (H, W) or BGR (H, W, 3), of any sizes.  pattern_size: the INNER corners (nx, ny).
+    find: gray (H, W) u8 -> (found, corners), cv_hip.findChessboardCorners' contract (that function when None; options go to it)."""
+    pts = chessboard_object_points(pattern_size, square_size)
+    if find is None:
+        from . import cv_hip
+        find = lambda gray: cv_hip.findChessboardCorners(gray, pattern_size, **options)
+    obj, img, used = [], [], []
+    for k, frame in enumerate(images):
+        a = np.asarray(frame)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+            raise ValueError("target_points_from_chessboards: image %d is not an 8-bit gray or BGR frame" % k)
+        if a.ndim == 3:
+            # cv2's BGR2GRAY weights in its 14-bit fixed point; host numpy: a calibration reads each photograph once
+            a = ((a[..., 0].astype(np.int32) * 1868 + a[..., 1].astype(np.int32) * 9617 + a[..., 2].astype(np.int32) * 4899 + 8192) >> 14).astype(np.uint8)
+        found, corners = find(np.ascontiguousarray(a))
+        if found:
+            obj.append(pts.copy()); img.append(np.asarray(corners, np.float64).reshape(-1, 2)); used.append(k)
     return obj, img, used
 
 

@@ -792,6 +792,80 @@ def detectQuads(gray, **options):
     return out.quads.cpu().numpy()[0, :n], quad_detect.records_numpy(out.records)[0, :n]
 
 
+def findChessboardCorners(image, patternSize, corners=None, flags=0, **options):
+    """cv2.findChessboardCorners' contract on this project's own method (chessboard.find_chessboard, include/agt_chess.h): image (H, W)
+    gray u8 on the host, patternSize (nx, ny) INNER corners -> (retval, corners (nx ny, 1, 2) float32, row by row, already refined
+    to the sub-pixel saddle points: no cornerSubPix call is needed after it).  retval is False, and the corners are zero, when no grid
+    of exactly that size is found.  It is not cv2's adaptive-threshold and link-quads method, so none of cv2's flags means anything
+    here: any non-zero flag is refused.  `corners` is accepted and ignored, as cv2 does.  options: as
+    chessboard.ChessboardFinder.corners takes them, and max_candidates (1024)."""
+    from . import chessboard
+    if flags:
+        raise error("findChessboardCorners: flags (%r) are cv2's method's; none is supported" % (flags,))
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise error("findChessboardCorners: image must be a 2-D uint8 (gray) image")
+    try:
+        nx, ny = int(patternSize[0]), int(patternSize[1])
+    except (TypeError, ValueError, IndexError) as e:
+        raise error("findChessboardCorners: patternSize: %s" % e)
+    if nx < 2 or ny < 2:
+        raise error("findChessboardCorners: patternSize must be at least 2 x 2 inner corners")
+    _require_gpu()
+    img = np.ascontiguousarray(img) if img.flags.writeable else img.copy()      # (torch takes no read-only array)
+    sizes = {k: options.pop(k) for k in ("max_candidates",) if k in options}
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        finder = chessboard.ChessboardFinder(img.shape[1], img.shape[0], 1, **sizes)
+        found, pts = chessboard.find_chessboard(torch.from_numpy(img).to(dev)[None], (nx, ny), finder, **options)[0]
+    except (chessboard.Q.ChessError, TypeError) as e:
+        raise error(str(e))
+    return bool(found), pts.reshape(nx * ny, 1, 2)
+
+
+CHESSBOARD_ROW_COLORS = ((0, 0, 255), (0, 128, 255), (0, 200, 200), (0, 255, 0), (200, 200, 0), (255, 0, 0), (255, 0, 255))     # cv2's
+CHESSBOARD_RADIUS = 4
+
+
+def chessboard_display_list(patternSize, corners, patternWasFound):
+    """The display list drawChessboardCorners paints (drawlib.PRIM_DTYPE array): found -- a segment between consecutive corners, then
+    a disc on every corner, one colour per row; not found -- a red disc on every corner.  Coordinates are rounded half away from zero."""
+    from . import drawlib
+    nx = int(patternSize[0])
+    pts = np.asarray(corners, np.float64).reshape(-1, 2)
+    if not np.isfinite(pts).all():
+        raise error("drawChessboardCorners: corners must be finite")
+    xy = (np.sign(pts) * np.floor(np.abs(pts) + 0.5)).astype(np.int64)
+    rec = []
+    if patternWasFound:
+        for k in range(1, len(xy)):
+            rec.append((drawlib.SEGMENT, xy[k - 1, 0], xy[k - 1, 1], xy[k, 0], xy[k, 1], 1, CHESSBOARD_ROW_COLORS[(k // nx) % 7]))
+    for k in range(len(xy)):
+        color = CHESSBOARD_ROW_COLORS[(k // nx) % 7] if patternWasFound else (0, 0, 255)
+        rec.append((drawlib.DISC, xy[k, 0], xy[k, 1], xy[k, 0], xy[k, 1], CHESSBOARD_RADIUS, color))
+    if any(abs(int(v)) > drawlib.MAX_COORD for v in xy.ravel()):
+        raise error("drawChessboardCorners: coordinates up to %d in magnitude are drawn" % drawlib.MAX_COORD)
+    return drawlib.prims(rec)
+
+
+def drawChessboardCorners(image, patternSize, corners, patternWasFound):
+    """cv2.drawChessboardCorners' arguments: image (H, W) or (H, W, 3) u8, changed in place and returned.  It paints
+    chessboard_display_list with overlay.draw_primitives: binary discs and segments, not cv2's raster."""
+    from . import drawlib, overlay
+    _require_gpu()
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8 or image.ndim not in (2, 3) or (image.ndim == 3 and image.shape[2] != 3):
+        raise error("drawChessboardCorners: image must be an 8-bit (H, W) or (H, W, 3) numpy array (it is changed in place)")
+    rec = chessboard_display_list(patternSize, corners, patternWasFound)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]
+    try:
+        overlay.draw_primitives(t, overlay.prims_tensor(rec, dev))
+    except drawlib.DrawError as e:
+        raise error(str(e))
+    np.copyto(image, t[0].cpu().numpy())
+    return image
+
+
 FILLED, LINE_AA = -1, 16
 
 
