@@ -5,6 +5,7 @@ A module keeps LIB_PATH, _lib and lib() of its own -- lib() reads the module's L
 a function that declares the argument types.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -77,3 +78,78 @@ def _f64(a, shape):
 
 def _addr(a):
     return C.c_void_p(a.ctypes.data)
+
+
+# ---- the image stages (tagcode, quadfit, quadfind, draw, chess): raw device addresses in, a batch of 8-bit frames as the input
+
+# agt_side_math.h's codes, under every library's own prefix; a library with more codes adds them to a copy of ERRORS
+OK = 0
+ERR_ARG, ERR_ALLOC, ERR_HIP = -1, -2, -5
+ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_HIP: "HIP"}
+
+
+def vp(a):
+    """a raw device address (an int, or None / 0 for NULL) as a ctypes argument"""
+    return C.c_void_p(a) if a else None
+
+
+def make_options(defaults, ints, floats, error_cls, what, kw):
+    """`defaults` with `kw` over them -> dict; an unknown name, an option of `ints` that no int32 holds or one of `floats` that is no
+    number is refused here (the ranges are the library's to check)"""
+    unknown = sorted(set(kw) - set(defaults))
+    if unknown:
+        raise TypeError("unknown %s option(s) %s (known: %s)" % (what, ", ".join(unknown), ", ".join(defaults)))
+    o = dict(defaults, **kw)
+    for k in ints:
+        if int(o[k]) != o[k] or not -2 ** 31 <= int(o[k]) < 2 ** 31:
+            raise error_cls(ERR_ARG, "option %s = %r" % (k, o[k]))
+    for k in floats:
+        if math.isnan(float(o[k])):
+            raise error_cls(ERR_ARG, "option %s = %r" % (k, o[k]))
+    return o
+
+
+def records_numpy(records, dtype):
+    """a u8 tensor [..., dtype.itemsize] of records (or its numpy copy) -> structured array [...] of `dtype` (synchronises)"""
+    a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
+    return np.ascontiguousarray(a).view(dtype).reshape(a.shape[:-1])
+
+
+GRAY_FRAMES = "frames must be cuda u8 [B, H, W] with unit pixel stride"
+
+
+def is_gray_frames(frames):
+    """what the image stages read (any row and frame stride)"""
+    import torch
+    return isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3 and frames.stride(2) == 1
+
+
+def check_frames(frames, min_size, width, height, max_batch, error_cls, what):
+    """-> (B, h, w) of frames on a workspace `what` made for [max_batch, height, width]"""
+    if not is_gray_frames(frames):
+        raise ValueError(GRAY_FRAMES)
+    B, h, w = frames.shape
+    if not (min_size <= w <= width and min_size <= h <= height and 1 <= B <= max_batch):
+        raise error_cls(ERR_ARG, "frames of shape %s on a %s for [%d, %d, %d]" % (tuple(frames.shape), what, max_batch, height, width))
+    return B, h, w
+
+
+def frame_args(frames):
+    """the call tail every image stage takes: (the current stream of the frames' device, pointer, pitch, frame_stride, width, height, B)"""
+    from .cv_hip import _raw_stream
+    B, h, w = frames.shape[:3]
+    return (_raw_stream(frames.device.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B)
+
+
+class PerDevice:
+    """cache(device index) -> factory(*args), made with that device current on first use, once per device"""
+
+    def __init__(self, factory, *args):
+        self.factory, self.args, self.made = factory, args, {}
+
+    def __call__(self, device):
+        if device not in self.made:
+            import torch
+            with torch.cuda.device(device):
+                self.made[device] = self.factory(*self.args)
+        return self.made[device]

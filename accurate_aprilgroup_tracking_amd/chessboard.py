@@ -11,22 +11,13 @@ import collections
 
 import numpy as np
 
+from . import _sidelib
 from . import chesslib as Q
 
 Corners = collections.namedtuple("Corners", "candidates counts records")
 Corners.__doc__ = """ChessboardFinder.corners' result, all cuda tensors: candidates i32 [B, max_candidates, 3] (x, y, response, in
 raster order), counts i32 [B, 4] (candidates before the cap, candidates written, the frame's largest response, flag bits), records u8
 [B, max_candidates, 48] (records_numpy gives the fields: x, y, det, shift, xf, yf, verdict).  Entries behind counts[b, 1] are zero."""
-
-
-def _check_frames(frames, width, height, max_batch):
-    import torch
-    if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3 and frames.stride(2) == 1):
-        raise ValueError("frames must be cuda u8 [B, H, W] with unit pixel stride")
-    B, h, w = frames.shape
-    if not (Q.MIN_SIZE <= w <= width and Q.MIN_SIZE <= h <= height and 1 <= B <= max_batch):
-        raise Q.ChessError(Q.ERR_ARG, "frames of shape %s on a ChessboardFinder for [%d, %d, %d]" % (tuple(frames.shape), max_batch, height, width))
-    return B, h, w
 
 
 class ChessboardFinder:
@@ -39,22 +30,15 @@ class ChessboardFinder:
                                 ("max_batch", self.max_batch, 1, Q.MAX_BATCH), ("max_candidates", self.max_candidates, 1, Q.MAX_CANDIDATES)):
             if not lo <= v <= hi:
                 raise Q.ChessError(Q.ERR_ARG, "ChessboardFinder(%s=%d), limits %d..%d" % (name, v, lo, hi))
-        self._finders = {}
-
-    def _finder(self, device):
-        import torch
-        if device not in self._finders:
-            with torch.cuda.device(device):
-                self._finders[device] = Q.Finder(self.width, self.height, self.max_batch, self.max_candidates)
-        return self._finders[device]
+        self._finder = _sidelib.PerDevice(Q.Finder, self.width, self.height, self.max_batch, self.max_candidates)
 
     def _call(self, frames):
         import torch
-        from .cv_hip import _raw_stream, _require_gpu
-        B, h, w = _check_frames(frames, self.width, self.height, self.max_batch)
+        from .cv_hip import _require_gpu
+        _sidelib.check_frames(frames, Q.MIN_SIZE, self.width, self.height, self.max_batch, Q.ChessError, "ChessboardFinder")
         _require_gpu()
         dev = frames.device
-        return torch, dev, self._finder(dev.index), (_raw_stream(dev.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B)
+        return torch, dev, self._finder(dev.index), _sidelib.frame_args(frames)
 
     def response(self, frames):
         """-> cuda i32 [B, H, W]: the corner response of every pixel (0 closer than 5 to a border).  Enqueues only."""
@@ -106,8 +90,7 @@ class ChessboardFinder:
 
 def records_numpy(records):
     """records tensor (or its numpy copy) -> structured array [B, max_candidates] with the fields of agt_chess_record (synchronises)"""
-    a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
-    return np.ascontiguousarray(a).view(Q.RECORD_DTYPE).reshape(a.shape[:-1])
+    return _sidelib.records_numpy(records, Q.RECORD_DTYPE)
 
 
 # ---- stage 4: the grid, on the host

@@ -1,20 +1,17 @@
 """ctypes binding of the chessboard corner finder (include/agt_chess.h -> libagt_chess.so).
 Built by build() of __graft_entry__ and loaded by _sidelib.load under the rules of hiplib: there is no CPU fallback."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 
 from . import _sidelib
+from ._sidelib import ERR_ALLOC, ERR_ARG, ERR_HIP, ERRORS, OK, vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_chess.so")
 
 VERSION = 100
-OK = 0
-ERR_ARG, ERR_ALLOC, ERR_HIP = -1, -2, -5
-ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_HIP: "HIP"}
 MIN_SIZE, MAX_SIZE, MAX_BATCH, MAX_CANDIDATES, MAX_NMS, MAX_HALF, MAX_ITERS = 11, 8192, 64, 65536, 8, 11, 64
 FLAG_CANDIDATES = 1
 VERDICT_OK, VERDICT_BORDER, VERDICT_FLAT, VERDICT_SHIFT = 0, 1, 2, 3
@@ -72,21 +69,8 @@ check = ChessError.check
 def options(**kw):
     """the defaults with `kw` over them -> Options; an unknown name, an integer option that no int32 holds or a float option that is
     no number is refused here (the ranges are the library's to check)"""
-    unknown = sorted(set(kw) - set(DEFAULTS))
-    if unknown:
-        raise TypeError("unknown chessboard option(s) %s (known: %s)" % (", ".join(unknown), ", ".join(DEFAULTS)))
-    o = dict(DEFAULTS, **kw)
-    for k in _INTS:
-        if int(o[k]) != o[k] or not -2 ** 31 <= int(o[k]) < 2 ** 31:
-            raise ChessError(ERR_ARG, "option %s = %r" % (k, o[k]))
-    for k in ("max_shift", "min_det"):
-        if math.isnan(float(o[k])):
-            raise ChessError(ERR_ARG, "option %s = %r" % (k, o[k]))
+    o = _sidelib.make_options(DEFAULTS, _INTS, ("max_shift", "min_det"), ChessError, "chessboard", kw)
     return Options(*([int(o[k]) for k in _INTS] + [0, float(o["max_shift"]), float(o["min_det"])]))
-
-
-def _vp(a):
-    return C.c_void_p(a) if a else None
 
 
 class Finder(_sidelib.Handle):
@@ -104,17 +88,17 @@ class Finder(_sidelib.Handle):
 
     def response(self, stream, frames_ptr, pitch, frame_stride, width, height, B, response_ptr):
         """agt_chess_response on raw device addresses (ints or None); enqueues only"""
-        check(self.L.agt_chess_response(self.h, _vp(stream), _vp(frames_ptr), pitch, frame_stride, width, height, B, _vp(response_ptr)),
+        check(self.L.agt_chess_response(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, vp(response_ptr)),
               "agt_chess_response")
 
     def candidates(self, stream, frames_ptr, pitch, frame_stride, width, height, B, opts, cands_ptr, counts_ptr):
-        check(self.L.agt_chess_candidates(self.h, _vp(stream), _vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
-                                          _vp(cands_ptr), _vp(counts_ptr)), "agt_chess_candidates")
+        check(self.L.agt_chess_candidates(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
+                                          vp(cands_ptr), vp(counts_ptr)), "agt_chess_candidates")
 
     def refine(self, stream, frames_ptr, pitch, frame_stride, width, height, B, opts, cands_ptr, counts_ptr, records_ptr):
-        check(self.L.agt_chess_refine(self.h, _vp(stream), _vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
-                                      _vp(cands_ptr), _vp(counts_ptr), _vp(records_ptr)), "agt_chess_refine")
+        check(self.L.agt_chess_refine(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
+                                      vp(cands_ptr), vp(counts_ptr), vp(records_ptr)), "agt_chess_refine")
 
     def corners(self, stream, frames_ptr, pitch, frame_stride, width, height, B, opts, cands_ptr, counts_ptr, records_ptr):
-        check(self.L.agt_chess_corners(self.h, _vp(stream), _vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
-                                       _vp(cands_ptr), _vp(counts_ptr), _vp(records_ptr)), "agt_chess_corners")
+        check(self.L.agt_chess_corners(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, self._opts(opts),
+                                       vp(cands_ptr), vp(counts_ptr), vp(records_ptr)), "agt_chess_corners")

@@ -4,13 +4,15 @@
 //   ch_response     one workgroup per TILE_W x TILE_H pixels: the tile and a 5-pixel halo staged in LDS once, the ring read from there;
 //                   the workgroup's largest response feeds the frame's atomicMax
 //   ch_count        one thread per pixel: the candidate test (thresholds, then the suppression window) into a byte mask, candidates
-//                   per SCAN_CHUNK pixels
+//                   per AGT_SCAN_CHUNK pixels
 //   ch_scan         one workgroup per frame: exclusive scan of those counts (so ids follow raster order), the frame's counts, the
 //                   table behind the written candidates zeroed
 //   ch_emit         the candidates of a chunk into their places of the table
 //   ch_refine       one wave per candidate, four to a workgroup: the saddle-point iteration, the window's samples in LDS
 // No kernel waits for another workgroup.  Every loop is a `for` with its bound in the header of the loop.
 // Every global write is a vector store or an atomic.
+// Shared with the other image stages: the frame arguments and their rule (agt_side_frames.h), the handle's buffers (agt_side_buffers.h),
+// the ordered compaction behind ch_count / ch_scan / ch_emit, the fixed-order wave sum and the bilinear fetch (agt_side_device.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -19,6 +21,7 @@
 
 #include "agt_side_buffers.h"
 #include "agt_side_device.h"
+#include "agt_side_frames.h"
 #include "../../include/agt_chess.h"
 
 #pragma clang fp contract(off)
@@ -29,18 +32,18 @@ static_assert(sizeof(agt_chess_record) == 48 && sizeof(agt_chess_options) == 40,
 
 namespace {
 
+using agt_side::Frames;
+using agt_side::div_up;
+
 constexpr int RING = 5;                                                 // the ring's radius = the halo = the border without a response
 constexpr int TILE_W = 64, TILE_H = 16, TILE_PX = TILE_W * TILE_H;      // a response workgroup's pixels
 constexpr int STAGE_W = TILE_W + 2 * RING, STAGE_H = TILE_H + 2 * RING, STAGE_PITCH = STAGE_W + 2;        // LDS: 26 x 76 bytes
 constexpr int RESP_THREADS = 256, PX_PER_THREAD = TILE_PX / RESP_THREADS;
-constexpr int SCAN_THREADS = 256, SCAN_ITERS = 4, SCAN_CHUNK = SCAN_THREADS * SCAN_ITERS, SCAN_SEGS = SCAN_ITERS * (SCAN_THREADS / 64);
 constexpr int REFINE_WAVES = 4, MAX_WIN = 2 * AGT_CHESS_MAX_HALF + 1, MAX_SAMP = MAX_WIN + 2;             // LDS: 4 x 625 doubles
 constexpr int REC_WORDS = sizeof(agt_chess_record) / 4;
 
 __device__ constexpr int RING_X[16] = { 5, 5, 4, 2, 0, -2, -4, -5, -5, -5, -4, -2, 0, 2, 4, 5 };
 __device__ constexpr int RING_Y[16] = { 0, 2, 4, 5, 5, 5, 4, 2, 0, -2, -4, -5, -5, -5, -4, -2 };
-
-struct Frames { const uint8_t* p; size_t pitch, stride; int w, h, B; };
 
 // the workspace, laid out for the call's frame size (n = w * h pixels, nchunk scan chunks per frame)
 struct Work {
@@ -129,57 +132,36 @@ __device__ __forceinline__ bool is_candidate(const int32_t* R, int i, int w, int
     return keep;
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void ch_count(Work K, int w, int h, Select S)
+__global__ __launch_bounds__(AGT_SCAN_THREADS) void ch_count(Work K, int w, int h, Select S)
 {
-    __shared__ int part[SCAN_THREADS / 64];
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = w * h;
+    __shared__ int part[AGT_SCAN_WAVES];
+    const int b = blockIdx.y, n = w * h;
     const int32_t* R = K.resp + (size_t)b * n;
     const int rmax = K.rmax[b];
     int found = 0;
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
-        const int i = blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x;
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
+        const int i = blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x;
         const bool c = i < n && is_candidate(R, i, w, h, rmax, S);
         if (i < n) K.mask[(size_t)b * n + i] = c ? 1 : 0;
         found += __popcll(__ballot(c));
     }
-    if (lane == 0) part[wave] = found;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int v = 0; v < SCAN_THREADS / 64; v++) s += part[v];
-        K.chunk[(size_t)b * K.nchunk + blockIdx.x] = s;
-    }
-}
-
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
+    const int total = agt_chunk_total(found, part);
+    if (threadIdx.x == 0) K.chunk[(size_t)b * K.nchunk + blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void ch_scan(Work K, int32_t* cands, int32_t* counts)
 {
     __shared__ int part[4];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x;
     int32_t* chunk = K.chunk + (size_t)b * K.nchunk;
     int run = 0;
     for (int base = 0; base < K.nchunk; base += 256) {
         const int i = base + threadIdx.x;
         const int c = i < K.nchunk ? chunk[i] : 0;
-        const int inc = wave_inclusive_sum(c, lane);
-        __syncthreads();                // (part may still be read from the round before)
-        if (lane == 63) part[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) { before += u < wave ? part[u] : 0; total += part[u]; }
-        if (i < K.nchunk) chunk[i] = run + before + inc - c;
+        int total;
+        const int ex = agt_block_exclusive_sum(c, part, total);
+        if (i < K.nchunk) chunk[i] = run + ex;
         run += total;
     }
     const int written = run < K.maxc ? run : K.maxc;
@@ -193,29 +175,25 @@ __global__ __launch_bounds__(256) void ch_scan(Work K, int32_t* cands, int32_t* 
     }
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void ch_emit(Work K, int w, int h, int32_t* cands)
+__global__ __launch_bounds__(AGT_SCAN_THREADS) void ch_emit(Work K, int w, int h, int32_t* cands)
 {
-    __shared__ int seg[SCAN_SEGS];
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = w * h;
+    __shared__ int seg[AGT_SCAN_SEGS];
+    const int b = blockIdx.y, n = w * h;
     const uint8_t* mask = K.mask + (size_t)b * n;
-    int kept[SCAN_ITERS], below[SCAN_ITERS];
+    int kept[AGT_SCAN_ITERS], below[AGT_SCAN_ITERS];
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
-        const int i = blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x;
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
+        const int i = blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x;
         kept[it] = i < n && mask[i] != 0;
-        const unsigned long long m = __ballot(kept[it]);
-        below[it] = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) seg[it * (SCAN_THREADS / 64) + wave] = __popcll(m);
+        below[it] = agt_chunk_below(kept[it], it, seg);
     }
     __syncthreads();
     const int first = K.chunk[(size_t)b * K.nchunk + blockIdx.x];
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
         if (!kept[it]) continue;
-        const int i = blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x, mine = it * (SCAN_THREADS / 64) + wave;
-        int id = first + below[it];
-#pragma unroll
-        for (int s = 0; s < SCAN_SEGS; s++) id += s < mine ? seg[s] : 0;
+        const int i = blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x;
+        const int id = agt_chunk_rank(first, below[it], it, seg);
         if (id < K.maxc) {
             int32_t* e = cands + ((size_t)b * K.maxc + id) * 3;
             const int y = i / w;
@@ -225,14 +203,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void ch_emit(Work K, int w, int h, in
 }
 
 // ---- (c) the saddle point: one wave per candidate
-
-// the sum of one value per lane in the header's order: P[l] += P[l xor m] for m = 32 .. 1; every lane ends with the same bits
-__device__ __forceinline__ double wave_sum_fixed(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64 * REFINE_WAVES) void ch_refine(Frames F, Refine A, const int32_t* cands, const int32_t* counts,
                                                               uint32_t* records, int maxc)
@@ -261,8 +231,7 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void ch_refine(Frames F, Refine 
             const double a = qx - fx, bb = qy - fy;
             for (int t = lane; t < ns * ns; t += 64) {
                 const int r = t / ns, c = t - r * ns;
-                const uint8_t* p = img + (size_t)(Y + r - A.half - 1) * F.pitch + (size_t)(X + c - A.half - 1);
-                samp[wave][t] = agt_blend4(a, bb, (double)p[0], (double)p[1], (double)p[F.pitch], (double)p[F.pitch + 1]);
+                samp[wave][t] = agt_bilinear_u8(img, F.pitch, X + c - A.half - 1, Y + r - A.half - 1, a, bb);
             }
         }
         __syncthreads();
@@ -279,7 +248,7 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void ch_refine(Frames F, Refine 
                 S1 = S1 + (gxx * px + gxy * py);
                 S2 = S2 + (gxy * px + gyy * py);
             }
-            Sa = wave_sum_fixed(Sa); Sb = wave_sum_fixed(Sb); Sc = wave_sum_fixed(Sc); S1 = wave_sum_fixed(S1); S2 = wave_sum_fixed(S2);
+            Sa = agt_wave_sum_fixed(Sa); Sb = agt_wave_sum_fixed(Sb); Sc = agt_wave_sum_fixed(Sc); S1 = agt_wave_sum_fixed(S1); S2 = agt_wave_sum_fixed(S2);
             det = Sa * Sc - Sb * Sb;
             if (!(det > A.min_det) || !agt_finite(det)) {
                 verdict = AGT_CHESS_VERDICT_FLAT; running = false;
@@ -313,8 +282,6 @@ __global__ __launch_bounds__(64 * REFINE_WAVES) void ch_refine(Frames F, Refine 
     out[11] = 0u;
 }
 
-inline int div_up(long long a, int b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
 
 struct agt_chess {
@@ -325,14 +292,8 @@ struct agt_chess {
 
 namespace {
 
-bool frames_ok(const agt_chess* q, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height, int B)
-{
-    if (!q || !d_frames) return false;
-    if (width < AGT_CHESS_MIN_SIZE || width > q->width || height < AGT_CHESS_MIN_SIZE || height > q->height || pitch < (size_t)width) return false;
-    if (B < 1 || B > q->max_batch) return false;
-    if (B > 1 && frame_stride < pitch * (size_t)(height - 1) + (size_t)width) return false;
-    return true;
-}
+// the frame rule against the handle's limits
+bool frames_ok(const agt_chess* q, const Frames& F) { return q && agt_side::frames_ok(F.p, F.pitch, F.stride, F.w, F.h, 1, F.B, AGT_CHESS_MIN_SIZE, q->width, q->height, q->max_batch); }
 
 // the defaults with `options` over them; false when a value is outside the header's ranges
 bool options_ok(const agt_chess_options* options, agt_chess_options& o)
@@ -343,12 +304,6 @@ bool options_ok(const agt_chess_options* options, agt_chess_options& o)
     if (o.half < 1 || o.half > AGT_CHESS_MAX_HALF || o.iters < 1 || o.iters > AGT_CHESS_MAX_ITERS || o.reserved0 != 0) return false;
     if (!(o.max_shift > 0.0 && o.max_shift <= 64.0) || !(o.min_det >= 0.0 && o.min_det <= 1.7976931348623157e308)) return false;
     return true;
-}
-
-Frames frames_of(const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height, int B)
-{
-    Frames F; F.p = d_frames; F.pitch = pitch; F.stride = frame_stride; F.w = width; F.h = height; F.B = B;
-    return F;
 }
 
 int enqueue_response(agt_chess* q, hipStream_t s, const Frames& F, int32_t* resp)
@@ -363,11 +318,11 @@ int enqueue_candidates(agt_chess* q, hipStream_t s, const Frames& F, const agt_c
 {
     RC(enqueue_response(q, s, F, q->K.resp));
     Work K = q->K;
-    K.nchunk = div_up((long long)F.w * F.h, SCAN_CHUNK);
+    K.nchunk = div_up((long long)F.w * F.h, AGT_SCAN_CHUNK);
     Select S; S.min_response = o.min_response; S.rel_pct = o.rel_pct; S.nms = o.nms;
-    hipLaunchKernelGGL(ch_count, dim3(K.nchunk, F.B), dim3(SCAN_THREADS), 0, s, K, F.w, F.h, S);
+    hipLaunchKernelGGL(ch_count, dim3(K.nchunk, F.B), dim3(AGT_SCAN_THREADS), 0, s, K, F.w, F.h, S);
     hipLaunchKernelGGL(ch_scan, dim3(F.B), dim3(256), 0, s, K, cands, counts);
-    hipLaunchKernelGGL(ch_emit, dim3(K.nchunk, F.B), dim3(SCAN_THREADS), 0, s, K, F.w, F.h, cands);
+    hipLaunchKernelGGL(ch_emit, dim3(K.nchunk, F.B), dim3(AGT_SCAN_THREADS), 0, s, K, F.w, F.h, cands);
     if (hipGetLastError() != hipSuccess) return AGT_CHESS_ERR_HIP;
     return AGT_CHESS_OK;
 }
@@ -403,55 +358,53 @@ int agt_chess_create(int width, int height, int max_batch, int max_candidates, a
     agt_chess* q = new (std::nothrow) agt_chess();
     if (!q) return AGT_CHESS_ERR_ALLOC;
     q->width = width; q->height = height; q->max_batch = max_batch; q->maxc = max_candidates;
-    const size_t B = (size_t)max_batch, n = (size_t)width * height, nc = (size_t)div_up((long long)n, SCAN_CHUNK);
+    const size_t B = (size_t)max_batch, n = (size_t)width * height, nc = (size_t)div_up((long long)n, AGT_SCAN_CHUNK);
     Work& K = q->K;
     K.maxc = max_candidates; K.nchunk = 0;
-    int rc = 0;
-    auto get = [&](auto** p, size_t count) { if (!rc) rc = q->buf.alloc(reinterpret_cast<void**>(p), count * sizeof(**p)); };
-    get(&K.resp, B * n); get(&K.mask, B * n); get(&K.chunk, B * nc); get(&K.rmax, B);
-    if (rc) { q->buf.free_all(); delete q; return rc; }
+    AgtSideBuffers& m = q->buf;
+    if (m.alloc_n(&K.resp, B * n) || m.alloc_n(&K.mask, B * n) || m.alloc_n(&K.chunk, B * nc) || m.alloc_n(&K.rmax, B)) {
+        agt_side_destroy(q);
+        return AGT_CHESS_ERR_ALLOC;
+    }
     *handle_out = q;
     return AGT_CHESS_OK;
 }
 
-int agt_chess_destroy(agt_chess* handle)
-{
-    if (!handle) return AGT_CHESS_ERR_ARG;
-    handle->buf.free_all();
-    delete handle;
-    return AGT_CHESS_OK;
-}
+int agt_chess_destroy(agt_chess* handle) { return agt_side_destroy(handle); }
 
 int agt_chess_response(agt_chess* handle, void* stream, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height,
                        int B, int32_t* d_response)
 {
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_response) return AGT_CHESS_ERR_ARG;
-    return enqueue_response(handle, (hipStream_t)stream, frames_of(d_frames, pitch, frame_stride, width, height, B), d_response);
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
+    if (!frames_ok(handle, F) || !d_response) return AGT_CHESS_ERR_ARG;
+    return enqueue_response(handle, (hipStream_t)stream, F, d_response);
 }
 
 int agt_chess_candidates(agt_chess* handle, void* stream, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height,
                          int B, const agt_chess_options* options, int32_t* d_candidates, int32_t* d_counts)
 {
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
     agt_chess_options o;
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_candidates || !d_counts || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
-    return enqueue_candidates(handle, (hipStream_t)stream, frames_of(d_frames, pitch, frame_stride, width, height, B), o, d_candidates, d_counts);
+    if (!frames_ok(handle, F) || !d_candidates || !d_counts || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
+    return enqueue_candidates(handle, (hipStream_t)stream, F, o, d_candidates, d_counts);
 }
 
 int agt_chess_refine(agt_chess* handle, void* stream, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height,
                      int B, const agt_chess_options* options, const int32_t* d_candidates, const int32_t* d_counts,
                      agt_chess_record* d_records)
 {
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
     agt_chess_options o;
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_candidates || !d_counts || !d_records || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
-    return enqueue_refine(handle, (hipStream_t)stream, frames_of(d_frames, pitch, frame_stride, width, height, B), o, d_candidates, d_counts, d_records);
+    if (!frames_ok(handle, F) || !d_candidates || !d_counts || !d_records || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
+    return enqueue_refine(handle, (hipStream_t)stream, F, o, d_candidates, d_counts, d_records);
 }
 
 int agt_chess_corners(agt_chess* handle, void* stream, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height,
                       int B, const agt_chess_options* options, int32_t* d_candidates, int32_t* d_counts, agt_chess_record* d_records)
 {
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
     agt_chess_options o;
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_candidates || !d_counts || !d_records || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
-    const Frames F = frames_of(d_frames, pitch, frame_stride, width, height, B);
+    if (!frames_ok(handle, F) || !d_candidates || !d_counts || !d_records || !options_ok(options, o)) return AGT_CHESS_ERR_ARG;
     RC(enqueue_candidates(handle, (hipStream_t)stream, F, o, d_candidates, d_counts));
     return enqueue_refine(handle, (hipStream_t)stream, F, o, d_candidates, d_counts, d_records);
 }

@@ -7,13 +7,22 @@
 //   Every barrier sits in wave-uniform control flow (the chunk loop's bounds are the kernel's arguments).  A pixel is written once, by its
 //   own thread, after the last chunk; a pixel outside the frame belongs to no thread that forms an address.
 // draw_pose_lists_kernel: one thread per point; it writes the point's dot and the outline segment that starts at it.
+// Shared with the other image stages: the frame arguments (here written to: MutableFrames) and their rule (agt_side_frames.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <limits.h>
 #include <stdint.h>
 
+#include "agt_side_frames.h"
+#include "agt_side_math.h"
 #include "../../include/agt_draw.h"
 
+static_assert(AGT_DRAW_OK == agt_side::OK && AGT_DRAW_ERR_ARG == agt_side::ERR_ARG && AGT_DRAW_ERR_HIP == agt_side::ERR_HIP,
+              "the codes of agt_side_math.h");
+
 namespace {
+
+using agt_side::div_up;
 
 constexpr int TILE_W = 32, TILE_H = 8;
 constexpr int THREADS = TILE_W * TILE_H;
@@ -23,8 +32,8 @@ static_assert(THREADS == AGT_DRAW_CHUNK, "a chunk is one primitive per thread");
 static_assert(sizeof(agt_draw_prim) == 32, "agt_draw_prim is 32 bytes");
 
 struct RasterCall {
-    uint8_t* frames; size_t pitch, frame_stride;
-    int w, h, channels, P;
+    agt_side::MutableFrames F;
+    int channels, P;
     const agt_draw_prim* prims;
     unsigned flags;
 };
@@ -67,7 +76,7 @@ __global__ __launch_bounds__(THREADS) void draw_raster_kernel(RasterCall C, int 
     const int tx1 = tx0 + TILE_W - 1, ty1 = ty0 + TILE_H - 1;       // the tile, inclusive (it may reach past the frame)
     const int b = batch0 + blockIdx.z;
     const int px = tx0 + (tid & (TILE_W - 1)), py = ty0 + tid / TILE_W;
-    const bool inside = px < C.w && py < C.h;
+    const bool inside = px < C.F.w && py < C.F.h;
 
     bool done = !inside, hit = false;
     uint32_t color = 0;
@@ -115,7 +124,7 @@ __global__ __launch_bounds__(THREADS) void draw_raster_kernel(RasterCall C, int 
     }
 
     if (!inside || !(hit || (C.flags & AGT_DRAW_CLEAR))) return;
-    uint8_t* out = C.frames + (size_t)b * C.frame_stride + (size_t)py * C.pitch + (size_t)px * (size_t)C.channels;
+    uint8_t* out = C.F.p + (size_t)b * C.F.stride + (size_t)py * C.F.pitch + (size_t)px * (size_t)C.channels;
     out[0] = (uint8_t)(color & 0xFFu);
     if (C.channels == 3) {
         out[1] = (uint8_t)((color >> 8) & 0xFFu);
@@ -196,22 +205,18 @@ int agt_draw_version(void) { return AGT_DRAW_VERSION; }
 int agt_draw_raster(void* stream, uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height, int channels, int B,
                     const agt_draw_prim* d_prims, int P, unsigned flags)
 {
-    if (!d_frames) return AGT_DRAW_ERR_ARG;
-    if (width < 1 || width > AGT_DRAW_MAX_SIZE_PX || height < 1 || height > AGT_DRAW_MAX_SIZE_PX) return AGT_DRAW_ERR_ARG;
     if (channels != 1 && channels != 3) return AGT_DRAW_ERR_ARG;
-    const size_t row = (size_t)width * (size_t)channels;
-    if (pitch < row) return AGT_DRAW_ERR_ARG;
-    if (P < 0 || P > AGT_DRAW_MAX_PRIMS || B < 1 || (long long)B * (long long)P > AGT_DRAW_MAX_TOTAL) return AGT_DRAW_ERR_ARG;
+    if (!agt_side::frames_ok(d_frames, pitch, frame_stride, width, height, channels, B, 1, AGT_DRAW_MAX_SIZE_PX, AGT_DRAW_MAX_SIZE_PX, INT_MAX)) return AGT_DRAW_ERR_ARG;
+    if (P < 0 || P > AGT_DRAW_MAX_PRIMS || (long long)B * (long long)P > AGT_DRAW_MAX_TOTAL) return AGT_DRAW_ERR_ARG;
     if (P > 0 && !d_prims) return AGT_DRAW_ERR_ARG;
-    if (B > 1 && frame_stride < pitch * (size_t)(height - 1) + row) return AGT_DRAW_ERR_ARG;
     if (flags & ~(unsigned)AGT_DRAW_CLEAR) return AGT_DRAW_ERR_ARG;
     if (P == 0 && !(flags & AGT_DRAW_CLEAR)) return AGT_DRAW_OK;
 
     RasterCall C;
-    C.frames = d_frames; C.pitch = pitch; C.frame_stride = frame_stride;
-    C.w = width; C.h = height; C.channels = channels; C.P = P;
+    C.F = agt_side::MutableFrames{ d_frames, pitch, frame_stride, width, height, B };
+    C.channels = channels; C.P = P;
     C.prims = d_prims; C.flags = flags;
-    const dim3 tiles((width + TILE_W - 1) / TILE_W, (height + TILE_H - 1) / TILE_H, 1);
+    const dim3 tiles(div_up(width, TILE_W), div_up(height, TILE_H), 1);
     for (int b0 = 0; b0 < B; b0 += MAX_BATCH_Z) {
         const int nb = B - b0 < MAX_BATCH_Z ? B - b0 : MAX_BATCH_Z;
         hipLaunchKernelGGL(draw_raster_kernel, dim3(tiles.x, tiles.y, nb), dim3(THREADS), 0, (hipStream_t)stream, C, b0);
@@ -239,7 +244,7 @@ int agt_draw_pose_lists(void* stream, const void* d_points, int dtype, int n, in
     C.w = width; C.h = height; C.radius = radius; C.thickness = thickness;
     C.dot_color = dot_color; C.line_color = line_color;
     C.dots = d_dots; C.outline = d_outline;
-    hipLaunchKernelGGL(draw_pose_lists_kernel, dim3((C.total + 255) / 256), dim3(256), 0, (hipStream_t)stream, C);
+    hipLaunchKernelGGL(draw_pose_lists_kernel, dim3(div_up(C.total, 256)), dim3(256), 0, (hipStream_t)stream, C);
     if (hipGetLastError() != hipSuccess) return AGT_DRAW_ERR_HIP;
     return AGT_DRAW_OK;
 }

@@ -5,7 +5,7 @@
 //   qf_label_tiles    one workgroup per TILE_W x TILE_H pixels: threshold, union-find in LDS, labels as global indices, the tile's areas
 //   qf_merge_borders  one thread per pixel on a workgroup-tile border: union with the pixel across the border (atomicMin, global)
 //   qf_flatten_area   one thread per pixel: label = root; a tile's root adds the tile's share of the area to the component's root
-//   qf_root_count     roots and roots inside the area limits per SCAN_CHUNK pixels
+//   qf_root_count     roots and roots inside the area limits per AGT_SCAN_CHUNK pixels
 //   qf_root_scan      one workgroup per frame: exclusive scan of those counts (ids follow label order), counts[0..1]
 //   qf_root_assign    the compact id of every root inside the area limits; its row of the component table set to the identities
 //   qf_support        one thread per pixel: the pixels of table components that can be extreme in a direction feed its atomicMax,
@@ -17,12 +17,16 @@
 // parent[i] <= i: find walks strictly decreasing indices, a merge is atomicMin on the larger root, so it ends without a lock; a stale
 // read only costs a step, never a wrong answer (the atomicMin's return value decides).
 // Every global write is a vector store or an atomic.
+// Shared with the other image stages: the frame arguments and their rule (agt_side_frames.h), the handle's buffers (agt_side_buffers.h),
+// the ordered compaction behind qf_root_count / _scan / _assign and qf_emit (agt_side_device.h; no floating point here: no mode re-stated).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
 #include <new>
 
 #include "agt_side_buffers.h"
+#include "agt_side_device.h"
+#include "agt_side_frames.h"
 #include "../../include/agt_quadfind.h"
 
 static_assert(AGT_QUADFIND_OK == agt_side::OK && AGT_QUADFIND_ERR_ARG == agt_side::ERR_ARG && AGT_QUADFIND_ERR_ALLOC == agt_side::ERR_ALLOC &&
@@ -31,17 +35,17 @@ static_assert(sizeof(agt_quadfind_record) == 32 && sizeof(agt_quadfind_options) 
 
 namespace {
 
+using agt_side::Frames;
+using agt_side::div_up;
+
 constexpr int TILE_W = 64, TILE_H = 16, TILE_PX = TILE_W * TILE_H;     // a labelling workgroup's pixels (LDS: 8 KiB)
 constexpr int SUPPORT_ROUNDS = 4;
 constexpr int LABEL_THREADS = 256, PX_PER_THREAD = TILE_PX / LABEL_THREADS;
-constexpr int SCAN_THREADS = 256, SCAN_ITERS = 4, SCAN_CHUNK = SCAN_THREADS * SCAN_ITERS, SCAN_SEGS = SCAN_ITERS * (SCAN_THREADS / 64);
 constexpr int PROJ_BIAS = 1 << 26;      // |x dx + y dy| <= 2 * 8192 * 1024 = 2^24
 constexpr int MIN_EDGE_SQ = 64;
 
 __device__ constexpr int DIR_X[16] = { 1024, 946, 724, 392, 0, -392, -724, -946, -1024, -946, -724, -392, 0, 392, 724, 946 };
 __device__ constexpr int DIR_Y[16] = { 0, 392, 724, 946, 1024, 946, 724, 392, 0, -392, -724, -946, -1024, -946, -724, -392 };
-
-struct Frames { const uint8_t* p; size_t pitch, stride; int w, h, B; };
 
 // the workspace, laid out for the call's frame size (n = w * h pixels, nt = th * tw tiles, nchunk scan chunks per frame)
 struct Work {
@@ -228,52 +232,20 @@ __device__ __forceinline__ int2 root_kind(const int32_t* L, const int32_t* area,
     return k;
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void qf_root_count(Work K, int n, int min_area, int max_area)
+__global__ __launch_bounds__(AGT_SCAN_THREADS) void qf_root_count(Work K, int n, int min_area, int max_area)
 {
-    __shared__ int2 part[SCAN_THREADS / 64];
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int2 part[AGT_SCAN_WAVES];
+    const int b = blockIdx.y;
     const int32_t *L = K.label + (size_t)b * n, *area = K.area + (size_t)b * n;
     int roots = 0, kept = 0;
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
-        const int2 k = root_kind(L, area, blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x, n, min_area, max_area);
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
+        const int2 k = root_kind(L, area, blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x, n, min_area, max_area);
         roots += __popcll(__ballot(k.x));
         kept += __popcll(__ballot(k.y));
     }
-    if (lane == 0) part[wave] = make_int2(roots, kept);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int2 s = make_int2(0, 0);
-#pragma unroll
-        for (int v = 0; v < SCAN_THREADS / 64; v++) { s.x += part[v].x; s.y += part[v].y; }
-        K.chunk[(size_t)b * K.nchunk + blockIdx.x] = s;
-    }
-}
-
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// The exclusive sum of one value per thread over a 256-thread workgroup in thread order, and the workgroup's total.
-// part: LDS, 4 ints; two barriers.
-__device__ __forceinline__ int block_exclusive_sum(int v, int* part, int& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = wave_inclusive_sum(v, lane);
-    __syncthreads();                // (part may still be read from the round before)
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int u = 0; u < 4; u++) { before += u < wave ? part[u] : 0; total += part[u]; }
-    return before + inc - v;
+    const int2 total = agt_chunk_total(make_int2(roots, kept), part);
+    if (threadIdx.x == 0) K.chunk[(size_t)b * K.nchunk + blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void qf_root_scan(Work K, int32_t* counts)
@@ -286,7 +258,7 @@ __global__ __launch_bounds__(256) void qf_root_scan(Work K, int32_t* counts)
         const int i = base + threadIdx.x;
         const int2 c = i < K.nchunk ? chunk[i] : make_int2(0, 0);
         int total;
-        const int ex = block_exclusive_sum(c.y, part, total);
+        const int ex = agt_block_exclusive_sum(c.y, part, total);
         if (i < K.nchunk) chunk[i].y = run + ex;
         run += total;
         int r = c.x;
@@ -299,28 +271,24 @@ __global__ __launch_bounds__(256) void qf_root_scan(Work K, int32_t* counts)
     if (threadIdx.x == 0) { counts[4 * b] = roots; counts[4 * b + 1] = run; }
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void qf_root_assign(Work K, int n, int min_area, int max_area)
+__global__ __launch_bounds__(AGT_SCAN_THREADS) void qf_root_assign(Work K, int n, int min_area, int max_area)
 {
-    __shared__ int seg[SCAN_SEGS];
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int seg[AGT_SCAN_SEGS];
+    const int b = blockIdx.y;
     const int32_t *L = K.label + (size_t)b * n, *area = K.area + (size_t)b * n;
-    int kept[SCAN_ITERS], below[SCAN_ITERS];
+    int kept[AGT_SCAN_ITERS], below[AGT_SCAN_ITERS];
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
-        kept[it] = root_kind(L, area, blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x, n, min_area, max_area).y;
-        const unsigned long long m = __ballot(kept[it]);
-        below[it] = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) seg[it * (SCAN_THREADS / 64) + wave] = __popcll(m);
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
+        kept[it] = root_kind(L, area, blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x, n, min_area, max_area).y;
+        below[it] = agt_chunk_below(kept[it], it, seg);
     }
     __syncthreads();
     const int first = K.chunk[(size_t)b * K.nchunk + blockIdx.x].y;
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
         if (!kept[it]) continue;
-        const int i = blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x, mine = it * (SCAN_THREADS / 64) + wave;
-        int id = first + below[it];
-#pragma unroll
-        for (int s = 0; s < SCAN_SEGS; s++) id += s < mine ? seg[s] : 0;
+        const int i = blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x;
+        const int id = agt_chunk_rank(first, below[it], it, seg);
         const bool in = id < K.maxc;
         K.cid[(size_t)b * n + i] = in ? id : -1;
         if (in) {
@@ -333,8 +301,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void qf_root_assign(Work K, int n, in
     }
     // a root outside the area limits: no id
 #pragma unroll
-    for (int it = 0; it < SCAN_ITERS; it++) {
-        const int i = blockIdx.x * SCAN_CHUNK + it * SCAN_THREADS + threadIdx.x;
+    for (int it = 0; it < AGT_SCAN_ITERS; it++) {
+        const int i = blockIdx.x * AGT_SCAN_CHUNK + it * AGT_SCAN_THREADS + threadIdx.x;
         if (!kept[it] && i < n && L[i] == i) K.cid[(size_t)b * n + i] = -1;
     }
 }
@@ -491,7 +459,7 @@ __global__ __launch_bounds__(256) void qf_emit(Work K, uint32_t* quads, uint32_t
         const int id = base + threadIdx.x;
         const int v = id < have ? K.c_valid[(size_t)b * K.maxc + id] : 0;
         int total;
-        const int at = run + block_exclusive_sum(v, part, total);
+        const int at = run + agt_block_exclusive_sum(v, part, total);
         if (v && at < K.maxq) {
 #pragma unroll
             for (int j = 0; j < 8; j++) { oq[8 * (size_t)at + j] = iq[8 * (size_t)id + j]; orec[8 * (size_t)at + j] = irec[8 * (size_t)id + j]; }
@@ -506,8 +474,6 @@ __global__ __launch_bounds__(256) void qf_emit(Work K, uint32_t* quads, uint32_t
     }
 }
 
-inline int div_up(long long a, int b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
 
 struct agt_quadfind {
@@ -518,14 +484,8 @@ struct agt_quadfind {
 
 namespace {
 
-bool frames_ok(const agt_quadfind* q, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width, int height, int B)
-{
-    if (!q || !d_frames) return false;
-    if (width < AGT_QUADFIND_MIN_SIZE || width > q->width || height < AGT_QUADFIND_MIN_SIZE || height > q->height || pitch < (size_t)width) return false;
-    if (B < 1 || B > q->max_batch) return false;
-    if (B > 1 && frame_stride < pitch * (size_t)(height - 1) + (size_t)width) return false;
-    return true;
-}
+// the frame rule against the handle's limits
+bool frames_ok(const agt_quadfind* q, const Frames& F) { return q && agt_side::frames_ok(F.p, F.pitch, F.stride, F.w, F.h, 1, F.B, AGT_QUADFIND_MIN_SIZE, q->width, q->height, q->max_batch); }
 
 // steps 1 and 2 of the rule into `label` ([B][h][w])
 int enqueue_labels(agt_quadfind* q, hipStream_t s, const Frames& F, int min_contrast, int32_t* label)
@@ -557,36 +517,31 @@ int agt_quadfind_create(int width, int height, int max_batch, int max_components
     agt_quadfind* q = new (std::nothrow) agt_quadfind();
     if (!q) return AGT_QUADFIND_ERR_ALLOC;
     q->width = width; q->height = height; q->max_batch = max_batch; q->maxc = max_components; q->maxq = max_quads;
-    const size_t B = (size_t)max_batch, n = (size_t)width * height, nt = (size_t)(width / 4) * (height / 4), nc = (size_t)div_up((long long)n, SCAN_CHUNK);
+    const size_t B = (size_t)max_batch, n = (size_t)width * height, nt = (size_t)(width / 4) * (height / 4), nc = (size_t)div_up((long long)n, AGT_SCAN_CHUNK);
     const size_t mc = (size_t)max_components;
     Work& K = q->K;
     K.maxc = max_components; K.maxq = max_quads; K.nchunk = 0;
-    int rc = 0;
-    auto get = [&](auto** p, size_t count) { if (!rc) rc = q->buf.alloc(reinterpret_cast<void**>(p), count * sizeof(**p)); };
-    get(&K.mn, B * nt); get(&K.mx, B * nt); get(&K.MN, B * nt); get(&K.MX, B * nt);
-    get(&K.label, B * n); get(&K.area, B * n); get(&K.cid, B * n);
-    get(&K.chunk, B * nc);
-    get(&K.c_root, B * mc); get(&K.c_area, B * mc); get(&K.c_sup, B * mc * 16);
-    get(&K.c_valid, B * mc); get(&K.c_quad, B * mc * 8); get(&K.c_rec, B * mc);
-    if (rc) { q->buf.free_all(); delete q; return rc; }
+    AgtSideBuffers& m = q->buf;
+    if (m.alloc_n(&K.mn, B * nt) || m.alloc_n(&K.mx, B * nt) || m.alloc_n(&K.MN, B * nt) || m.alloc_n(&K.MX, B * nt) ||
+        m.alloc_n(&K.label, B * n) || m.alloc_n(&K.area, B * n) || m.alloc_n(&K.cid, B * n) ||
+        m.alloc_n(&K.chunk, B * nc) ||
+        m.alloc_n(&K.c_root, B * mc) || m.alloc_n(&K.c_area, B * mc) || m.alloc_n(&K.c_sup, B * mc * 16) ||
+        m.alloc_n(&K.c_valid, B * mc) || m.alloc_n(&K.c_quad, B * mc * 8) || m.alloc_n(&K.c_rec, B * mc)) {
+        agt_side_destroy(q);
+        return AGT_QUADFIND_ERR_ALLOC;
+    }
     *handle_out = q;
     return AGT_QUADFIND_OK;
 }
 
-int agt_quadfind_destroy(agt_quadfind* handle)
-{
-    if (!handle) return AGT_QUADFIND_ERR_ARG;
-    handle->buf.free_all();
-    delete handle;
-    return AGT_QUADFIND_OK;
-}
+int agt_quadfind_destroy(agt_quadfind* handle) { return agt_side_destroy(handle); }
 
 int agt_quadfind_labels(agt_quadfind* handle, void* stream, const uint8_t* d_frames, size_t pitch, size_t frame_stride, int width,
                         int height, int B, int min_contrast, int32_t* d_labels)
 {
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_labels) return AGT_QUADFIND_ERR_ARG;
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
+    if (!frames_ok(handle, F) || !d_labels) return AGT_QUADFIND_ERR_ARG;
     if (min_contrast < 1 || min_contrast > 255) return AGT_QUADFIND_ERR_ARG;
-    Frames F; F.p = d_frames; F.pitch = pitch; F.stride = frame_stride; F.w = width; F.h = height; F.B = B;
     return enqueue_labels(handle, (hipStream_t)stream, F, min_contrast, d_labels);
 }
 
@@ -594,20 +549,20 @@ int agt_quadfind_detect(agt_quadfind* handle, void* stream, const uint8_t* d_fra
                         int height, int B, const agt_quadfind_options* options, float* d_quads, agt_quadfind_record* d_records,
                         int32_t* d_counts)
 {
-    if (!frames_ok(handle, d_frames, pitch, frame_stride, width, height, B) || !d_quads || !d_records || !d_counts) return AGT_QUADFIND_ERR_ARG;
+    const Frames F = { d_frames, pitch, frame_stride, width, height, B };
+    if (!frames_ok(handle, F) || !d_quads || !d_records || !d_counts) return AGT_QUADFIND_ERR_ARG;
     agt_quadfind_options o;
     o.min_contrast = 40; o.min_area = 24; o.max_area = INT32_MAX; o.min_fill_pct = 5;
     if (options) o = *options;
     if (o.min_contrast < 1 || o.min_contrast > 255 || o.min_area < 1 || o.max_area < o.min_area || o.min_fill_pct < 0 || o.min_fill_pct > 100) return AGT_QUADFIND_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    Frames F; F.p = d_frames; F.pitch = pitch; F.stride = frame_stride; F.w = width; F.h = height; F.B = B;
     RC(enqueue_labels(handle, s, F, o.min_contrast, handle->K.label));
     Work K = handle->K;
     const int n = width * height;
-    K.nchunk = div_up(n, SCAN_CHUNK);
-    hipLaunchKernelGGL(qf_root_count, dim3(K.nchunk, B), dim3(SCAN_THREADS), 0, s, K, n, o.min_area, o.max_area);
+    K.nchunk = div_up(n, AGT_SCAN_CHUNK);
+    hipLaunchKernelGGL(qf_root_count, dim3(K.nchunk, B), dim3(AGT_SCAN_THREADS), 0, s, K, n, o.min_area, o.max_area);
     hipLaunchKernelGGL(qf_root_scan, dim3(B), dim3(256), 0, s, K, d_counts);
-    hipLaunchKernelGGL(qf_root_assign, dim3(K.nchunk, B), dim3(SCAN_THREADS), 0, s, K, n, o.min_area, o.max_area);
+    hipLaunchKernelGGL(qf_root_assign, dim3(K.nchunk, B), dim3(AGT_SCAN_THREADS), 0, s, K, n, o.min_area, o.max_area);
     hipLaunchKernelGGL(qf_support, dim3(div_up(n, 256), B), dim3(256), 0, s, K, width, height);
     hipLaunchKernelGGL(qf_quads, dim3(div_up(K.maxc, 64), B), dim3(64), 0, s, K, d_counts, width, height, o.min_fill_pct);
     hipLaunchKernelGGL(qf_emit, dim3(B), dim3(256), 0, s, K, reinterpret_cast<uint32_t*>(d_quads), reinterpret_cast<uint32_t*>(d_records), d_counts);

@@ -8,34 +8,40 @@
 //   the used-station counts come out of one ballot, line e - 1 reaches row e by a shuffle from 48 lanes on, and the four new corners
 //   are read back from lanes 0, 16, 32 and 48, so every lane starts the next pass with the whole quad.
 // Every decision that ends a pass (station counts, the intersection's denominator) is taken on wave-uniform values or a ballot.
+// Shared with the other image stages: the frame arguments and their rule (agt_side_frames.h), the fixed-order butterfly sum (here
+// over a row: agt_wave_sum_fixed<8>) and the bilinear fetch (agt_side_device.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "agt_side_device.h"
+#include "agt_side_frames.h"
+#include "agt_side_math.h"
 #include "../../include/agt_quadfit.h"
 
 #pragma clang fp contract(off)
 
+static_assert(AGT_QUADFIT_OK == agt_side::OK && AGT_QUADFIT_ERR_ARG == agt_side::ERR_ARG && AGT_QUADFIT_ERR_HIP == agt_side::ERR_HIP,
+              "the codes of agt_side_math.h");
+
 namespace {
+
+using agt_side::Frames;
 
 constexpr int QUAD_WAVES = 4;           // quads per workgroup
 constexpr int MIN_USED = 8;             // used stations an edge needs
 
 struct QuadCall {
-    const uint8_t* frames; size_t pitch, frame_stride;
-    int w, h, Q, total;
+    Frames F;
+    int Q, total;
     const uint32_t* quads; const uint8_t* mask;
     double range; int iters; double min_strength;
     uint32_t* out32; double* out64; agt_quad_record* rec; uint8_t* ok; uint8_t* cmask;
 };
 
-__device__ __forceinline__ double row_sum(double x)
-{
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
+// the sum over the 16 lanes of a row (masks 8, 4, 2, 1)
+__device__ __forceinline__ double row_sum(double x) { return agt_wave_sum_fixed<8>(x); }
 
 // corner j of four held in registers (no indexed private array: no scratch)
 __device__ __forceinline__ double pick(const double (&v)[4], int j) { return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3]; }
@@ -61,10 +67,7 @@ __device__ __forceinline__ double sample(const uint8_t* __restrict__ img, size_t
     const bool in = fx >= 0.0 && fx <= (double)(w - 2) && fy >= 0.0 && fy <= (double)(h - 2);         // (NaN and inf fail)
     inside = inside && in;
     const int ix = in ? (int)fx : 0, iy = in ? (int)fy : 0;
-    const double a = x - fx, b = y - fy;
-    const uint8_t* p = img + (size_t)iy * pitch + (size_t)ix;
-    const double i00 = p[0], i10 = p[1], i01 = p[pitch], i11 = p[pitch + 1];
-    return agt_blend4(a, b, i00, i10, i01, i11);
+    return agt_bilinear_u8(img, pitch, ix, iy, x - fx, y - fy);
 }
 
 __global__ __launch_bounds__(64 * QUAD_WAVES) void quad_refine_kernel(QuadCall C)
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void quad_refine_kernel(QuadCall C
 #pragma unroll
         for (int j = 0; j < 4; j++) shoelace += x[j] * y[(j + 1) & 3] - x[(j + 1) & 3] * y[j];
         const double sg = shoelace > 0.0 ? 1.0 : -1.0;
-        const uint8_t* img = C.frames + (size_t)b * C.frame_stride;
+        const uint8_t* img = C.F.p + (size_t)b * C.F.stride;
         const double u = (((double)i + 0.5) / 16.0 - 0.5) * 0.75;
         int refused = AGT_QUAD_OK;
 
@@ -126,8 +129,8 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void quad_refine_kernel(QuadCall C
             double Mc = 0.0, Mn = 0.0, gm = 0.0;
             for (int k = -8; k <= 8; k++) {
                 const double o = r * (double)k / 8.0;
-                const double I1 = sample(img, C.pitch, C.w, C.h, px + (o + 1.0) * nx, py + (o + 1.0) * ny, inside);
-                const double I0 = sample(img, C.pitch, C.w, C.h, px + (o - 1.0) * nx, py + (o - 1.0) * ny, inside);
+                const double I1 = sample(img, C.F.pitch, C.F.w, C.F.h, px + (o + 1.0) * nx, py + (o + 1.0) * ny, inside);
+                const double I0 = sample(img, C.F.pitch, C.F.w, C.F.h, px + (o - 1.0) * nx, py + (o - 1.0) * ny, inside);
                 const double dg = I1 - I0;
                 if (dg > 0.0) {                 // (a dropped station's sums are never used)
                     Mc += dg * dg;
@@ -231,22 +234,20 @@ int agt_quad_refine(void* stream, const uint8_t* d_frames, size_t pitch, size_t 
                     const float* d_quads, const uint8_t* d_mask, int Q, double range_px, int iters, double min_strength,
                     float* d_quads_out, double* d_quads64_out, agt_quad_record* d_records, uint8_t* d_ok, uint8_t* d_corner_mask)
 {
-    if (!d_frames || !d_quads || !d_quads_out || !d_records) return AGT_QUADFIT_ERR_ARG;
-    if (width < 4 || width > AGT_QUADFIT_MAX_SIZE || height < 4 || height > AGT_QUADFIT_MAX_SIZE || pitch < (size_t)width) return AGT_QUADFIT_ERR_ARG;
-    if (B < 1 || Q < 1 || (long long)B * (long long)Q > AGT_QUADFIT_MAX_QUADS) return AGT_QUADFIT_ERR_ARG;
-    if (B > 1 && frame_stride < pitch * (size_t)(height - 1) + (size_t)width) return AGT_QUADFIT_ERR_ARG;
+    if (!agt_side::frames_ok(d_frames, pitch, frame_stride, width, height, 1, B, 4, AGT_QUADFIT_MAX_SIZE, AGT_QUADFIT_MAX_SIZE, INT_MAX)) return AGT_QUADFIT_ERR_ARG;
+    if (!d_quads || !d_quads_out || !d_records) return AGT_QUADFIT_ERR_ARG;
+    if (Q < 1 || (long long)B * (long long)Q > AGT_QUADFIT_MAX_QUADS) return AGT_QUADFIT_ERR_ARG;
     if (!(range_px > 0.0) || !(range_px <= AGT_QUADFIT_MAX_RANGE)) return AGT_QUADFIT_ERR_ARG;              // (NaN fails)
     if (iters < 1 || iters > AGT_QUADFIT_MAX_ITERS) return AGT_QUADFIT_ERR_ARG;
     if (!(min_strength >= 0.0) || !(min_strength <= 1.7976931348623157e308)) return AGT_QUADFIT_ERR_ARG;    // (NaN and inf fail)
 
     QuadCall C;
-    C.frames = d_frames; C.pitch = pitch; C.frame_stride = frame_stride;
-    C.w = width; C.h = height; C.Q = Q; C.total = B * Q;
+    C.F = Frames{ d_frames, pitch, frame_stride, width, height, B };
+    C.Q = Q; C.total = B * Q;
     C.quads = reinterpret_cast<const uint32_t*>(d_quads); C.mask = d_mask;
     C.range = range_px; C.iters = iters; C.min_strength = min_strength;
     C.out32 = reinterpret_cast<uint32_t*>(d_quads_out); C.out64 = d_quads64_out; C.rec = d_records; C.ok = d_ok; C.cmask = d_corner_mask;
-    const int blocks = (C.total + QUAD_WAVES - 1) / QUAD_WAVES;
-    hipLaunchKernelGGL(quad_refine_kernel, dim3(blocks), dim3(64 * QUAD_WAVES), 0, (hipStream_t)stream, C);
+    hipLaunchKernelGGL(quad_refine_kernel, dim3(agt_side::div_up(C.total, QUAD_WAVES)), dim3(64 * QUAD_WAVES), 0, (hipStream_t)stream, C);
     if (hipGetLastError() != hipSuccess) return AGT_QUADFIT_ERR_HIP;
     return AGT_QUADFIT_OK;
 }

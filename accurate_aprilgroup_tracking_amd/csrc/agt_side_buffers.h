@@ -20,6 +20,9 @@ struct AgtSideBuffers {
         return agt_side::OK;
     }
 
+    template <class T>
+    int alloc_n(T** p, size_t count) { return alloc(reinterpret_cast<void**>(p), count * sizeof(T)); }
+
     int upload(void* dst, const void* src, size_t bytes)
     {
         if (!bytes) return agt_side::OK;
@@ -43,3 +46,13 @@ struct AgtSideBuffers {
         allocs.clear();
     }
 };
+
+// the end of a handle made with new whose device memory is all in its member `buf`: also the way out of a create that failed half-way
+template <class Handle>
+int agt_side_destroy(Handle* h)
+{
+    if (!h) return agt_side::ERR_ARG;
+    h->buf.free_all();
+    delete h;
+    return agt_side::OK;
+}

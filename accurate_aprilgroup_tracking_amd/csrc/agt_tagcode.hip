@@ -7,24 +7,34 @@
 // off-diagonal sums vanish exactly (both cell sets are symmetric about the centre), so each needs three data sums; every sum is an
 // xor butterfly over the wave -- a fixed order, the same value in every lane.  The word is a ballot, the family search strides the
 // lanes over the 4n candidates and ends in a wave minimum of (hamming << 16 | 4 i + k), which is the tie rule.
+// Shared with the other image stages: the frame arguments and their rule (agt_side_frames.h), the family's device buffer
+// (agt_side_buffers.h), the fixed-order wave sum and the bilinear fetch (agt_side_device.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <limits.h>
 #include <stdint.h>
 #include <new>
 #include <vector>
 
+#include "agt_side_buffers.h"
 #include "agt_side_device.h"
+#include "agt_side_frames.h"
 #include "../../include/agt_tagcode.h"
 
 #pragma clang fp contract(off)
 
+static_assert(AGT_TAGCODE_OK == agt_side::OK && AGT_TAGCODE_ERR_ARG == agt_side::ERR_ARG && AGT_TAGCODE_ERR_ALLOC == agt_side::ERR_ALLOC &&
+              AGT_TAGCODE_ERR_HIP == agt_side::ERR_HIP, "the codes of agt_side_math.h");
+
 namespace {
+
+using agt_side::Frames;
 
 constexpr int TAG_WAVES = 4;            // quads per workgroup
 
 struct TagCall {
-    const uint8_t* frames; size_t pitch, frame_stride;
-    int w, h, Q, total;
+    Frames F;
+    int Q, total;
     const float* quads; const uint8_t* mask; const int32_t* expected;
     const uint64_t* cand; int n4;
     int max_hamming; double min_margin;
@@ -46,13 +56,6 @@ __host__ __device__ constexpr double border_suu()
     return s;
 }
 constexpr double RING_SUU = ring_suu(), BORDER_SUU = border_suu(), RING_N = 36.0, BORDER_N = 28.0, PAYLOAD_N = 36.0;
-
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
 
 __device__ __forceinline__ uint32_t wave_min(uint32_t x)
 {
@@ -79,10 +82,7 @@ __device__ __forceinline__ Sample sample_point(const double (&H)[9], double u, d
 __device__ __forceinline__ double bilinear(const uint8_t* __restrict__ img, size_t pitch, const Sample& s)
 {
     const double fx = floor(s.x), fy = floor(s.y);
-    const double a = s.x - fx, b = s.y - fy;
-    const uint8_t* p = img + (size_t)(int)fy * pitch + (size_t)(int)fx;
-    const double i00 = p[0], i10 = p[1], i01 = p[pitch], i11 = p[pitch + 1];
-    return agt_blend4(a, b, i00, i10, i01, i11);
+    return agt_bilinear_u8(img, pitch, (int)fx, (int)fy, s.x - fx, s.y - fy);
 }
 
 __global__ __launch_bounds__(64 * TAG_WAVES) void tag_decode_kernel(TagCall C)
@@ -148,24 +148,24 @@ __global__ __launch_bounds__(64 * TAG_WAVES) void tag_decode_kernel(TagCall C)
         const int r2 = j < 10 ? -1 : j < 20 ? 8 : j < 28 ? j - 20 : j - 28;
         const int c2 = j < 10 ? j - 1 : j < 20 ? j - 11 : j < 28 ? -1 : 8;
         const double u2 = cell_coord(c2), v2 = cell_coord(r2);
-        const Sample s1 = sample_point(H, u1, v1, C.w, C.h), s2 = sample_point(H, u2, v2, C.w, C.h);
+        const Sample s1 = sample_point(H, u1, v1, C.F.w, C.F.h), s2 = sample_point(H, u2, v2, C.F.w, C.F.h);
         if (__ballot(s1.degenerate || s2.degenerate) != 0ull) status = AGT_TAG_DEGENERATE;
         else if (__ballot(s1.outside || s2.outside) != 0ull) status = AGT_TAG_OUTSIDE;
         else {
-            const uint8_t* img = C.frames + (size_t)b * C.frame_stride;
-            const double I1 = bilinear(img, C.pitch, s1), I2 = bilinear(img, C.pitch, s2);
+            const uint8_t* img = C.F.p + (size_t)b * C.F.stride;
+            const double I1 = bilinear(img, C.F.pitch, s1), I2 = bilinear(img, C.F.pitch, s2);
             const double wb = payload ? 0.0 : 1.0, wr = ring ? 1.0 : 0.0;
-            const double bk_a = wave_sum(wb * u1 * I1) / BORDER_SUU, bk_b = wave_sum(wb * v1 * I1) / BORDER_SUU, bk_c = wave_sum(wb * I1) / BORDER_N;
-            const double w_a = wave_sum(wr * u2 * I2) / RING_SUU, w_b = wave_sum(wr * v2 * I2) / RING_SUU, w_c = wave_sum(wr * I2) / RING_N;
+            const double bk_a = agt_wave_sum_fixed(wb * u1 * I1) / BORDER_SUU, bk_b = agt_wave_sum_fixed(wb * v1 * I1) / BORDER_SUU, bk_c = agt_wave_sum_fixed(wb * I1) / BORDER_N;
+            const double w_a = agt_wave_sum_fixed(wr * u2 * I2) / RING_SUU, w_b = agt_wave_sum_fixed(wr * v2 * I2) / RING_SUU, w_c = agt_wave_sum_fixed(wr * I2) / RING_N;
             const double Wv = w_a * u1 + w_b * v1 + w_c, Bv = bk_a * u1 + bk_b * v1 + bk_c;
             const double d = I1 - 0.5 * (Wv + Bv);
             const bool bit = payload && d > 0.0;
             const uint64_t ballot = __ballot(bit);
-            contrast = wave_sum(payload ? Wv - Bv : 0.0) / PAYLOAD_N;
+            contrast = agt_wave_sum_fixed(payload ? Wv - Bv : 0.0) / PAYLOAD_N;
             if (!(contrast > 0.0)) { status = AGT_TAG_INVERTED; contrast = 0.0; }
             else {
                 const int n1 = __popcll(ballot), n0 = 36 - n1;
-                const double s_hi = wave_sum(bit ? d : 0.0), s_lo = wave_sum(payload && !bit ? -d : 0.0);
+                const double s_hi = agt_wave_sum_fixed(bit ? d : 0.0), s_lo = agt_wave_sum_fixed(payload && !bit ? -d : 0.0);
                 const double m1 = n1 ? s_hi / (double)n1 : 0.0, m0 = n0 ? s_lo / (double)n0 : 0.0;
                 margin = m1 < m0 ? m1 : m0;
                 // lane 8 r + c holds cell (r, c): reversed, row r's columns 1..6 sit at bits 62 - 8 r .. 57 - 8 r, column 1 highest
@@ -216,7 +216,7 @@ uint64_t rotate_cw(uint64_t code)
 }  // namespace
 
 struct agt_tag_family {
-    hipStream_t stream;
+    AgtSideBuffers buf;     // (buf.stream: the stream of the decodes)
     uint64_t* d_cand;       // [n][4]: code i turned clockwise k times
     int n;
 };
@@ -227,10 +227,7 @@ int agt_tagcode_version(void) { return AGT_TAGCODE_VERSION; }
 
 int agt_tag_family_destroy(agt_tag_family* f)
 {
-    if (!f) return AGT_TAGCODE_OK;
-    if (f->d_cand) (void)hipFree(f->d_cand);
-    delete f;
-    return AGT_TAGCODE_OK;
+    return f ? agt_side_destroy(f) : AGT_TAGCODE_OK;
 }
 
 int agt_tag_family_create(const uint64_t* codes, int n, int bits_per_side, void* stream, agt_tag_family** out)
@@ -247,13 +244,10 @@ int agt_tag_family_create(const uint64_t* codes, int n, int bits_per_side, void*
     }
     agt_tag_family* f = new (std::nothrow) agt_tag_family();
     if (!f) return AGT_TAGCODE_ERR_ALLOC;
-    f->stream = (hipStream_t)stream; f->d_cand = nullptr; f->n = n;
-    const size_t bytes = cand.size() * sizeof(uint64_t);
-    if (hipMalloc((void**)&f->d_cand, bytes) != hipSuccess) { (void)hipGetLastError(); delete f; return AGT_TAGCODE_ERR_ALLOC; }
-    // (the source is a local: it must be read before this returns)
-    if (hipMemcpyAsync(f->d_cand, cand.data(), bytes, hipMemcpyHostToDevice, f->stream) != hipSuccess || hipStreamSynchronize(f->stream) != hipSuccess) {
-        (void)hipGetLastError(); agt_tag_family_destroy(f); return AGT_TAGCODE_ERR_HIP;
-    }
+    f->buf.stream = (hipStream_t)stream; f->d_cand = nullptr; f->n = n;
+    int rc = f->buf.alloc_n(&f->d_cand, cand.size());
+    if (!rc) rc = f->buf.upload(f->d_cand, cand.data(), cand.size() * sizeof(uint64_t));
+    if (rc) { agt_side_destroy(f); return rc; }
     *out = f;
     return AGT_TAGCODE_OK;
 }
@@ -262,23 +256,21 @@ int agt_tag_decode(agt_tag_family* f, const uint8_t* d_frames, size_t pitch, siz
                    const float* d_quads, const uint8_t* d_mask, int Q, const int32_t* d_expected, int max_hamming, double min_margin,
                    agt_tag_record* d_records, uint8_t* d_ok, uint8_t* d_corner_mask, double* d_homography)
 {
-    if (!d_frames || !d_quads || !d_records) return AGT_TAGCODE_ERR_ARG;
-    if (width < 4 || width > AGT_TAGCODE_MAX_SIZE || height < 4 || height > AGT_TAGCODE_MAX_SIZE || pitch < (size_t)width) return AGT_TAGCODE_ERR_ARG;
-    if (B < 1 || Q < 1 || (long long)B * (long long)Q > AGT_TAGCODE_MAX_QUADS) return AGT_TAGCODE_ERR_ARG;
-    if (B > 1 && frame_stride < pitch * (size_t)(height - 1) + (size_t)width) return AGT_TAGCODE_ERR_ARG;
+    if (!agt_side::frames_ok(d_frames, pitch, frame_stride, width, height, 1, B, 4, AGT_TAGCODE_MAX_SIZE, AGT_TAGCODE_MAX_SIZE, INT_MAX)) return AGT_TAGCODE_ERR_ARG;
+    if (!d_quads || !d_records) return AGT_TAGCODE_ERR_ARG;
+    if (Q < 1 || (long long)B * (long long)Q > AGT_TAGCODE_MAX_QUADS) return AGT_TAGCODE_ERR_ARG;
     if (max_hamming < 0 || max_hamming > 36) return AGT_TAGCODE_ERR_ARG;
     if (!(min_margin >= 0.0) || !(min_margin <= 1.7976931348623157e308)) return AGT_TAGCODE_ERR_ARG;      // (NaN and inf fail)
     if (!f) return AGT_TAGCODE_ERR_FAMILY;
 
     TagCall C;
-    C.frames = d_frames; C.pitch = pitch; C.frame_stride = frame_stride;
-    C.w = width; C.h = height; C.Q = Q; C.total = B * Q;
+    C.F = Frames{ d_frames, pitch, frame_stride, width, height, B };
+    C.Q = Q; C.total = B * Q;
     C.quads = d_quads; C.mask = d_mask; C.expected = d_expected;
     C.cand = f->d_cand; C.n4 = 4 * f->n;
     C.max_hamming = max_hamming; C.min_margin = min_margin;
     C.rec = d_records; C.ok = d_ok; C.cmask = d_corner_mask; C.H = d_homography;
-    const int blocks = (C.total + TAG_WAVES - 1) / TAG_WAVES;
-    hipLaunchKernelGGL(tag_decode_kernel, dim3(blocks), dim3(64 * TAG_WAVES), 0, f->stream, C);
+    hipLaunchKernelGGL(tag_decode_kernel, dim3(agt_side::div_up(C.total, TAG_WAVES)), dim3(64 * TAG_WAVES), 0, f->buf.stream, C);
     if (hipGetLastError() != hipSuccess) return AGT_TAGCODE_ERR_HIP;
     return AGT_TAGCODE_OK;
 }

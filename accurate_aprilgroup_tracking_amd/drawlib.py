@@ -6,14 +6,12 @@ import os
 import numpy as np
 
 from . import _sidelib
+from ._sidelib import ERR_ARG, ERR_HIP, ERRORS, OK, vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_draw.so")
 
 VERSION = 100
-OK = 0
-ERR_ARG, ERR_HIP = -1, -5
-ERRORS = {ERR_ARG: "ARG", ERR_HIP: "HIP"}
 MAX_SIZE_PX, MAX_PRIMS, MAX_TOTAL, MAX_POINTS, MAX_COORD, MAX_SIZE, CHUNK = 16384, 4096, 1 << 20, 4096, 32767, 64, 256
 NONE, DISC, SEGMENT = range(3)
 CLEAR = 1
@@ -73,7 +71,6 @@ def prims(records):
 
 def raster(stream, frames_ptr, pitch, frame_stride, width, height, channels, B, prims_ptr, P, flags=0):
     """agt_draw_raster on raw device addresses (ints or None); enqueues only"""
-    vp = lambda a: C.c_void_p(a) if a else None
     check(lib().agt_draw_raster(vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, channels, B, vp(prims_ptr), P, flags),
           "agt_draw_raster")
 
@@ -81,6 +78,5 @@ def raster(stream, frames_ptr, pitch, frame_stride, width, height, channels, B, 
 def pose_lists(stream, points_ptr, dtype, n, B, gate_ptr, gate_stride, width, height, corners_per_tag, radius, thickness, dot_color,
                line_color, dots_ptr, outline_ptr):
     """agt_draw_pose_lists on raw device addresses (ints or None); enqueues only"""
-    vp = lambda a: C.c_void_p(a) if a else None
     check(lib().agt_draw_pose_lists(vp(stream), vp(points_ptr), dtype, n, B, vp(gate_ptr), gate_stride, width, height, corners_per_tag,
                                     radius, thickness, dot_color, line_color, vp(dots_ptr), vp(outline_ptr)), "agt_draw_pose_lists")

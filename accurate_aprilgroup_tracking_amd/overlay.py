@@ -9,6 +9,7 @@ without synchronising.
 import numpy as np
 import torch
 
+from . import _sidelib
 from . import drawlib as D
 from .cv_hip import _raw_stream, _require_gpu
 
@@ -26,8 +27,7 @@ def prims_tensor(prims, device):
 
 def prims_numpy(prims):
     """cuda u8 [B, P, 32] (or its numpy copy) -> structured array [B, P] with the fields of agt_draw_prim (synchronises)"""
-    a = prims.cpu().numpy() if isinstance(prims, torch.Tensor) else np.asarray(prims)
-    return np.ascontiguousarray(a).view(D.PRIM_DTYPE).reshape(a.shape[:-1])
+    return _sidelib.records_numpy(prims, D.PRIM_DTYPE)
 
 
 def draw_primitives(frames, prims, clear=False):
@@ -48,8 +48,8 @@ def draw_primitives(frames, prims, clear=False):
     P = prims.shape[1]
     dev = frames.device
     with torch.cuda.device(dev):
-        D.raster(_raw_stream(dev.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, channels, B,
-                 prims.data_ptr() if P else None, P, D.CLEAR if clear else 0)
+        args = _sidelib.frame_args(frames)
+        D.raster(*args[:-1], channels, args[-1], prims.data_ptr() if P else None, P, D.CLEAR if clear else 0)
     return frames
 
 

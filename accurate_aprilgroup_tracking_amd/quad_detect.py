@@ -8,11 +8,11 @@ Limits: 4-connectivity; a quiet zone under about 2 px merges a tag with its surr
 """
 import collections
 
-import numpy as np
 import torch
 
+from . import _sidelib
 from . import quadfindlib as Q
-from .cv_hip import _raw_stream, _require_gpu
+from .cv_hip import _require_gpu
 
 Found = collections.namedtuple("Found", "quads records counts")
 Found.__doc__ = """QuadDetector.detect's result, all cuda tensors: quads f32 [B, max_quads, 4, 2] (contiguous: quad_refine.refine_quads
@@ -23,12 +23,7 @@ b are candidates in ascending label order; the rest are zero."""
 
 
 def _check_frames(frames, width, height, max_batch):
-    if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3 and frames.stride(2) == 1):
-        raise ValueError("frames must be cuda u8 [B, H, W] with unit pixel stride")
-    B, h, w = frames.shape
-    if not (Q.MIN_SIZE <= w <= width and Q.MIN_SIZE <= h <= height and 1 <= B <= max_batch):
-        raise Q.QuadFindError(Q.ERR_ARG, "frames of shape %s on a QuadDetector for [%d, %d, %d]" % (tuple(frames.shape), max_batch, height, width))
-    return B, h, w
+    return _sidelib.check_frames(frames, Q.MIN_SIZE, width, height, max_batch, Q.QuadFindError, "QuadDetector")
 
 
 class QuadDetector:
@@ -44,13 +39,7 @@ class QuadDetector:
                                 ("max_quads", self.max_quads, 1, self.max_components)):
             if not lo <= v <= hi:
                 raise Q.QuadFindError(Q.ERR_ARG, "QuadDetector(%s=%d), limits %d..%d" % (name, v, lo, hi))
-        self._finders = {}
-
-    def _finder(self, device):
-        if device not in self._finders:
-            with torch.cuda.device(device):
-                self._finders[device] = Q.Finder(self.width, self.height, self.max_batch, self.max_components, self.max_quads)
-        return self._finders[device]
+        self._finder = _sidelib.PerDevice(Q.Finder, self.width, self.height, self.max_batch, self.max_components, self.max_quads)
 
     def detect(self, frames, **options):
         """frames: cuda u8 [B, H, W] (unit pixel stride; any row and frame stride).  options: min_contrast (40), min_area (24),
@@ -67,11 +56,10 @@ class QuadDetector:
 
     def detect_into(self, frames, out, opts=None):
         """detect() into the tensors of `out` (a Found, or any three cuda tensors of those shapes with 4-byte aligned storage)"""
-        B, h, w = _check_frames(frames, self.width, self.height, self.max_batch)
+        _check_frames(frames, self.width, self.height, self.max_batch)
         dev = frames.device
         with torch.cuda.device(dev):
-            self._finder(dev.index).detect(_raw_stream(dev.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B, opts,
-                                           *[t.data_ptr() for t in out])
+            self._finder(dev.index).detect(*_sidelib.frame_args(frames), opts, *[t.data_ptr() for t in out])
         return out
 
     def labels(self, frames, min_contrast=40):
@@ -81,12 +69,10 @@ class QuadDetector:
         dev = frames.device
         out = torch.empty((B, h, w), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            self._finder(dev.index).labels(_raw_stream(dev.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B,
-                                           min_contrast, out.data_ptr())
+            self._finder(dev.index).labels(*_sidelib.frame_args(frames), min_contrast, out.data_ptr())
         return out
 
 
 def records_numpy(records):
     """records tensor (or its numpy copy) -> structured array [B, max_quads] with the fields of agt_quadfind_record (synchronises)"""
-    a = records.cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
-    return np.ascontiguousarray(a).view(Q.RECORD_DTYPE).reshape(a.shape[:-1])
+    return _sidelib.records_numpy(records, Q.RECORD_DTYPE)

@@ -9,11 +9,11 @@ of the four border edges and the lines are intersected.  The seeds come from som
 """
 import collections
 
-import numpy as np
 import torch
 
+from . import _sidelib
 from . import quadfitlib as Q
-from .cv_hip import _raw_stream, _require_gpu
+from .cv_hip import _require_gpu
 
 Refined = collections.namedtuple("Refined", "quads quads64 records ok corner_mask")
 Refined.__doc__ = """refine_quads' result, all cuda tensors: quads f32 [B, Q, 4, 2] (contiguous: tag_decode.decode_quads takes it as
@@ -28,7 +28,7 @@ def refine_quads(frames, quads, mask=None, range_px=2.0, iters=2, min_strength=4
     an eighth of the edge's length); a quad that moves further than 2 range_px is refused.  iters: passes, 1..8.  min_strength: the
     weakest edge's mean step height a quad needs.  Enqueues on the current stream and returns a Refined without synchronising."""
     _require_gpu()
-    assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3 and frames.stride(2) == 1, "frames must be cuda u8 [B, H, W] with unit pixel stride"
+    assert _sidelib.is_gray_frames(frames), _sidelib.GRAY_FRAMES
     B, h, w = frames.shape
     assert quads.dtype == torch.float32 and quads.is_cuda and quads.is_contiguous() and quads.dim() == 4 and quads.shape[0] == B and tuple(quads.shape[2:]) == (4, 2)
     nq = quads.shape[1]
@@ -39,12 +39,11 @@ def refine_quads(frames, quads, mask=None, range_px=2.0, iters=2, min_strength=4
                   torch.empty((B, nq, Q.RECORD_DTYPE.itemsize), dtype=torch.uint8, device=dev), torch.empty((B, nq), dtype=torch.uint8, device=dev),
                   torch.empty((B, 4 * nq), dtype=torch.uint8, device=dev))
     with torch.cuda.device(dev):
-        Q.refine(_raw_stream(dev.index), frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B, quads.data_ptr(),
-                 None if mask is None else mask.data_ptr(), nq, range_px, iters, min_strength, *[t.data_ptr() for t in out])
+        Q.refine(*_sidelib.frame_args(frames), quads.data_ptr(), None if mask is None else mask.data_ptr(), nq, range_px, iters,
+                 min_strength, *[t.data_ptr() for t in out])
     return out
 
 
 def records_numpy(records):
     """records tensor (or its numpy copy) -> structured array [B, Q] with the fields of agt_quad_record (synchronises)"""
-    a = records.cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
-    return np.ascontiguousarray(a).view(Q.RECORD_DTYPE).reshape(a.shape[:-1])
+    return _sidelib.records_numpy(records, Q.RECORD_DTYPE)

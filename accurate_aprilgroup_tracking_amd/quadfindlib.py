@@ -6,14 +6,12 @@ import os
 import numpy as np
 
 from . import _sidelib
+from ._sidelib import ERR_ALLOC, ERR_ARG, ERR_HIP, ERRORS, OK, vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_quadfind.so")
 
 VERSION = 100
-OK = 0
-ERR_ARG, ERR_ALLOC, ERR_HIP = -1, -2, -5
-ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_HIP: "HIP"}
 MIN_SIZE, MAX_SIZE, MAX_BATCH, MAX_COMPONENTS, MAX_QUADS = 8, 8192, 64, 65536, 65536
 FLAG_QUADS, FLAG_COMPONENTS = 1, 2
 DEFAULTS = dict(min_contrast=40, min_area=24, max_area=2 ** 31 - 1, min_fill_pct=5)
@@ -60,13 +58,7 @@ check = QuadFindError.check
 
 def options(**kw):
     """the defaults with `kw` over them -> Options; an unknown name or a value that no int32 holds is refused here"""
-    unknown = sorted(set(kw) - set(DEFAULTS))
-    if unknown:
-        raise TypeError("unknown quad finder option(s) %s (known: %s)" % (", ".join(unknown), ", ".join(DEFAULTS)))
-    o = dict(DEFAULTS, **kw)
-    for k, v in o.items():
-        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
-            raise QuadFindError(ERR_ARG, "option %s = %r" % (k, v))
+    o = _sidelib.make_options(DEFAULTS, tuple(DEFAULTS), (), QuadFindError, "quad finder", kw)
     return Options(*[int(o[k]) for k in ("min_contrast", "min_area", "max_area", "min_fill_pct")])
 
 
@@ -82,13 +74,11 @@ class Finder(_sidelib.Handle):
 
     def detect(self, stream, frames_ptr, pitch, frame_stride, width, height, B, opts, quads_ptr, records_ptr, counts_ptr):
         """agt_quadfind_detect on raw device addresses (ints or None); opts: Options or None; enqueues only"""
-        vp = lambda a: C.c_void_p(a) if a else None
         check(self.L.agt_quadfind_detect(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B,
                                          C.byref(opts) if opts is not None else None, vp(quads_ptr), vp(records_ptr), vp(counts_ptr)),
               "agt_quadfind_detect")
 
     def labels(self, stream, frames_ptr, pitch, frame_stride, width, height, B, min_contrast, labels_ptr):
         """agt_quadfind_labels on raw device addresses; enqueues only"""
-        vp = lambda a: C.c_void_p(a) if a else None
         check(self.L.agt_quadfind_labels(self.h, vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, int(min_contrast),
                                          vp(labels_ptr)), "agt_quadfind_labels")

@@ -6,14 +6,12 @@ import os
 import numpy as np
 
 from . import _sidelib
+from ._sidelib import ERR_ARG, ERR_HIP, ERRORS, OK, vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_quadfit.so")
 
 VERSION = 100
-OK = 0
-ERR_ARG, ERR_HIP = -1, -5
-ERRORS = {ERR_ARG: "ARG", ERR_HIP: "HIP"}
 MAX_SIZE, MAX_QUADS, MAX_COORD, MIN_EDGE, MAX_RANGE, MAX_ITERS = 16384, 1 << 20, 1048576.0, 8.0, 16.0, 8
 QUAD_OK, QUAD_MASKED, QUAD_DEGENERATE, QUAD_SHORT, QUAD_WEAK, QUAD_DIVERGED = range(6)
 STATUS_NAMES = ["OK", "MASKED", "DEGENERATE", "SHORT", "WEAK", "DIVERGED"]
@@ -53,7 +51,6 @@ check = QuadFitError.check
 def refine(stream, frames_ptr, pitch, frame_stride, width, height, B, quads_ptr, mask_ptr, Q, range_px, iters, min_strength,
            quads_out_ptr, quads64_out_ptr, records_ptr, ok_ptr, corner_mask_ptr):
     """agt_quad_refine on raw device addresses (ints or None); enqueues only"""
-    vp = lambda a: C.c_void_p(a) if a else None
     check(lib().agt_quad_refine(vp(stream), vp(frames_ptr), pitch, frame_stride, width, height, B, vp(quads_ptr), vp(mask_ptr), Q,
                                 float(range_px), int(iters), float(min_strength), vp(quads_out_ptr), vp(quads64_out_ptr), vp(records_ptr),
                                 vp(ok_ptr), vp(corner_mask_ptr)), "agt_quad_refine")

@@ -13,6 +13,7 @@ import collections
 import numpy as np
 import torch
 
+from . import _sidelib
 from . import tagcodelib as T
 from .cv_hip import _raw_stream, _require_gpu
 
@@ -59,7 +60,7 @@ def decode_quads(frames, quads, family, mask=None, expected=None, max_hamming=2,
     mask: cuda u8 [B, Q] or None, expected: cuda i32 [Q] or None (then a verdict also needs id == expected[q] and rot == 0).
     Enqueues on the current stream and returns a Decoded without synchronising."""
     _require_gpu()
-    assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3 and frames.stride(2) == 1, "frames must be cuda u8 [B, H, W] with unit pixel stride"
+    assert _sidelib.is_gray_frames(frames), _sidelib.GRAY_FRAMES
     B, h, w = frames.shape
     assert quads.dtype == torch.float32 and quads.is_cuda and quads.is_contiguous() and quads.dim() == 4 and quads.shape[0] == B and tuple(quads.shape[2:]) == (4, 2)
     Q = quads.shape[1]
@@ -69,9 +70,9 @@ def decode_quads(frames, quads, family, mask=None, expected=None, max_hamming=2,
         assert expected.dtype == torch.int32 and expected.is_cuda and expected.is_contiguous() and tuple(expected.shape) == (Q,)
     dev = frames.device
     out = _outputs(B, Q, dev)
-    family.handle(dev.index).decode(frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, B, quads.data_ptr(),
-                                    None if mask is None else mask.data_ptr(), Q, None if expected is None else expected.data_ptr(),
-                                    max_hamming, min_margin, *[t.data_ptr() for t in out])
+    # (the family's handle carries the stream)
+    family.handle(dev.index).decode(*_sidelib.frame_args(frames)[1:], quads.data_ptr(), None if mask is None else mask.data_ptr(), Q,
+                                    None if expected is None else expected.data_ptr(), max_hamming, min_margin, *[t.data_ptr() for t in out])
     return out
 
 
@@ -82,8 +83,7 @@ def _outputs(B, Q, dev):
 
 def records_numpy(records):
     """records tensor (or its numpy copy) -> structured array [B, Q] with the fields of agt_tag_record (synchronises)"""
-    a = records.cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
-    return np.ascontiguousarray(a).view(T.RECORD_DTYPE).reshape(a.shape[:-1])
+    return _sidelib.records_numpy(records, T.RECORD_DTYPE)
 
 
 _TURN = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])     # square corner j -> corner j - 1

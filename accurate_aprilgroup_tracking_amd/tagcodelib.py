@@ -6,14 +6,14 @@ import os
 import numpy as np
 
 from . import _sidelib
+from ._sidelib import ERR_ALLOC, ERR_ARG, ERR_HIP, OK, vp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagt_tagcode.so")
 
 VERSION = 100
-OK = 0
-ERR_ARG, ERR_ALLOC, ERR_HIP, ERR_FAMILY = -1, -2, -5, -13
-ERRORS = {ERR_ARG: "ARG", ERR_ALLOC: "ALLOC", ERR_HIP: "HIP", ERR_FAMILY: "FAMILY"}
+ERR_FAMILY = -13
+ERRORS = {**_sidelib.ERRORS, ERR_FAMILY: "FAMILY"}
 MAX_CODES, MAX_SIZE, MAX_QUADS, MAX_COORD = 16384, 16384, 1 << 20, 1048576.0
 TAG_OK, TAG_MASKED, TAG_DEGENERATE, TAG_OUTSIDE, TAG_INVERTED, TAG_NO_MATCH, TAG_LOW_MARGIN = range(7)
 STATUS_NAMES = ["OK", "MASKED", "DEGENERATE", "OUTSIDE", "INVERTED", "NO_MATCH", "LOW_MARGIN"]
@@ -62,13 +62,11 @@ class Family(_sidelib.Handle):
         codes = np.ascontiguousarray(np.asarray(codes, np.uint64).reshape(-1))
         self.n = codes.size
         self.h = C.c_void_p()
-        check(self.L.agt_tag_family_create(C.c_void_p(codes.ctypes.data), self.n, int(bits_per_side), C.c_void_p(stream) if stream else None,
-                                           C.byref(self.h)), "agt_tag_family_create")
+        check(self.L.agt_tag_family_create(C.c_void_p(codes.ctypes.data), self.n, int(bits_per_side), vp(stream), C.byref(self.h)), "agt_tag_family_create")
 
     def decode(self, frames_ptr, pitch, frame_stride, width, height, B, quads_ptr, mask_ptr, Q, expected_ptr, max_hamming, min_margin,
                records_ptr, ok_ptr, corner_mask_ptr, homography_ptr):
         """agt_tag_decode on raw device addresses (ints or None); enqueues only"""
-        vp = lambda a: C.c_void_p(a) if a else None
         check(self.L.agt_tag_decode(self.h, vp(frames_ptr), pitch, frame_stride, width, height, B, vp(quads_ptr), vp(mask_ptr), Q,
                                     vp(expected_ptr), int(max_hamming), float(min_margin), vp(records_ptr), vp(ok_ptr), vp(corner_mask_ptr),
                                     vp(homography_ptr)), "agt_tag_decode")

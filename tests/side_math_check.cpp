@@ -1,15 +1,18 @@
-// side_math_check.cpp -- a CPU driver of csrc/agt_side_math.h, the host code the side libraries share.  tests/test_side_math.py builds it
+// side_math_check.cpp -- a CPU driver of csrc/agt_side_math.h and csrc/agt_side_frames.h, the host code the side libraries share.  tests/test_side_math.py builds it
 // with the host compiler under AddressSanitizer and UBSan, runs it and holds what it prints to its expectations.
 //   lm MAX_ITERS FTOL LAMBDA0 UP DOWN LAMBDA_MAX COST0 N_RESIDUALS TRIAL...
 //                       lm_options ("-" keeps a default), then lm_solve with callables that replay the trial costs (the last one repeats;
 //                       "u": the step is not solved, "f": it fails) -> "rc steps commits", the report, the lambda of every step
 //   chol FILE           FILE: int32 n, n x n doubles A (row-major), n doubles b -> "ok" or "refused", then x
 //   tilt TAU_X TAU_Y    the 18 doubles of tilt_matrices
+//   frames P PITCH FRAME_STRIDE WIDTH HEIGHT CHANNELS B MIN_SIZE MAX_W MAX_H MAX_B
+//                       frames_ok with P = 0 for a null pointer, anything else for some address (never read) -> "1" or "0"
 // Doubles are printed as %a.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string>
+#include "../accurate_aprilgroup_tracking_amd/csrc/agt_side_frames.h"
 #include "../accurate_aprilgroup_tracking_amd/csrc/agt_side_math.h"
 #include "../include/agt_calib.h"
 
@@ -68,6 +71,14 @@ int main(int argc, char** argv)
         for (double x : m) printf("%a\n", x);
         return 0;
     }
-    fprintf(stderr, "usage: side_math_check lm OPTIONS... COST0 N_RESIDUALS TRIAL... | chol FILE | tilt TAU_X TAU_Y\n");
+    if (mode == "frames" && argc == 13) {
+        static const uint8_t somewhere = 0;
+        long long v[11];
+        for (int i = 0; i < 11; i++) v[i] = strtoll(argv[2 + i], nullptr, 10);
+        printf("%d\n", (int)agt_side::frames_ok(v[0] ? &somewhere : nullptr, (size_t)v[1], (size_t)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6],
+                                                (int)v[7], (int)v[8], (int)v[9], (int)v[10]));
+        return 0;
+    }
+    fprintf(stderr, "usage: side_math_check lm OPTIONS... COST0 N_RESIDUALS TRIAL... | chol FILE | tilt TAU_X TAU_Y | frames ARGUMENTS...\n");
     return 2;
 }

@@ -1,5 +1,5 @@
-"""CPU: the host code the side libraries share (csrc/agt_side_math.h: the Levenberg-Marquardt loop, cholesky_solve, the tilt matrices)
-driven without a device by tests/side_math_check.cpp -- a program of its own, built with the host compiler under AddressSanitizer and
+"""CPU: the host code the side libraries share (csrc/agt_side_math.h: the Levenberg-Marquardt loop, cholesky_solve, the tilt matrices;
+csrc/agt_side_frames.h: the rule for a batch of frames) driven without a device by tests/side_math_check.cpp -- a program of its own, built with the host compiler under AddressSanitizer and
 UBSan (which also shows that the header needs no HIP) and run as a subprocess."""
 import ctypes
 import math
@@ -144,3 +144,37 @@ def test_tilt_matrices_against_the_oracle(program, oracle, tau):
     err = max(np.abs(m[:9] - M).max(), np.abs(m[9:] - Mi).max())
     print("tau %s: largest difference %.3e" % (tau, err))
     assert err < 1e-15
+
+
+# ---- agt_side::frames_ok: one case per clause of the rule.  A library in the style of the quad finder: sizes 8 .. 640 x 480, up to 4
+# frames, one byte a pixel; every case changes one thing about a batch that is accepted.
+INT_MAX = 2 ** 31 - 1
+FRAMES = dict(p=1, pitch=100, stride=0, w=100, h=50, channels=1, B=1, min_size=8, max_w=640, max_h=480, max_B=4)
+FRAMES_CASES = [
+    ("as it is", {}, True),
+    ("null pointer", dict(p=0), False),
+    ("width min - 1", dict(w=7, pitch=7), False), ("width min", dict(w=8, pitch=8), True),
+    ("width max", dict(w=640, pitch=640), True), ("width max + 1", dict(w=641, pitch=641), False),
+    ("height min - 1", dict(h=7), False), ("height min", dict(h=8), True),
+    ("height max", dict(h=480), True), ("height max + 1", dict(h=481), False),
+    ("pitch row - 1", dict(pitch=99), False), ("pitch row", dict(pitch=100), True), ("pitch beyond the row", dict(pitch=128), True),
+    ("B 0", dict(B=0), False), ("B 1, frame_stride 0", dict(B=1, stride=0), True), ("B -1", dict(B=-1), False),
+    ("B max_B", dict(B=4, stride=5000), True), ("B max_B + 1", dict(B=5, stride=5000), False),
+    ("no cap, B INT_MAX", dict(B=INT_MAX, max_B=INT_MAX, stride=5000), True),
+    # the second frame may begin where the last row of the first ends: pitch (h - 1) + row = 128 * 49 + 100
+    ("B 2, frames touching", dict(B=2, pitch=128, stride=128 * 49 + 100), True),
+    ("B 2, one byte less", dict(B=2, pitch=128, stride=128 * 49 + 100 - 1), False),
+    ("B 2, frame_stride 0", dict(B=2, stride=0), False),
+    # three bytes a pixel: the row is 300 bytes.  The pitch and the stride that pass for one channel must not
+    ("3 channels, pitch of 1 channel", dict(channels=3, pitch=100), False), ("3 channels, pitch row", dict(channels=3, pitch=300), True),
+    ("1 channel, stride for 1 channel", dict(B=2, pitch=300, stride=300 * 49 + 100), True),
+    ("3 channels, stride for 1 channel", dict(B=2, channels=3, pitch=300, stride=300 * 49 + 100), False),
+    ("3 channels, frames touching", dict(B=2, channels=3, pitch=300, stride=300 * 49 + 300), True),
+    ("3 channels, one byte less", dict(B=2, channels=3, pitch=300, stride=300 * 49 + 300 - 1), False),
+]
+
+
+@pytest.mark.parametrize("name, change, accepted", FRAMES_CASES, ids=[c[0] for c in FRAMES_CASES])
+def test_frames_ok(program, name, change, accepted):
+    args = dict(FRAMES, **change)
+    assert program("frames", *[args[k] for k in FRAMES]).split() == ["1" if accepted else "0"]
